@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py - BEVGen stage-2 sampling path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 N > 1: the script launches its own N ranks (one per GPU, `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ...`)
 unless it already runs under a launcher (WORLD_SIZE set); inside, the RCCL world size must equal N or the run fails.
@@ -14,14 +14,20 @@ per GPU), no data-path collective; the only RCCL traffic is the final gather of 
 `strong_scaling` leg (16 scenes in total) is added to the line.
 
 Default arithmetic mode: f16x3 (every GEMM / conv / attention product as three f16 MFMAs on hi/lo splits, fp32 accumulation: fp32-class accuracy,
-bit-identical greedy tokens on every parity fixture); the line also carries a one-step `exact_fp32_mode` leg (exact fp32 MFMA).
+bit-identical greedy tokens on every parity fixture); the --full line also carries a one-step `exact_fp32_mode` leg (exact fp32 MFMA).
 
-One SHORT JSON line on rank 0: the contract keys, `roofline` for the dominant kernel of the workload (the LDS-DMA split-precision GEMM; `traffic` measured by
-this run through two `rocprofv3 --pmc` child passes, tools/pmc_inrun.py), `cpu_baseline` (the CPU oracle timed on this host), and LAST a flat `legs` object with the
+A plain run sets up, warms up, times the K steps and prints ONE short JSON line on rank 0: the contract keys (`metric`, `value`, `unit`, `higher_is_better`,
+`dtype`, `ms_per_step` = wall milliseconds of one timed step) and LAST a flat `legs` object with what the timed steps' own events give (median / p99 step,
+MaskGit iteration, VQGAN decode, gather).  --dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy (float32): `pixels` (the uint8 pixels
+[scenes, cams, 3, 256, 256] the step returns on rank 0; above 12 Mi elements a fixed sample, numpy default_rng(0), sorted flat indices) and `token_ids` (rank 0's
+MaskGit ids [scenes * cams, 16, 16]).  Inputs, weights and sampler seeds depend on the arguments only, so two builds can be compared output for output.
+
+--full adds every side measurement to the line: `roofline` for the dominant kernel of the workload (the LDS-DMA split-precision GEMM, from a separate profiled
+pass; `traffic` measured by two `rocprofv3 --pmc` child passes, tools/pmc_inrun.py), `cpu_baseline` (the CPU oracle timed on this host), and in `legs` the
 scalar result of every other leg - at N = 1: Route A decode (BASELINE config 4: ms per decode step mean / median / p99, decode-attention roofline fraction by
 SURVEY 8(d)'s bytes and by storage bytes, whole-step fraction; f32 / f16 KV cache, f16 weights, density 0.35, split path), config 5 on one GPU, the released 3-camera
 shape, single-scene latency, exact-fp32 and f16-weights modes; at N > 1: the strong-scaling leg and BASELINE configs[4] across the ranks (64 sequences per GPU,
-token ids gathered to rank 0), per-rank step times.  The unabridged per-leg objects go to gpurun_out/bench_detail_n<N>.json (`detail_file`).
+token ids gathered to rank 0), per-rank step times.  The unabridged per-leg objects of a --full run go to bench_out/bench_detail_n<N>.json (`detail_file`).
 """
 from __future__ import annotations
 
@@ -57,7 +63,13 @@ def parse():
     ap.add_argument("--decode-steps", type=int, default=0, help="0 = a full decode (N image tokens)")
     ap.add_argument("--precision", default="f16x3", choices=["fp32", "f16x3"], help="fp32 = exact fp32 MFMA; f16x3 = split-precision products (both bit-exact on the parity fixtures)")
     ap.add_argument("--no-exact-leg", action="store_true", help="skip the additional one-step run in exact-fp32 mode")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the last timed step's outputs as DIR/<name>.npy (float32)")
+    ap.add_argument("--full", action="store_true", help="also run the side measurements (profiled pass + roofline, other modes / shapes / configs, Route A decode, "
+                                                          "CPU baseline; the --no-* switches thin them out) and write the detail file")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 # Control-flow dry run (tests/test_bench_cpu.py): BEVGEN_BENCH_DRYRUN=1 swaps the library context for a shape-only stub and RCCL for gloo so that the N > 1 paths of this
@@ -110,7 +122,9 @@ class _StubContext:
 
 
 def self_launch(args):
-    """--gpus N without a launcher: become `torch.distributed.run` with N ranks on this node."""
+    """--gpus N without a launcher: run `torch.distributed.run` with N ranks on this node as a child process and exit with its status (a fresh child, not an
+    exec: this process has already opened the HIP runtime to count the GPUs)."""
+    import subprocess
     import torch
 
     have = args.gpus if DRY_RUN else torch.cuda.device_count()
@@ -122,7 +136,7 @@ def self_launch(args):
         port = s.getsockname()[1]
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={args.gpus}", "--master-addr", "127.0.0.1", "--master-port", str(port),
            os.path.abspath(__file__)] + sys.argv[1:]
-    os.execv(sys.executable, cmd)
+    sys.exit(subprocess.call(cmd))
 
 
 def gemm_algorithmic_bytes(cfg, batch):
@@ -169,6 +183,24 @@ def pmc_traffic(kernel):
 def pct(xs, q):
     import numpy as np
     return float(np.percentile(np.asarray(xs, dtype=np.float64), q)) if len(xs) else None
+
+
+DUMP_MAX_ELEMENTS = 12 * 2 ** 20   # per dumped array: 48 MiB of float32, the whole dump stays under 64 MB
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: every array as out_dir/<name>.npy in float32 (token ids < 2^24 and uint8 pixels are exact).  An array above DUMP_MAX_ELEMENTS elements is
+    written as a fixed sample of its flattened values: numpy default_rng(0) draws the flat indices without replacement, sorted - the same positions for the same
+    shape in every run."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in arrays.items():
+        a = t.cpu().numpy().astype(np.float32)
+        if a.size > DUMP_MAX_ELEMENTS:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, DUMP_MAX_ELEMENTS, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 _SD_CACHE = {}
@@ -507,12 +539,15 @@ def main():
     from bevgen_amd import synthetic
     from bevgen_amd.parallel import gather_scenes
 
-    def run_route_m(precision, steps, warmup, cams, batch, weights="f32"):
+    def run_route_m(precision, steps, warmup, cams, batch, weights="f32", profile=True, outputs=None):
+        """profile: the separate profiled pass after the timed steps (roofline / kernel shares; --full).  outputs: a dict that receives the last timed step's
+        token ids (this rank's) and gathered pixels (rank 0) on the host."""
         cfg, ctx, _ = build_route_m(cams, batch, local_rank, precision, weights)
         bt = synthetic.make_batch(cfg, batch, seed=1000 + rank)  # each rank: its own shard of scenes
         bt = {k: v.to(ctx.device) for k, v in bt.items()}
         ev = [[Event(enable_timing=True) for _ in range(4)] for _ in range(steps)]
         seeds = []
+        last = {}
 
         def one_step(e=None):
             if e: e[0].record()
@@ -526,6 +561,8 @@ def main():
             if e: e[2].record()
             out = gather_scenes(px.reshape(batch, cams, 3, px.shape[-2], px.shape[-1]), dist)
             if e: e[3].record()
+            if outputs is not None:
+                last["token_ids"], last["pixels"] = ids, out
             return out
 
         for _ in range(warmup):
@@ -544,17 +581,21 @@ def main():
         if dist:
             dist.barrier()
         elapsed = time.perf_counter() - t0
-        # ... and the per-kernel roofline comes from a SEPARATE pass of the same step with a HIP-event pair around every GEMM / convolution / attention launch
-        # (two extra hipEventRecords per launch would otherwise sit inside the headline number)
-        prof_steps = min(steps, 2)
-        ctx.profile_begin()
-        tp0 = time.perf_counter()
-        for i in range(prof_steps):
-            one_step()
-        sync()
-        prof_elapsed = time.perf_counter() - tp0
-        prof = ctx.profile_end()
-        prof["_pass"] = {"steps": prof_steps, "ms": prof_elapsed * 1e3, "launches": 0}
+        if outputs is not None:
+            outputs.update({k: v.cpu() for k, v in last.items() if v is not None})
+        prof = None
+        if profile:
+            # ... and the per-kernel roofline comes from a SEPARATE pass of the same step with a HIP-event pair around every GEMM / convolution / attention launch
+            # (two extra hipEventRecords per launch would otherwise sit inside the headline number)
+            prof_steps = min(steps, 2)
+            ctx.profile_begin()
+            tp0 = time.perf_counter()
+            for i in range(prof_steps):
+                one_step()
+            sync()
+            prof_elapsed = time.perf_counter() - tp0
+            prof = ctx.profile_end()
+            prof["_pass"] = {"steps": prof_steps, "ms": prof_elapsed * 1e3, "launches": 0}
         t = torch.tensor([elapsed, mine], dtype=torch.float64, device=ctx.device)
         per_rank = [t.clone() for _ in range(world)] if dist else [t]
         if dist:
@@ -565,9 +606,15 @@ def main():
         ctx.close()
         return max(float(x[0]) for x in per_rank), prof, parts, cfg
 
-    elapsed, prof, parts, cfg_m = run_route_m(args.precision, args.steps, args.warmup, args.cams, args.batch)
+    outputs = {} if args.dump_outputs else None
+    elapsed, prof, parts, cfg_m = run_route_m(args.precision, args.steps, args.warmup, args.cams, args.batch, profile=args.full, outputs=outputs)
+    if outputs is not None and rank == 0:
+        dump_outputs(args.dump_outputs, outputs)
+    if not args.full:
+        # a plain run measures the headline only: every side leg below belongs to --full
+        args.no_extra_legs = args.no_decode_leg = args.no_cpu_baseline = args.no_exact_leg = True
     strong = None
-    if world > 1 and 16 % world == 0:
+    if args.full and world > 1 and 16 % world == 0:
         s_steps = max(2, min(args.steps, 5))
         e_s, _, p_s, _ = run_route_m(args.precision, s_steps, 1, args.cams, 16 // world)   # 16 scenes in total, sharded
         strong = {"scaling": "strong", "global_batch": 16, "scenes_per_gpu": 16 // world, "steps": s_steps, "value": 16 * s_steps / e_s, "unit": "scenes/s", "ms_per_step": e_s * 1e3 / s_steps,
@@ -630,12 +677,15 @@ def main():
         "ms_per_maskgit_iteration": float(np.mean(parts["generate"])) / args.timesteps,
         "vqgan_decode_ms_per_scene": float(np.mean(parts["vq_decode"])) / args.batch,
         "gather_ms_per_step": float(np.mean(parts["gather"])),
-        "roofline": roof(prof, args.precision, measure=True),
-        "kernel_time_share": {k: v["ms"] / prof["_pass"]["ms"] for k, v in prof.items() if v["launches"]},
-        "kernel_tflops": {k: (v["work"] / (v["ms"] * 1e-3) / 1e12) for k, v in prof.items() if v["launches"] and k in ("gemm", "gemm_small", "conv3x3", "attention")},
-        "profiled_pass": {"steps": prof["_pass"]["steps"], "ms_per_step": prof["_pass"]["ms"] / prof["_pass"]["steps"],
-                          "note": "roofline / kernel_time_share / kernel_tflops come from this separate pass of the same step with a HIP-event pair around every hot launch; `value` is timed without it"},
     }
+    if prof is not None:
+        detail.update({
+            "roofline": roof(prof, args.precision, measure=True),
+            "kernel_time_share": {k: v["ms"] / prof["_pass"]["ms"] for k, v in prof.items() if v["launches"]},
+            "kernel_tflops": {k: (v["work"] / (v["ms"] * 1e-3) / 1e12) for k, v in prof.items() if v["launches"] and k in ("gemm", "gemm_small", "conv3x3", "attention")},
+            "profiled_pass": {"steps": prof["_pass"]["steps"], "ms_per_step": prof["_pass"]["ms"] / prof["_pass"]["steps"],
+                              "note": "roofline / kernel_time_share / kernel_tflops come from this separate pass of the same step with a HIP-event pair around every hot launch; `value` is timed without it"},
+        })
     line = detail
     if DRY_RUN:
         line["dry_run"] = True
@@ -670,7 +720,7 @@ def main():
         e1, _, p1, _ = run_route_m(args.precision, 3, 1, args.cams, 1)
         line["single_scene_latency"] = {"value": e1 * 1e3 / 3, "unit": "ms per scene", "higher_is_better": False, "ms_per_maskgit_iteration": float(np.mean(p1["generate"])) / args.timesteps,
                                         "config": f"Route M, {args.cams}x256x256, batch 1, 3 steps"}
-    if world == 1 and (DRY_RUN or not args.no_extra_legs) and args.batch == 16:
+    if world == 1 and args.full and (DRY_RUN or not args.no_extra_legs) and args.batch == 16:
         # No multi-GPU node has been available to builder or driver: the 16-scene STRONG-scaling leg at N GPUs puts 16 / N scenes on each GPU with no data-path
         # collective, so one GPU running batch 16 / N is that leg's per-GPU load.  prediction(N) = N x scenes/s at batch 16 / N (an upper bound: the gather of 19 MB
         # of uint8 pixels to rank 0 and launch skew come on top); N = 1 is the headline itself.
@@ -741,24 +791,27 @@ def main():
         line["cpu_baseline"] = cpu_baseline(args.cams, args.timesteps, args.cpu_baseline)
 
     # ---- what is printed: ONE short JSON line (contract keys + compact `roofline` / `cpu_baseline` + flat scalars per leg, `legs` LAST so that it survives a tail
-    #      cut); everything above goes, unabridged, to the detail file next to it
-    detail_path = os.path.join(ROOT, "gpurun_out", f"bench_detail_n{n_gpus}.json")
-    try:
-        os.makedirs(os.path.dirname(detail_path), exist_ok=True)
-        json.dump(detail, open(detail_path, "w"), indent=1)
-    except OSError as e:
-        detail_path = f"not written: {e}"
+    #      cut); with --full everything above goes, unabridged, to the detail file under bench_out/
+    detail_path = None
+    if args.full:
+        detail_path = os.path.join(ROOT, "bench_out", f"bench_detail_n{n_gpus}.json")
+        try:
+            os.makedirs(os.path.dirname(detail_path), exist_ok=True)
+            json.dump(detail, open(detail_path, "w"), indent=1)
+        except OSError as e:
+            detail_path = f"not written: {e}"
     short = {k: detail[k] for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data", "config",
                                     "rccl_world_size", "per_rank_ms_per_step")}
     if DRY_RUN:
         short["dry_run"] = True
-    r = detail["roofline"]
-    short["roofline"] = {k: r[k] for k in ("bound", "achieved", "peak", "unit", "frac", "traffic", "kernel", "launches", "avg_us")}
-    if r.get("traffic_detail"):
-        short["roofline"]["traffic_over_algorithmic"] = r["traffic_detail"]["traffic_over_algorithmic"]
-        short["roofline"]["traffic_source"] = "in-run rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE child passes"
-    elif r.get("traffic_note"):
-        short["roofline"]["traffic_note"] = r["traffic_note"][:100]
+    if "roofline" in detail:
+        r = detail["roofline"]
+        short["roofline"] = {k: r[k] for k in ("bound", "achieved", "peak", "unit", "frac", "traffic", "kernel", "launches", "avg_us")}
+        if r.get("traffic_detail"):
+            short["roofline"]["traffic_over_algorithmic"] = r["traffic_detail"]["traffic_over_algorithmic"]
+            short["roofline"]["traffic_source"] = "in-run rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE child passes"
+        elif r.get("traffic_note"):
+            short["roofline"]["traffic_note"] = r["traffic_note"][:100]
     if "cpu_baseline" in detail:
         c = detail["cpu_baseline"]
         short["cpu_baseline"] = {"value": c["value"], "unit": c["unit"], "cores": c["cores"], "kind": c["kind"],
@@ -781,10 +834,11 @@ def main():
                         "kernel trace of the replayed graph; traffic = in-run PMC at short contexts"}
         if "error" in tr:
             short["roofline_decode_attention"]["traffic_note"] = str(tr["error"])[:100]
-    elif DRY_RUN:
+    elif DRY_RUN and args.full:
         short["roofline_decode_attention"] = {"bound": "hbm", "kernel": "ar_attn_fused_kernel<kv=f16, G=1, w=f16>", "achieved": None, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": None,
                                               "launches": 0, "avg_us": None, "traffic": None}
-    short["detail_file"] = os.path.relpath(detail_path, ROOT) if os.path.isabs(detail_path) else detail_path
+    if detail_path is not None:
+        short["detail_file"] = os.path.relpath(detail_path, ROOT) if os.path.isabs(detail_path) else detail_path
 
     def dshort(d):
         ra, rs = d["roofline_decode_attention"], d["decode_step_roofline"]
@@ -795,8 +849,10 @@ def main():
                    if isinstance(ra.get("kernel_trace"), dict) and "avg_us" in ra["kernel_trace"] else {})}
 
     legs = {"ms_per_step_median": rnd(detail["ms_per_step_median"], 2), "ms_per_step_p99": rnd(detail["ms_per_step_p99"], 2), "ms_per_maskgit_iteration": rnd(detail["ms_per_maskgit_iteration"], 3),
-            "vqgan_decode_ms_per_scene": rnd(detail["vqgan_decode_ms_per_scene"], 3), "gather_ms_per_step": rnd(detail["gather_ms_per_step"], 3),
-            "kernel_tflops": {k: rnd(v, 1) for k, v in detail["kernel_tflops"].items()}, "kernel_time_share": {k: rnd(v, 3) for k, v in detail["kernel_time_share"].items() if k != "_pass"}}
+            "vqgan_decode_ms_per_scene": rnd(detail["vqgan_decode_ms_per_scene"], 3), "gather_ms_per_step": rnd(detail["gather_ms_per_step"], 3)}
+    if "kernel_tflops" in detail:
+        legs.update({"kernel_tflops": {k: rnd(v, 1) for k, v in detail["kernel_tflops"].items()},
+                     "kernel_time_share": {k: rnd(v, 3) for k, v in detail["kernel_time_share"].items() if k != "_pass"}})
     if strong is not None:
         legs["strong_scaling"] = {"global_batch": 16, "scenes_per_s": rnd(strong["value"]), "ms_per_step": rnd(strong["ms_per_step"], 2), "per_rank_ms_per_step": [rnd(x, 2) for x in strong["per_rank_ms_per_step"]]}
     if c5_multi is not None:

@@ -23,7 +23,7 @@ def _run(cmd, extra_env=None):
 
 def test_bench_world_2_control_flow_under_gloo():
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", str(_free_port()),
-           "bench.py", "--gpus", "2", "--steps", "3", "--warmup", "1", "--batch", "4"]
+           "bench.py", "--gpus", "2", "--steps", "3", "--warmup", "1", "--batch", "4", "--full"]
     r = _run(cmd)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -50,7 +50,7 @@ def test_bench_world_8_control_flow_under_gloo():
     """The real rank count of BASELINE configs[2] / configs[4]: 8 ranks (gloo, stub context): weak leg 16 scenes per rank, the strong leg 16 / 8 = 2 scenes per rank,
     config 5 with 64 sequences per rank gathered to rank 0 (512 rows)."""
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "8", "--master-addr", "127.0.0.1", "--master-port", str(_free_port()),
-           "bench.py", "--gpus", "8", "--steps", "2", "--warmup", "1"]
+           "bench.py", "--gpus", "8", "--steps", "2", "--warmup", "1", "--full"]
     r = _run(cmd, {"OMP_NUM_THREADS": "1"})
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -80,7 +80,7 @@ def test_bench_self_launch_and_world_size_mismatch():
 
 
 def test_bench_single_rank_dry_run_line_shape():
-    r = _run([sys.executable, "bench.py", "--steps", "2", "--warmup", "1", "--batch", "2"])
+    r = _run([sys.executable, "bench.py", "--steps", "2", "--warmup", "1", "--batch", "2", "--full"])
     assert r.returncode == 0, r.stderr[-3000:]
     d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][0])
     assert d["n_gpus"] == 1 and d["metric"].startswith("multi-view scenes/sec") and d["unit"] == "scenes/s" and d["vs_baseline"] is None
@@ -93,10 +93,41 @@ def test_bench_single_rank_dry_run_line_shape():
 
 
 def test_bench_single_gpu_predictions_of_the_scaling_legs():
-    """At the default batch (16) the N = 1 line states what one GPU does at the per-GPU load of the 2 / 4 / 8-GPU strong-scaling legs (batch 8 / 4 / 2)."""
-    r = _run([sys.executable, "bench.py", "--steps", "2", "--warmup", "1"])
+    """At the default batch (16) the N = 1 --full line states what one GPU does at the per-GPU load of the 2 / 4 / 8-GPU strong-scaling legs (batch 8 / 4 / 2)."""
+    r = _run([sys.executable, "bench.py", "--steps", "2", "--warmup", "1", "--full"])
     assert r.returncode == 0, r.stderr[-3000:]
     d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][0])
     p = d["legs"]["scaling_prediction_from_one_gpu"]
     assert set(p["strong_16_scenes"]) == {"2", "4", "8"} and set(p["per_gpu_scenes_per_s_at_batch"]) == {"8", "4", "2"} and set(p["weak_16_per_gpu"]) == {"2", "4", "8"}
     assert abs(p["weak_16_per_gpu"]["8"] - 8 * d["value"]) / d["value"] < 1e-2
+
+
+def test_bench_plain_run_times_the_headline_only():
+    """Without --full the run sets up, warms up, times --steps steps and prints the contract keys: no profiled pass, side leg, CPU baseline or detail file."""
+    r = _run([sys.executable, "bench.py", "--steps", "3", "--warmup", "1", "--batch", "2"])
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    assert d["metric"].startswith("multi-view scenes/sec") and d["unit"] == "scenes/s" and d["higher_is_better"] is True and d["dtype"].startswith("f32")
+    assert d["steps"] == 3 and d["warmup"] == 1 and abs(d["value"] - 2 * 3 / (d["ms_per_step"] * 3e-3)) / d["value"] < 1e-6
+    assert not {"roofline", "roofline_decode_attention", "cpu_baseline", "detail_file"} & set(d)
+    assert set(d["legs"]) == {"ms_per_step_median", "ms_per_step_p99", "ms_per_maskgit_iteration", "vqgan_decode_ms_per_scene", "gather_ms_per_step"}
+
+
+def test_bench_dump_outputs_is_reproducible(tmp_path):
+    """--dump-outputs writes the last timed step's pixels and token ids as float32 .npy files, under 64 MB in all (the 16-scene pixels as a fixed sample), and the
+    same arguments give the same arrays."""
+    import numpy as np
+
+    runs = []
+    for i in range(2):
+        out = tmp_path / f"run{i}"
+        r = _run([sys.executable, "bench.py", "--steps", "2", "--warmup", "1", "--dump-outputs", str(out)])
+        assert r.returncode == 0, r.stderr[-3000:]
+        assert sum(f.stat().st_size for f in out.iterdir()) < 64e6
+        runs.append({f.stem: np.load(f) for f in out.glob("*.npy")})
+    a, b = runs
+    assert set(a) == {"pixels", "token_ids"} and all(v.dtype == np.float32 for v in a.values())
+    assert a["token_ids"].shape == (16 * 6, 16, 16) and a["pixels"].ndim == 1 and 0 < a["pixels"].size < 16 * 6 * 3 * 256 * 256
+    assert all(np.array_equal(a[k], b[k]) for k in a)

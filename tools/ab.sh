@@ -26,7 +26,7 @@ if [ $W = m ]; then
   export BEVGEN_BENCH_NO_PMC=1
   for i in $(seq ${ROUNDS:-3}); do for v in $VARIANTS; do
     select_variant $v
-    python bench.py --steps 3 --warmup 1 --no-decode-leg --no-extra-legs --no-cpu-baseline --no-exact-leg "$@" 2>/dev/null | python -c "
+    python bench.py --full --steps 3 --warmup 1 --no-decode-leg --no-extra-legs --no-cpu-baseline --no-exact-leg "$@" 2>/dev/null | python -c "
 import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); l=d['legs']; print('$TAG', 'scenes/s', round(d['value'],3), 'ms/step', round(d['ms_per_step'],1), 'it', round(l['ms_per_maskgit_iteration'],2), 'vq/scene', round(l.get('vqgan_decode_ms_per_scene',0),2), {k: round(x,3) for k,x in l['kernel_time_share'].items()}, {k: round(x,1) for k,x in l['kernel_tflops'].items()})" | tee -a $OUT
   done; done
 elif [ $W = decode ]; then

@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""stdin: one bench.py JSON line -> the decode-leg numbers."""
+"""stdin: one `bench.py --full` JSON line -> the decode-leg numbers."""
 import json, sys
 d = json.loads(sys.stdin.read().strip().splitlines()[-1])
 print("scenes/s", round(d["value"], 3), "| ms/decode-step", round(d.get("ms_per_decode_step", 0), 4), "| decode scenes/s", round(d.get("decode_scenes_per_s", 0), 3),
