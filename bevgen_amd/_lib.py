@@ -69,6 +69,7 @@ SIGNATURES = {
     "bevgen_ar_prefill": (_i, [_p, _p, _p, _p, _i, _p]),
     "bevgen_ar_logits": (_i, [_p, _p, _p]),
     "bevgen_ar_decode_step": (_i, [_p, _p, _p]),
+    "bevgen_ar_forward": (_i, [_p, _p, _p, _p, _i, _p, _i, _p, _p, _p, _p, _p, _p]),
     "bevgen_ar_sample": (_i, [_p, _p, _p, _p, _i, _i, _i, _f, _i, _p, _i, _p, _p, _p]),
     "bevgen_ar_sample_forced": (_i, [_p, _p, _p, _p, _i, _i, _i, _f, _i, _p, _i, _p, _p, _p, _p]),
     "bevgen_vq_decode": (_i, [_p, _p, _i, _i, _i, _i, _p, _p]),

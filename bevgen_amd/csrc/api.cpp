@@ -196,7 +196,18 @@ int bevgen_ar_decode_step(bevgen_ctx* ctx, const int64_t* tok, void* stream) {
     });
 }
 
-int bevgen_ar_sample(bevgen_ctx* ctx, const int64_t* cond, const float* I_inv, const float* E_inv, int B, int steps, int top_k, float temperature, int greedy,
+int bevgen_ar_forward(bevgen_ctx* ctx, const int64_t* cond, const float* I_inv, const float* E_inv, int B, const int64_t* ids, int n_steps, float* logits,
+                      const int64_t* target, const float* weight, float* nll, float* loss, void* stream) {
+    return guarded(ctx, [&] {
+        need_final(ctx);
+        BG_REQUIRE(cond && I_inv && E_inv && ids, "ar_forward: null input");
+        BG_REQUIRE(B >= 1 && (ctx->cfg.max_batch <= 0 || B <= ctx->cfg.max_batch), "ar_forward: batch %d exceeds max_batch %d", B, ctx->cfg.max_batch);
+        BG_REQUIRE(target || (!nll && !loss && !weight), "ar_forward: d_nll / d_loss / d_weight need d_target");
+        ar_forward(*ctx, cond, I_inv, E_inv, B, ids, n_steps, logits, target, weight, nll, loss, (hipStream_t)stream);
+    });
+}
+
+int bevgen_ar_sample(bevgen_ctx* ctx, const int64_t* cond,const float* I_inv, const float* E_inv, int B, int steps, int top_k, float temperature, int greedy,
                      const float* noise_u, int samples_per_layout, int64_t* out, float* step_logits, void* stream) {
     return guarded(ctx, [&] {
         need_final(ctx);

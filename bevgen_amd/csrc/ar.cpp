@@ -191,21 +191,11 @@ void sparse_self_attention_op(Ctx& c, const float* q, const float* k, const floa
     launch_attention(a, s);
 }
 
-// ------------------------------------------------------------------------------------------------ prefill
-// samples_per_layout = S > 1 (BASELINE config 5): consecutive groups of S sequences share their condition (BEV ids and cameras), so the condition
-// prefix is pushed through the stack once per LAYOUT (B / S sequences) and its K/V rows are then replicated into the S cache slots of the group.
-void ar_prefill(Ctx& c, const int64_t* cond, const float* I_inv, const float* E_inv, int B, hipStream_t s, int samples_per_layout) {
+// persistent per-batch state of a decode (K/V cache of every layer, geometric embeddings, newest hidden row, device step counter): zeroed cache, step 0
+static void ar_state_setup(Ctx& c, int B, hipStream_t s) {
     const auto& g = c.cfg;
-    BG_REQUIRE(g.route == BEVGEN_ROUTE_AR, "context was not created for the autoregressive route");
-    BG_REQUIRE(B >= 1, "batch must be positive");
-    const int S = samples_per_layout < 1 ? 1 : samples_per_layout;
-    BG_REQUIRE(B % S == 0, "batch %d is not a multiple of samples_per_layout %d", B, S);
-    const int G = B / S;   // layouts = sequences actually prefilled
-    const int D = c.D, H = c.H, K = c.K, L = c.L;
+    const int D = c.D, H = c.H, L = c.L;
     auto& st = c.ars;
-    // decode_path = auto: the split layer's QKV operand image is packed by the first batch that will run it (S sequences per workgroup only on the fused paths)
-    if (effective_decode_path(c, B, fused_path(c, B, S) ? S : 1) == BEVGEN_DECODE_SPLIT) ctx_pack_split_qkv(c, s);
-    // persistent per-batch state
     const size_t cache_b = (size_t)g.num_layers * B * H * L * 64 * cache_elem_bytes(c);
     const size_t img_b = g.image_embed ? (size_t)B * g.num_cams * c.T * D * sizeof(float) : 0;
     const size_t need = 2 * cache_b + img_b + (size_t)B * g.num_cams * D * sizeof(float) + (size_t)B * D * sizeof(float) + 16 * 256;
@@ -222,6 +212,23 @@ void ar_prefill(Ctx& c, const int64_t* cond, const float* I_inv, const float* E_
     HIP_CHECK(hipMemsetAsync(st.kcache, 0, cache_b, s));
     HIP_CHECK(hipMemsetAsync(st.vcache, 0, cache_b, s));
     HIP_CHECK(hipMemsetAsync(st.d_step, 0, sizeof(int), s));
+}
+
+// ------------------------------------------------------------------------------------------------ prefill
+// samples_per_layout = S > 1 (BASELINE config 5): consecutive groups of S sequences share their condition (BEV ids and cameras), so the condition
+// prefix is pushed through the stack once per LAYOUT (B / S sequences) and its K/V rows are then replicated into the S cache slots of the group.
+void ar_prefill(Ctx& c, const int64_t* cond, const float* I_inv, const float* E_inv, int B, hipStream_t s, int samples_per_layout) {
+    const auto& g = c.cfg;
+    BG_REQUIRE(g.route == BEVGEN_ROUTE_AR, "context was not created for the autoregressive route");
+    BG_REQUIRE(B >= 1, "batch must be positive");
+    const int S = samples_per_layout < 1 ? 1 : samples_per_layout;
+    BG_REQUIRE(B % S == 0, "batch %d is not a multiple of samples_per_layout %d", B, S);
+    const int G = B / S;   // layouts = sequences actually prefilled
+    const int D = c.D, H = c.H, K = c.K, L = c.L;
+    auto& st = c.ars;
+    // decode_path = auto: the split layer's QKV operand image is packed by the first batch that will run it (S sequences per workgroup only on the fused paths)
+    if (effective_decode_path(c, B, fused_path(c, B, S) ? S : 1) == BEVGEN_DECODE_SPLIT) ctx_pack_split_qkv(c, s);
+    ar_state_setup(c, B, s);
 
     // workspace: the decode-step buffers first (stable addresses), then the prefill activations
     const size_t rows = (size_t)G * K;
@@ -634,6 +641,123 @@ void ar_sample(Ctx& c, const int64_t* cond, const float* I_inv, const float* E_i
     head_and_pick(w.logits, q);
     HIP_CHECK(hipEventRecord(c.graph_ev_out, q));
     HIP_CHECK(hipStreamWaitEvent(s, c.graph_ev_out, 0));
+}
+
+// ------------------------------------------------------------------------------------------------ one-pass teacher-forced forward + token scoring
+// GPT.forward over the K condition rows AND the first n image rows in decode order (gpt:319-391; shared_step's cross-entropy ar_lm:277-349) as ONE batched pass:
+// the prefill's layer loop over R = K + n rows per sequence instead of n single-row decode steps.  Input row K + s embeds ids[b, fwd_idx[s]]; logits row s comes from
+// hidden row K - 1 + s.  The mask is causal in decode order, so no computed row sees the pad rows K + N .. L, which are never computed.  The context is left as after
+// ar_prefill + n ar_decode_step calls with the same tokens: cache rows [0, R) of every layer, hidden = row R - 1, step counters = n.
+//
+// Workspace rule.  The layer loop is the outer one, so that the masked bias and the key-tile lists of a layer (keep_heads x R x Rpad floats: 359 MB at config 4 with
+// per-head layouts, the largest single item) are built once per LAYER (once per CALL when the layers share a layout) and never per group; the residual stream x of all B
+// sequences therefore lives across layers (B x R x D floats).  Everything else of a layer - ln rows, q|k|v, the MLP hidden rows, Q and the fp32 K/V image the flash
+// kernel reads: 13 D floats per row - is allocated for one GROUP of Bg = max(1, min(B, 4096 / R)) sequences and reused by the groups in turn: at most 4096 rows, or one
+// sequence (2368 rows at config 4), whatever B is.  The head runs in chunks of at most 2048 rows of one sequence.
+void ar_forward(Ctx& c, const int64_t* cond, const float* I_inv, const float* E_inv, int B, const int64_t* ids, int n, float* logits, const int64_t* target,
+                const float* weight, float* nll, float* loss, hipStream_t s) {
+    const auto& g = c.cfg;
+    BG_REQUIRE(g.route == BEVGEN_ROUTE_AR, "context was not created for the autoregressive route");
+    BG_REQUIRE(B >= 1, "batch must be positive");
+    BG_REQUIRE(n >= 1 && n <= c.N, "ar_forward: n_steps=%d out of range [1,%d]", n, c.N);
+    const int D = c.D, H = c.H, K = c.K, L = c.L, V = c.V;
+    const int R = K + n, Rpad = (int)round_up(R, 32);
+    BG_REQUIRE(R <= L, "ar_forward: %d condition + %d image rows exceed the sequence length %d", K, n, L);
+    auto& st = c.ars;
+    if (effective_decode_path(c, B, 1) == BEVGEN_DECODE_SPLIT) ctx_pack_split_qkv(c, s);   // decode steps may follow
+    ar_state_setup(c, B, s);
+    st.G = 1;
+    st.pick_embeds = false;
+
+    const int Bg = std::max(1, std::min(B, 4096 / R));
+    const size_t rows_g = (size_t)Bg * R;
+    const int CH = std::min(n, 2048);   // head chunk (rows of one sequence)
+    const int Hk = c.keep_heads;
+    const size_t kv_g = (size_t)Bg * H * Rpad * 64;
+    const size_t fwd_b = ((size_t)B * R * D + (size_t)B * K * D + rows_g * D * 3 + rows_g * 3 * D + rows_g * 4 * D + (size_t)Bg * H * R * 64 + 2 * kv_g + (size_t)Hk * R * Rpad +
+                          (size_t)CH * D + (logits ? 0 : (size_t)CH * V) + (size_t)B * n) * sizeof(float) +
+                         attn_tiles_elems(Hk, R, Rpad) * sizeof(uint16_t) + 32 * 256;
+    c.arena.reserve(step_ws_bytes(c, B) + fwd_b);
+    c.arena.reset();
+    (void)step_ws(c, B);   // the decode-step buffers keep their addresses at the start of the arena
+    float* x = c.arena.get<float>((size_t)B * R * D);
+    float* cx = c.arena.get<float>((size_t)B * K * D);
+    float* xn = c.arena.get<float>(rows_g * D);
+    float* x2 = c.arena.get<float>(rows_g * D);
+    float* h = c.arena.get<float>(rows_g * D);
+    float* qkv = c.arena.get<float>(rows_g * 3 * D);
+    float* m1 = c.arena.get<float>(rows_g * 4 * D);
+    float* Q = c.arena.get<float>((size_t)Bg * H * R * 64);
+    float* tk = c.arena.get<float>(kv_g);   // exact fp32 K / V of the group's rows, padded to the attention's key tile (rows R .. Rpad stay zero)
+    float* tv = c.arena.get<float>(kv_g);
+    float* bias = c.arena.get<float>((size_t)Hk * R * Rpad);
+    uint16_t* tiles = c.arena.get<uint16_t>(attn_tiles_elems(Hk, R, Rpad));
+    float* hn = c.arena.get<float>((size_t)CH * D);
+    float* ltile = logits ? nullptr : c.arena.get<float>((size_t)CH * V);
+    float* wnll = c.arena.get<float>((size_t)B * n);
+    HIP_CHECK(hipMemsetAsync(tk, 0, kv_g * sizeof(float), s));
+    HIP_CHECK(hipMemsetAsync(tv, 0, kv_g * sizeof(float), s));
+
+    // ---- embeddings: condition rows [0, K), image rows [K, R) in decode order
+    if (g.image_embed)
+        launch_camera_embed(I_inv, E_inv, c.image_plane, c.pf("img_embed.weight"), c.pf("cam_embed.weight"), st.img_embed, st.c_embed, B, g.num_cams, c.T, D, s);
+    launch_cond_embed(cond, c.pf("cond_tok_emb.weight"), c.pf("cond_pos_emb"), g.bev_embed ? c.pf("bev_grid") : nullptr, g.bev_embed ? c.pf("bev_embed.weight") : nullptr,
+                      g.bev_embed ? c.pf("bev_embed.bias") : nullptr, g.bev_embed ? c.pf("bev_cam_pos_emb") : nullptr, st.c_embed, cx, B, g.num_cams, K, D, g.cond_vocab_size, s);
+    HIP_CHECK(hipMemcpy2DAsync(x, (size_t)R * D * 4, cx, (size_t)K * D * 4, (size_t)K * D * 4, B, hipMemcpyDeviceToDevice, s));
+    launch_ar_seq_embed(ids, c.pf("x_tok_emb.weight"), st.img_embed, c.pf("x_pos_emb"), c.fwd_idx, x, B, n, R, K, c.N, D, g.vocab_size + 1, s);
+
+    // ---- layers
+    const int kvd = cache_dtype(c);
+    const size_t eb = cache_elem_bytes(c);
+    const size_t layer_bytes = (size_t)B * H * L * 64 * eb;
+    const size_t seq_bytes = (size_t)H * L * 64 * eb;
+    for (int i = 0; i < g.num_layers; ++i) {
+        const ArLayer& l = c.ar[i];
+        if (i == 0 || c.keep_layers > 1) {   // shared layout (density 1): one bias image and one set of tile lists per call
+            launch_build_masked_bias(c.attn_bias, c.vis_of_layer(i), bias, Hk, R, R, Rpad, L, 0.125f, s);
+            launch_build_attn_tiles(bias, (long)R * Rpad, Rpad, Hk, R, Rpad, tiles, s);
+        }
+        for (int b0 = 0; b0 < B; b0 += Bg) {
+            const int nb = std::min(Bg, B - b0);
+            const int rows = nb * R;
+            float* xg = x + (size_t)b0 * R * D;
+            char* kcb = reinterpret_cast<char*>(st.kcache) + i * layer_bytes + b0 * seq_bytes;
+            char* vcb = reinterpret_cast<char*>(st.vcache) + i * layer_bytes + b0 * seq_bytes;
+            launch_layernorm(xg, D, l.ln1_w, l.ln1_b, xn, D, rows, D, 1e-5f, s);
+            gemm(xn, D, l.wqkv, D, l.bqkv, qkv, 3 * D, rows, 3 * D, D, ACT_NONE, nullptr, 0, s);
+            launch_ar_qkv_scatter(qkv, Q, tk, tv, 0, nb, H, R, 0, Rpad, s);          // what this pass's attention reads
+            launch_ar_qkv_scatter(qkv, nullptr, kcb, vcb, kvd, nb, H, R, 0, L, s);   // the persistent cache rows [0, R) the decode steps read (fp32 or fp16)
+            AttnArgs a{};
+            a.Q = Q; a.K = tk; a.V = tv; a.bias = bias; a.R = xn; a.O = x2;
+            a.B = nb; a.H = H; a.Nq = R; a.Nk_pad = Rpad;
+            a.q_bstride = (long)H * R * 64; a.q_hstride = (long)R * 64;
+            a.kv_bstride = (long)H * Rpad * 64; a.kv_hstride = (long)Rpad * 64;
+            a.ldbias = Rpad; a.bias_head_stride = Hk > 1 ? (long)R * Rpad : 0; a.scale = 0.125f;
+            a.tiles = tiles; a.tiles_head_stride = Hk > 1 ? (long)cdiv(R, 128) * (Rpad / 32 + 1) : 0; a.tiles_ld = Rpad / 32 + 1;
+            a.o_bstride = (long)R * D; a.o_qstride = D; a.o_hstride = 64;
+            launch_attention(a, s);   // x2 = ln1(x) + attn
+            launch_layernorm(x2, D, l.ln2_w, l.ln2_b, h, D, rows, D, 1e-5f, s);
+            gemm(h, D, l.mlp0_w, D, l.mlp0_b, m1, 4 * D, rows, 4 * D, D, ACT_GELU, nullptr, 0, s);
+            gemm(m1, 4 * D, l.mlp2_w, 4 * D, l.mlp2_b, xg, D, rows, D, 4 * D, ACT_NONE, x2, D, s);
+        }
+    }
+
+    // ---- state hand-over: as after n decode steps
+    launch_gather_rows(x, st.hidden, B, R - 1, R, D, s);
+    launch_set_i32(st.d_step, n, s);
+    st.step = n;
+
+    // ---- ln_f + head + scoring, per sequence in row chunks: logits row s <- hidden row K - 1 + s.  The SAME chunking whether or not the caller wants the logits (then the
+    // head GEMM writes straight into d_logits, else into a tile that the row kernel consumes at once): nll / loss are bit-identical between the two forms
+    for (int b = 0; b < B; ++b)
+        for (int s0 = 0; s0 < n; s0 += CH) {
+            const int rows = std::min(CH, n - s0);
+            float* lg = logits ? logits + ((size_t)b * n + s0) * V : ltile;
+            launch_layernorm(x + ((size_t)b * R + K - 1 + s0) * D, D, c.pf("ln_f.weight"), c.pf("ln_f.bias"), hn, D, rows, D, 1e-5f, s);
+            gemm(hn, D, c.pf("head.weight"), D, nullptr, lg, V, rows, V, D, ACT_NONE, nullptr, 0, s);
+            launch_ar_score_rows(lg, V, target, weight, c.fwd_idx, b, s0, rows, c.N, V, nll ? nll + (size_t)b * n + s0 : nullptr, wnll + (size_t)b * n + s0, s);
+        }
+    if (loss) launch_mean_fixed_order(wnll, (long)B * n, loss, s);
 }
 
 }  // namespace bevgen

@@ -404,6 +404,12 @@ struct ArPickTail {
 void launch_ar_pick(const float* logits, int ldl, const float* u /*[steps, rows] or null*/, const int* d_step /*or null: u is this step's row*/, const int64_t* forced,
                     int64_t* out, int rows, int V, int top_k, float temperature, hipStream_t s, const ArPickTail* tail = nullptr);
 
+// Route A token scoring (ar_lm:349 per row): rows [s0, s0 + rows) in decode order of sequence b, logits [rows, ldl]; nll[r] = logsumexp - logit[target[b, fwd_idx[s0 + r]]]
+// (nll may be null), wnll[r] = weight[b, fwd_idx[s0 + r]] * nll[r] (weight null = 1); target null: only the NaN / inf check of the rows (BG_ST_NONFINITE_LOGITS)
+void launch_ar_score_rows(const float* logits, int ldl, const int64_t* target /*[B, N] camera-major*/, const float* weight, const int64_t* fwd_idx, int b, int s0, int rows,
+                          int N, int V, float* nll, float* wnll, hipStream_t s);
+void launch_mean_fixed_order(const float* x, long n, float* out, hipStream_t s);   // out[0] = sum(x) / n, double accumulation in a fixed order (bit-reproducible)
+
 // ---------------------------------------------------------------- vq.hip
 void launch_codebook_gather(const int64_t* ids, const float* codebook, float* out, int rows, int dim, int n_embed, hipStream_t s);
 // NHWC [n,hw,C] -> NCHW [n,C,hw] with optional per-channel x*std+mean and clamp to [0,1] (bev_utils/util.py:97-118)

@@ -208,6 +208,8 @@ void ar_decode_step(Ctx& c, const int64_t* tok, hipStream_t s);
 void ar_sample(Ctx& c, const int64_t* cond, const float* I_inv, const float* E_inv, int B, int steps, int top_k, float temperature, int greedy,
                const float* noise_u, int samples_per_layout, const int64_t* forced, int64_t* out, float* step_logits, hipStream_t s);
 int ar_step_times(Ctx& c, float* out_ms, int cap);
+void ar_forward(Ctx& c, const int64_t* cond, const float* I_inv, const float* E_inv, int B, const int64_t* ids, int n_steps, float* logits, const int64_t* target,
+                const float* weight, float* nll, float* loss, hipStream_t s);
 // vqdec.cpp
 void vq_finalize(Ctx& c);
 void vq_decode(Ctx& c, const int64_t* ids, const float* latents_nchw, int n, int lat_h, int lat_w, int out_mode, void* out, hipStream_t s);
@@ -226,6 +228,10 @@ void launch_build_masked_bias(const float* add /*[L,L] or null*/, const SparseVi
                               hipStream_t s);
 void launch_ar_step_embed(const int64_t* tok, const float* tok_emb, const float* img_embed, const float* pos_emb, const int64_t* fwd_idx, const int* d_step,
                           float* x, int B, int C, int T, int D, int vocab_rows, hipStream_t s);
+void launch_ar_seq_embed(const int64_t* ids /*[B, N] camera-major*/, const float* tok_emb, const float* img_embed, const float* pos_emb, const int64_t* fwd_idx,
+                         float* x /*[B, rows_per_seq, D]: rows row0 .. row0 + n_steps of every sequence*/, int B, int n_steps, int rows_per_seq, int row0, int N, int D,
+                         int vocab_rows, hipStream_t s);
+void launch_set_i32(int* p, int v, hipStream_t s);
 void launch_store_tokens(const int64_t* tok, const int64_t* fwd_idx, const int* d_step, int64_t* out, int B, int N, hipStream_t s);
 void launch_gather_rows(const float* x, float* out, int B, int row, int rows_per_batch, int D, hipStream_t s);
 void launch_replicate_prefix(void* kc, void* vc, int layers, int B, int H, int L, int rows, int src, int dst0, int count, int elem_bytes, hipStream_t s);

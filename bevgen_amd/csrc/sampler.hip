@@ -309,6 +309,85 @@ void launch_ar_pick(const float* logits, int ldl, const float* u, const int* d_s
     LAUNCH_CHECK();
 }
 
+// ---------------------------------------------------------------------------------------------- Route A token scoring (teacher-forced cross-entropy)
+// shared_step's F.cross_entropy(logits, target) (cond_transformer_multi_view.py:349) per row: nll = logsumexp(row) - row[target].  One wave per logits row; the row is
+// read once with coalesced 16-byte loads (lane l holds float4 l, l + 64, ...) and stays in registers for the maximum and the sum; V > 64 * 4 * SCORE_V4 or V % 4 != 0
+// walks the row twice from memory instead.  Row r of the chunk is decode position s0 + r of sequence b: its target / weight sit at camera-major index fwd_idx[s0 + r].
+// A NaN / inf logit raises BG_ST_NONFINITE_LOGITS exactly as ar_pick_kernel does; a target outside [0, V) gives a NaN nll.
+constexpr int SCORE_V4 = 8;   // float4 per lane held in registers: V <= 2048
+template <bool REG>
+__global__ __launch_bounds__(256) void ar_score_rows_kernel(const float* __restrict__ logits, int ldl, const int64_t* __restrict__ target, const float* __restrict__ weight,
+                                                            const int64_t* __restrict__ fwd_idx, long b, int s0, int rows, int N, int V, float* __restrict__ nll,
+                                                            float* __restrict__ wnll, unsigned* __restrict__ status) {
+    const int lane = threadIdx.x & 63;
+    const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (r >= rows) return;   // (whole waves: no cross-lane operation is skipped by part of a wave)
+    const float* lr = logits + (long)r * ldl;
+    bool nf = false;
+    float mx = -INFINITY, sum = 0.f;
+    if (REG) {
+        const float4* l4 = reinterpret_cast<const float4*>(lr);
+        const int nv = V >> 2;
+        float4 v[SCORE_V4];
+#pragma unroll
+        for (int k = 0; k < SCORE_V4; ++k) {
+            const int o = lane + 64 * k;
+            v[k] = o < nv ? l4[o] : make_float4(-INFINITY, -INFINITY, -INFINITY, -INFINITY);
+            if (o < nv) nf = nf || nonfinite(v[k].x) || nonfinite(v[k].y) || nonfinite(v[k].z) || nonfinite(v[k].w);
+            mx = fmaxf(fmaxf(mx, fmaxf(v[k].x, v[k].y)), fmaxf(v[k].z, v[k].w));
+        }
+        mx = wave_max(mx);
+#pragma unroll
+        for (int k = 0; k < SCORE_V4; ++k)
+            if (lane + 64 * k < nv) sum += (expf(v[k].x - mx) + expf(v[k].y - mx)) + (expf(v[k].z - mx) + expf(v[k].w - mx));
+    } else {
+        for (int i = lane; i < V; i += 64) {
+            const float x = lr[i];
+            nf = nf || nonfinite(x);
+            mx = fmaxf(mx, x);
+        }
+        mx = wave_max(mx);
+        for (int i = lane; i < V; i += 64) sum += expf(lr[i] - mx);
+    }
+    sum = wave_sum(sum);
+    if (nf) status_raise(status, BG_ST_NONFINITE_LOGITS);
+    if (!target || lane != 0) return;
+    const int s = s0 + r;
+    const long j = fwd_idx[s];
+    const long t = target[b * N + j];
+    const float v = (t >= 0 && t < V) ? (mx + logf(sum)) - lr[t] : __uint_as_float(0x7fc00000u);
+    if (nll) nll[r] = v;
+    wnll[r] = weight ? weight[b * N + j] * v : v;
+}
+void launch_ar_score_rows(const float* logits, int ldl, const int64_t* target, const float* weight, const int64_t* fwd_idx, int b, int s0, int rows, int N, int V,
+                          float* nll, float* wnll, hipStream_t s) {
+    BG_REQUIRE(rows >= 1 && s0 >= 0 && s0 + rows <= N, "ar_score_rows: decode positions [%d, %d) outside [0, %d)", s0, s0 + rows, N);
+    BG_REQUIRE(!target || wnll, "ar_score_rows: a target needs the weighted-nll buffer");
+    const bool reg = V % 4 == 0 && ldl % 4 == 0 && V <= 64 * 4 * SCORE_V4 && (reinterpret_cast<uintptr_t>(logits) & 15) == 0;
+    if (reg) hipLaunchKernelGGL(ar_score_rows_kernel<true>, dim3(cdiv(rows, 4)), dim3(256), 0, s, logits, ldl, target, weight, fwd_idx, (long)b, s0, rows, N, V, nll, wnll, status_current());
+    else hipLaunchKernelGGL(ar_score_rows_kernel<false>, dim3(cdiv(rows, 4)), dim3(256), 0, s, logits, ldl, target, weight, fwd_idx, (long)b, s0, rows, N, V, nll, wnll, status_current());
+    LAUNCH_CHECK();
+}
+
+// loss = sum(x) / n in a FIXED order (thread t adds elements t, t + 256, ... in double, then a binary tree over the 256 partial sums): two calls give the same bits,
+// no float atomics.  One workgroup: n = B * n_steps <= a few 10^4.
+__global__ __launch_bounds__(256) void mean_fixed_order_kernel(const float* __restrict__ x, long n, float* __restrict__ out) {
+    __shared__ double sh[256];
+    double acc = 0.0;
+    for (long i = threadIdx.x; i < n; i += 256) acc += (double)x[i];
+    sh[threadIdx.x] = acc;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if ((int)threadIdx.x < o) sh[threadIdx.x] += sh[threadIdx.x + o];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) out[0] = (float)(sh[0] / (double)n);
+}
+void launch_mean_fixed_order(const float* x, long n, float* out, hipStream_t s) {
+    hipLaunchKernelGGL(mean_fixed_order_kernel, dim3(1), dim3(256), 0, s, x, n, out);
+    LAUNCH_CHECK();
+}
+
 // the uniforms the samplers draw in registers, written out (tests: explicit-noise run == seeded run)
 __global__ void philox_fill_kernel(float* __restrict__ out, long n, unsigned long long seed, unsigned iter, unsigned stream, int V) {
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {

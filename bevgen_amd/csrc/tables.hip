@@ -110,6 +110,44 @@ void launch_ar_step_embed(const int64_t* tok, const float* tok_emb, const float*
     LAUNCH_CHECK();
 }
 
+// Route A teacher-forced forward: the same row for EVERY decode position s < n_steps of every sequence in one launch, written in decode order behind the K
+// condition rows - x[b, K + s, :] = (x_tok_emb[ids[b, j]] + img_embed[b, j]) + x_pos_emb[j],  j = forward_shuffle_idx[s]; ids camera-major [B, N] as GPT.forward
+// receives them (id = vocab_size: the pad embedding, gpt:328-329).  Same operation order as ar_step_embed_kernel.
+__global__ __launch_bounds__(256) void ar_seq_embed_kernel(const int64_t* __restrict__ ids, const float* __restrict__ tok_emb, const float* __restrict__ img_embed,
+                                                           const float* __restrict__ pos_emb, const int64_t* __restrict__ fwd_idx, float* __restrict__ x, int rows_per_seq,
+                                                           int row0, int N, int D, int vocab_rows) {
+    const int s = blockIdx.x, b = blockIdx.y;
+    const long j = fwd_idx[s];
+    long id = ids[(long)b * N + j];
+    id = id < 0 ? 0 : (id >= vocab_rows ? vocab_rows - 1 : id);
+    const float4* te = reinterpret_cast<const float4*>(tok_emb + id * D);
+    const float4* ie = reinterpret_cast<const float4*>(img_embed ? img_embed + ((long)b * N + j) * D : tok_emb);
+    const float4* pe = reinterpret_cast<const float4*>(pos_emb + j * D);
+    float4* xo = reinterpret_cast<float4*>(x + ((long)b * rows_per_seq + row0 + s) * D);
+    for (int o = threadIdx.x; o < (D >> 2); o += 256) {
+        float4 v = te[o];
+        if (img_embed) {
+            const float4 g = ie[o];
+            v.x += g.x; v.y += g.y; v.z += g.z; v.w += g.w;
+        }
+        const float4 p = pe[o];
+        xo[o] = make_float4(v.x + p.x, v.y + p.y, v.z + p.z, v.w + p.w);
+    }
+}
+void launch_ar_seq_embed(const int64_t* ids, const float* tok_emb, const float* img_embed, const float* pos_emb, const int64_t* fwd_idx, float* x, int B, int n_steps,
+                         int rows_per_seq, int row0, int N, int D, int vocab_rows, hipStream_t s) {
+    BG_REQUIRE(D % 4 == 0, "ar_seq_embed: D must be a multiple of 4");
+    BG_REQUIRE(n_steps >= 1 && n_steps <= N && row0 + n_steps <= rows_per_seq, "ar_seq_embed: %d rows from %d do not fit %d rows per sequence", n_steps, row0, rows_per_seq);
+    hipLaunchKernelGGL(ar_seq_embed_kernel, dim3(n_steps, B), dim3(256), 0, s, ids, tok_emb, img_embed, pos_emb, fwd_idx, x, rows_per_seq, row0, N, D, vocab_rows);
+    LAUNCH_CHECK();
+}
+
+__global__ void set_i32_kernel(int* p, int v) { *p = v; }
+void launch_set_i32(int* p, int v, hipStream_t s) {
+    hipLaunchKernelGGL(set_i32_kernel, dim3(1), dim3(1), 0, s, p, v);
+    LAUNCH_CHECK();
+}
+
 // out[b, fwd_idx[step]] = tok[b]   (x[:, i, k] = ix, cond_transformer_multi_view.py:219)
 __global__ void store_tokens_kernel(const int64_t* __restrict__ tok, const int64_t* __restrict__ fwd_idx, const int* __restrict__ d_step, int64_t* __restrict__ out, int B, int N) {
     const int b = blockIdx.x * blockDim.x + threadIdx.x;

@@ -35,6 +35,7 @@ class Net2NetTransformer(_Base):
                                       "configuration and is not implemented; refusing rather than ignoring it")
         self.first_stage_key, self.cond_stage_key = first_stage_key, cond_stage_key
         self.skip_sampling, self.partial_decoding, self.top_k = skip_sampling, partial_decoding, top_k
+        self.bbox_ce_weight = bbox_ce_weight
         self.first_stage_model = first_stage.eval() if first_stage is not None else None
         self.cond_stage_model = cond_stage.eval() if cond_stage is not None else None
         self.transformer = transformer
@@ -175,9 +176,72 @@ class Net2NetTransformer(_Base):
         gt = self.expand_all_images(denormalize_tensor(x_img)) if x_img is not None else None
         return {"gen": gen, "rec": rec, "gt": gt}
 
+    # ---- teacher-forced loss (ar_lm:109-152, 277-384)
+    def _zc_indices(self, batch):
+        """(z ids [B, C, T], cond ids [B, K]) on the transformer's device: ar_lm:111-115 (precomputed batch['z_ids'] / batch['cond_ids'] short-circuit the encoders)."""
+        dev = next(self.transformer.parameters()).device
+        _, c = self.encode_to_c(None if "cond_ids" in batch else self.get_input(self.cond_stage_key, batch).to(dev), batch)
+        c = c.to(dev)
+        if "z_ids" in batch:
+            z = batch["z_ids"].to(dev)
+        else:
+            _, z = self.encode_to_z(self.get_input(self.first_stage_key, batch).to(dev), batch)
+        return z.reshape(c.shape[0], self.cfg.num_cams, self.cfg.num_cam_tokens), c
+
+    @staticmethod
+    def _geometry(batch, dev):
+        return {**batch, "intrinsics_inv": batch["intrinsics_inv"].to(dev), "extrinsics_inv": batch["extrinsics_inv"].to(dev)}
+
+    @torch.no_grad()
+    def shared_step(self, batch, batch_idx, inference=False):
+        """ar_lm:277-349: the unweighted mean cross-entropy of the ground-truth image tokens given the BEV condition (one pass, scored on the device)."""
+        if getattr(self, "bbox_ce_weight", 0.0) > 0:
+            raise NotImplementedError("bbox_ce_weight > 0 (ar_lm:281-347: cross-entropy weighted inside the projected bounding boxes of batch['bbx'], training only) is "
+                                      "not implemented; refusing rather than ignoring it")
+        z, c = self._zc_indices(batch)
+        _, loss = self.transformer.score(z, c, self._geometry(batch, c.device), sampling=False)
+        return loss
+
+    def validation_step(self, batch, batch_idx):
+        """ar_lm:364-376."""
+        loss = self.shared_step(batch, batch_idx)
+        if hasattr(self, "log"):
+            self.log("val/loss", loss, prog_bar=True, on_step=False, on_epoch=True)
+        ret = {"loss": loss}
+        if batch_idx == 0:
+            ret = {**self.log_images(batch), **ret}
+        return ret
+
+    @torch.no_grad()
+    def inference_step(self, batch):
+        """ar_lm:144-152: the logits of the all-pad image sequence."""
+        if not hasattr(self, "z_indices"):
+            dev = next(self.transformer.parameters()).device
+            _, c = self.encode_to_c(None if "cond_ids" in batch else self.get_input(self.cond_stage_key, batch).to(dev), batch)
+            self.c_indices = c.to(dev)
+            self.z_indices = torch.full((c.shape[0], self.cfg.num_cams, self.cfg.num_cam_tokens), self.cfg.vocab_size, dtype=torch.int64, device=dev)
+        return self.transformer.forward_onepass(self.z_indices, self.c_indices, self._geometry(batch, self.c_indices.device), sampling=False)
+
     def test_step(self, batch, batch_idx):
+        """ar_lm:378-384; `test/loss` only where the batch carries ground truth and a logger exists (the generate-only pipeline feeds neither)."""
+        if (self.first_stage_key in batch or "z_ids" in batch) and hasattr(self, "log"):
+            self.log("test/loss", self.shared_step(batch, batch_idx), prog_bar=True, on_step=False, on_epoch=True)
         return self.log_images(batch, generate_only=True, top_k=self.top_k)
 
-    def forward(self, batch):
-        return self.log_images(batch, generate_only=True, top_k=self.top_k)
+    def forward(self, *args):
+        """One argument: ``forward(batch)`` -> the image dict of the generate path.  Three: the reference's ``forward(x, c, batch)`` -> (logits [B, N, V], target [B, N])
+        (ar_lm:109-136); ``x`` / ``c`` may be None where the batch carries ``z_ids`` / ``cond_ids``."""
+        if len(args) == 1:
+            return self.log_images(args[0], generate_only=True, top_k=self.top_k)
+        if len(args) != 3:
+            raise TypeError(f"forward takes (batch) or (x, c, batch), got {len(args)} arguments")
+        x, c, batch = args
+        dev = next(self.transformer.parameters()).device
+        _, c_indices = self.encode_to_c(c, batch)
+        c_indices = c_indices.to(dev)
+        z = batch["z_ids"].to(dev) if "z_ids" in batch else self.encode_to_z(x.to(dev), batch)[1]
+        z = z.reshape(c_indices.shape[0], self.cfg.num_cams, self.cfg.num_cam_tokens)
+        target = z.reshape(z.shape[0], -1).clone()
+        logits = self.transformer.forward_onepass(z, c_indices, self._geometry(batch, dev), sampling=False)
+        return logits.contiguous(), target.contiguous()
 

@@ -93,3 +93,33 @@ class GPT(RuntimeOptionsMixin, nn.Module):
         ctx.synchronize()   # gpt:383,388 (finite inputs / logits asserted by the reference): the device status word of the N step calls, read once
         logits = torch.stack(rows, dim=1)  # decode order
         return logits[:, cfg.backward_shuffle_idx.to(logits.device)]
+
+    def _teacher_ids(self, cam_indices, sampling):
+        """The ids GPT.forward embeds, camera-major [B, N]: with ``sampling=False`` the camera-major last token becomes the pad id (gpt:328-329)."""
+        cfg = self.cfg
+        flat = cam_indices.reshape(cam_indices.shape[0], cfg.num_img_tokens).clone()
+        if not sampling:
+            flat[:, -1] = cfg.vocab_size
+        return flat
+
+    @torch.no_grad()
+    def forward_onepass(self, cam_indices, bev_indices, batch, sampling, **kwargs):
+        """The logits of ``forward`` [B, N, V] camera-major, computed as ONE batched pass over the K + N rows (bevgen_ar_forward) instead of N decode steps."""
+        cfg = self.cfg
+        ctx = self.context()
+        logits, _, _ = ctx.ar_forward(bev_indices, batch["intrinsics_inv"], batch["extrinsics_inv"], self._teacher_ids(cam_indices, sampling).to(ctx.device))
+        return logits[:, cfg.backward_shuffle_idx.to(logits.device)]
+
+    @torch.no_grad()
+    def score(self, cam_indices, bev_indices, batch, sampling, target=None, weight=None):
+        """Teacher-forced token cross-entropy of one pass (ar_lm:277-349): -> (nll [B, N] camera-major, loss).  ``target`` (default: ``cam_indices`` themselves, before
+        the pad substitution) and ``weight`` (default 1) are camera-major [B, N]; loss = sum(weight * nll) / (B N).  Both come from the device: the logits are
+        never materialised."""
+        cfg = self.cfg
+        ctx = self.context()
+        B = cam_indices.shape[0]
+        if target is None:
+            target = cam_indices
+        _, nll, loss = ctx.ar_forward(bev_indices, batch["intrinsics_inv"], batch["extrinsics_inv"], self._teacher_ids(cam_indices, sampling).to(ctx.device),
+                                      target=target.reshape(B, cfg.num_img_tokens), weight=weight, want_logits=False)
+        return nll[:, cfg.backward_shuffle_idx.to(nll.device)], loss

@@ -300,6 +300,42 @@ class Context:
         token = _req(token, torch.int64, self.device, "token")
         self._check(self.lib.bevgen_ar_decode_step(self._h, _ptr(token), self._s()))
 
+    def ar_forward(self, cond_ids, I_inv, E_inv, ids, *, n_steps=None, target=None, weight=None, want_logits=True, check=True):
+        """One-pass teacher-forced forward over the condition rows and the first ``n_steps`` image rows (``bevgen_ar_forward``).  ``ids`` / ``target`` / ``weight``
+        are camera-major [B, N] as ``GPT.forward`` receives them; the results are in DECODE order: ``logits`` [B, n_steps, V] (None with ``want_logits=False``: they are
+        then never materialised), and with a ``target`` ``nll`` [B, n_steps] and ``loss`` (0-d, sum(w * nll) / (B * n_steps)), else None.  Afterwards the context is as
+        after ``ar_prefill`` + ``n_steps`` ``ar_decode_step`` calls.  Returns (logits, nll, loss)."""
+        cfg = self.cfg
+        d = self.device
+        cond_ids = _req(cond_ids, torch.int64, d, "cond_ids")
+        I_inv = _req(I_inv, torch.float32, d, "I_inv")
+        E_inv = _req(E_inv, torch.float32, d, "E_inv")
+        B, N = cond_ids.shape[0], cfg.num_img_tokens
+        n = N if n_steps is None else int(n_steps)
+        if not 1 <= n <= N:
+            raise ValueError(f"n_steps={n} out of range [1, {N}]")
+        ids = _req(ids, torch.int64, d, "ids").reshape(B, -1)
+        if ids.shape[1] != N:
+            raise ValueError(f"ids must hold {N} camera-major image tokens per sequence, got {ids.shape[1]}")
+        if target is None and weight is not None:
+            raise ValueError("weight needs a target")
+        if target is not None:
+            target = _req(target, torch.int64, d, "target").reshape(B, -1)
+            if target.shape[1] != N:
+                raise ValueError(f"target must hold {N} camera-major image tokens per sequence, got {target.shape[1]}")
+        if weight is not None:
+            weight = _req(weight, torch.float32, d, "weight").reshape(B, -1)
+            if weight.shape[1] != N:
+                raise ValueError(f"weight must hold {N} values per sequence, got {weight.shape[1]}")
+        logits = torch.empty((B, n, cfg.vocab_size), dtype=torch.float32, device=d) if want_logits else None
+        nll = torch.empty((B, n), dtype=torch.float32, device=d) if target is not None else None
+        loss = torch.empty((), dtype=torch.float32, device=d) if target is not None else None
+        self._ar_B = B
+        self._check(self.lib.bevgen_ar_forward(self._h, _ptr(cond_ids), _ptr(I_inv), _ptr(E_inv), B, _ptr(ids), n, _ptr(logits), _ptr(target), _ptr(weight), _ptr(nll),
+                                               _ptr(loss), self._s()))
+        self._done(check)
+        return logits, nll, loss
+
     def ar_sample(self, cond_ids, I_inv, E_inv, *, steps=None, top_k=None, temperature=1.0, greedy=True, noise_u=None, samples_per_layout=1, return_logits=False,
                   forced_ids=None, check=True):
         """Route A sampling with the KV cache.  forced_ids [steps, B] int64 in decode order (>= 0: emit this token, < 0: draw) = partial decoding."""

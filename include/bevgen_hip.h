@@ -212,6 +212,24 @@ int bevgen_ar_logits(bevgen_ctx* ctx, float* d_logits, void* stream);
  * embedding of the token at its (camera, latent cell) + one pass over all layers against the KV cache. */
 int bevgen_ar_decode_step(bevgen_ctx* ctx, const int64_t* d_token, void* stream);
 
+/* Teacher-forced GPT.forward (transformer/mingpt_sparse.py:319-391) over the K condition rows and the first n_steps image rows in decode order, as ONE batched pass,
+ * plus shared_step's token cross-entropy (stage2/cond_transformer_multi_view.py:277-349), asynchronous on `stream`:
+ *   d_ids    [B, C*T] int64 camera-major, as GPT.forward receives them: input row K + s is the embedding of d_ids[b, forward_shuffle_idx[s]]; an id equal to
+ *            vocab_size is the pad embedding (gpt:328-329 substitutes it for the camera-major last token when sampling = False - the caller does that)
+ *   n_steps  1 .. C*T; pad rows K + C*T .. seq_len are never computed (the mask is causal in decode order: no computed row sees them)
+ *   d_logits [B, n_steps, V] in DECODE order, or NULL: row s comes from hidden row K - 1 + s and predicts decode position s.  With NULL the logits are produced and
+ *            consumed in row chunks and never exist as one buffer
+ *   d_target [B, C*T] int64 camera-major or NULL (then d_weight, d_nll and d_loss must be NULL); a target outside [0, V) gives a NaN nll
+ *   d_weight [B, C*T] float camera-major or NULL (= 1)
+ *   d_nll    [B, n_steps] float in decode order or NULL: logsumexp(logits[b, s, :]) - logits[b, s, d_target[b, forward_shuffle_idx[s]]] (unweighted)
+ *   d_loss   1 float or NULL: sum(w * nll) / (B * n_steps), reduced in a fixed order in double precision - two identical calls give the same bits
+ * A NaN / inf logit raises BEVGEN_STATUS_NONFINITE_LOGITS as the samplers do.  Precision / weight modes are those of bevgen_ar_prefill.  Afterwards the context is
+ * exactly as after bevgen_ar_prefill followed by n_steps calls of bevgen_ar_decode_step with the same tokens (K/V cache rows [0, K + n_steps) in the context's cache
+ * dtype, newest hidden row, step counter): bevgen_ar_logits / bevgen_ar_decode_step may follow.  There is no samples_per_layout form of this call: every sequence
+ * is scored on its own. */
+int bevgen_ar_forward(bevgen_ctx* ctx, const int64_t* d_cond_ids, const float* d_I_inv, const float* d_E_inv, int B, const int64_t* d_ids, int n_steps,
+                      float* d_logits, const int64_t* d_target, const float* d_weight, float* d_nll, float* d_loss, void* stream);
+
 /* Net2NetTransformer.sample (stage2/cond_transformer_multi_view.py:154-227) with prefill + KV cache:
  *   top_k <= 0 disables the filter; greedy != 0 -> arg-max (sample=False), else inverse-CDF draw with d_noise_u [steps, B];
  *   samples_per_layout: consecutive groups of sequences share cond ids/cameras (B = layouts * samples_per_layout rows are
