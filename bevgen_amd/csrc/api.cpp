@@ -379,6 +379,59 @@ int bevgen_op_mlp_fused(bevgen_ctx* ctx, const float* x, const float* ln_w, cons
     });
 }
 
+int bevgen_op_remask(bevgen_ctx* ctx, int64_t* ids, const float* scores, const int64_t* init_ids, int rows, int T, int n_mask, int64_t mask_id, void* stream) {
+    return guarded(ctx, [&] {
+        BG_REQUIRE(ids && scores && rows >= 1 && T >= 1, "op_remask: bad arguments");
+        launch_remask(ids, scores, init_ids, rows, T, n_mask, mask_id, (hipStream_t)stream);
+    });
+}
+
+int bevgen_op_maskgit_pick(bevgen_ctx* ctx, int64_t* ids, const float* logits, int ldl, const float* gumbel_u, int rows, int V, int k, float temperature, int64_t mask_id,
+                           unsigned long long seed, unsigned iter, float* conf_scores, int conf_mode, void* stream) {
+    return guarded(ctx, [&] {
+        BG_REQUIRE(ids && logits && rows >= 1 && V >= 1 && ldl >= V, "op_maskgit_pick: bad arguments");
+        launch_maskgit_pick(ids, logits, ldl, gumbel_u, rows, V, k, temperature, mask_id, (hipStream_t)stream, seed, iter, conf_scores, conf_mode);
+    });
+}
+
+int bevgen_op_critic_scores(bevgen_ctx* ctx, const float* embed, int lde, const float* w, const float* b, const float* u, float noise_scale, float frac,
+                            unsigned long long seed, unsigned iter, float* scores, int rows, int D, void* stream) {
+    return guarded(ctx, [&] {
+        BG_REQUIRE(embed && w && b && scores && rows >= 1 && D >= 1 && lde >= D, "op_critic_scores: bad arguments");
+        launch_critic_scores(embed, lde, w, b, u, noise_scale, frac, scores, rows, D, (hipStream_t)stream, seed, iter);
+    });
+}
+
+int bevgen_op_ar_pick(bevgen_ctx* ctx, const float* logits, int ldl, const float* u, const int* d_step, const int64_t* forced, int64_t* out, int rows, int V, int top_k,
+                      float temperature, int64_t* out_all, const int64_t* fwd_idx, int N, const float* tok_emb, const float* img_embed, const float* pos_emb, float* x, int C, int T,
+                      int D, int vocab_rows, void* stream) {
+    return guarded(ctx, [&] {
+        BG_REQUIRE(logits && out && rows >= 1 && V >= 1 && ldl >= V, "op_ar_pick: bad arguments");
+        BG_REQUIRE(!out_all || (fwd_idx && N >= 1), "op_ar_pick: out_all needs fwd_idx and N");
+        BG_REQUIRE(!x || (out_all && tok_emb && pos_emb && vocab_rows >= 1 && D >= 1), "op_ar_pick: x needs out_all, tok_emb, pos_emb and vocab_rows");
+        ArPickTail tail;
+        tail.out_all = out_all; tail.fwd_idx = fwd_idx; tail.N = N;
+        tail.tok_emb = tok_emb; tail.img_embed = img_embed; tail.pos_emb = pos_emb; tail.x = x;
+        tail.C = C; tail.T = T; tail.D = D; tail.vocab_rows = vocab_rows;
+        launch_ar_pick(logits, ldl, u, d_step, forced, out, rows, V, top_k, temperature, (hipStream_t)stream, out_all ? &tail : nullptr);
+    });
+}
+
+int bevgen_op_ar_score_rows(bevgen_ctx* ctx, const float* logits, int ldl, const int64_t* target, const float* weight, const int64_t* fwd_idx, int b, int s0, int rows, int N,
+                            int V, float* nll, float* wnll, void* stream) {
+    return guarded(ctx, [&] {
+        BG_REQUIRE(logits && V >= 1 && ldl >= V && b >= 0 && (!target || fwd_idx), "op_ar_score_rows: bad arguments");
+        launch_ar_score_rows(logits, ldl, target, weight, fwd_idx, b, s0, rows, N, V, nll, wnll, (hipStream_t)stream);
+    });
+}
+
+int bevgen_op_mean_fixed_order(bevgen_ctx* ctx, const float* x, long n, float* out, void* stream) {
+    return guarded(ctx, [&] {
+        BG_REQUIRE(x && out && n >= 1, "op_mean_fixed_order: bad arguments");
+        launch_mean_fixed_order(x, n, out, (hipStream_t)stream);
+    });
+}
+
 int bevgen_op_layernorm(bevgen_ctx* ctx, const float* x, const float* gamma, const float* beta, float* y, int rows, int D, float eps, void* stream) {
     return guarded(ctx, [&] { launch_layernorm(x, D, gamma, beta, y, D, rows, D, eps, (hipStream_t)stream); });
 }

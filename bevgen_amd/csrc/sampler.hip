@@ -64,6 +64,7 @@ __global__ __launch_bounds__(256) void remask_kernel(int64_t* __restrict__ ids, 
 }
 
 void launch_remask(int64_t* ids, const float* scores, const int64_t* init_ids, int rows, int T, int n_mask, int64_t mask_id, hipStream_t s) {
+    BG_REQUIRE(T >= 1 && (size_t)T * sizeof(float) <= 64 * 1024, "remask: %d scores per row do not fit the 64 KiB of dynamic LDS", T);
     hipLaunchKernelGGL(remask_kernel, dim3(rows), dim3(256), T * sizeof(float), s, ids, scores, init_ids, T, n_mask, mask_id);
     LAUNCH_CHECK();
 }
@@ -143,6 +144,7 @@ __global__ __launch_bounds__(256) void maskgit_pick_kernel(int64_t* __restrict__
 void launch_maskgit_pick(int64_t* ids, const float* logits, int ldl, const float* gumbel_u, int rows, int V, int k, float temperature, int64_t mask_id, hipStream_t s,
                          unsigned long long seed, unsigned iter, float* conf_scores, int conf_mode) {
     BG_REQUIRE(V <= 64 * VPL_MAX, "maskgit_pick: vocabulary %d > %d", V, 64 * VPL_MAX);
+    BG_REQUIRE(k >= 1, "maskgit_pick: top-k count %d < 1 (topk_filter_thres = 1 keeps no logit)", k);
     BG_REQUIRE(conf_mode == 0 || conf_scores, "maskgit_pick: confidence scores requested without an output buffer");
     const float temp_div = fmaxf(temperature, 1e-10f);
     hipLaunchKernelGGL(maskgit_pick_kernel, dim3(cdiv(rows, 4)), dim3(256), 0, s, ids, logits, ldl, gumbel_u, (long)rows, V, k, temp_div, mask_id, seed, iter, conf_scores,
@@ -177,6 +179,8 @@ __global__ __launch_bounds__(256) void critic_scores_kernel(const float* __restr
 void launch_critic_scores(const float* embed, int lde, const float* w, const float* b, const float* u, float noise_scale, float frac, float* scores, int rows, int D, hipStream_t s,
                           unsigned long long seed, unsigned iter) {
     BG_REQUIRE(D % 4 == 0, "critic_scores: D must be a multiple of 4");
+    BG_REQUIRE(lde % 4 == 0 && ((reinterpret_cast<uintptr_t>(embed) | reinterpret_cast<uintptr_t>(w)) & 15) == 0,
+               "critic_scores: 16-byte loads need lde %% 4 == 0 (got %d) and 16-byte aligned embed / w", lde);
     hipLaunchKernelGGL(critic_scores_kernel, dim3(cdiv(rows, 4)), dim3(256), 0, s, embed, lde, w, b, u, noise_scale, frac, scores, (long)rows, D, seed, iter, status_current());
     LAUNCH_CHECK();
 }

@@ -469,6 +469,60 @@ class Context:
         self._check(self.lib.bevgen_op_mlp_fused(self._h, _ptr(x), _ptr(ln_w), _ptr(ln_b), float(eps), _ptr(w1), _ptr(b1), _ptr(w2), _ptr(b2), int(w_f16), _ptr(out), M, D, self._s()))
         return out
 
+    # token samplers / scorers (sampler.hip): the tensors are handed over as they are - a row stride or an offset view is part of what the caller tests
+    @staticmethod
+    def _ld(t, ld):
+        assert t.dim() == 2 and (t.shape[1] == 1 or t.stride(1) == 1), "rows must be unit-stride"
+        return int(ld) if ld is not None else (t.stride(0) if t.shape[0] > 1 else t.shape[1])
+
+    def op_remask(self, ids, scores, n_mask, mask_id, init_ids=None):
+        """In place on ids [rows, T] int64: the n_mask highest scores of each row (ties: lower index first) become mask_id, then init_ids != mask_id are re-imposed."""
+        rows, T = ids.shape
+        self._check(self.lib.bevgen_op_remask(self._h, _ptr(ids), _ptr(scores), _ptr(init_ids), rows, T, int(n_mask), int(mask_id), self._s()))
+        return ids
+
+    def op_maskgit_pick(self, ids, logits, V, *, mask_id, k=None, topk_filter_thres=None, temperature=1.0, gumbel_u=None, seed=0, it=0, conf_scores=None, conf_mode=0, ldl=None):
+        """In place on ids [rows] int64 (only entries == mask_id change); logits [rows, ldl >= V].  k, or topk_filter_thres as MaskGit.generate takes it (k = ceil((1 - thres) V);
+        a threshold that keeps no logit is refused by the library like k = 0)."""
+        if k is None:
+            k = V if topk_filter_thres is None else topk_count(topk_filter_thres, V)
+        self._check(self.lib.bevgen_op_maskgit_pick(self._h, _ptr(ids), _ptr(logits), self._ld(logits, ldl), _ptr(gumbel_u), ids.numel(), int(V), int(k), float(temperature),
+                                                    int(mask_id), C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), int(it), _ptr(conf_scores), int(conf_mode), self._s()))
+        return ids
+
+    def op_critic_scores(self, embed, w, b, D=None, *, u=None, noise_scale=0.0, frac=0.0, seed=0, it=0, lde=None):
+        """scores [rows] = embed[:, :D] . w + b + ((u - 0.5) * noise_scale) * frac; u explicit, else Philox stream 1 of (seed, it) when seed != 0, else 0.5."""
+        rows = embed.shape[0]
+        D = embed.shape[1] if D is None else int(D)
+        scores = torch.empty((rows,), dtype=torch.float32, device=self.device)
+        self._check(self.lib.bevgen_op_critic_scores(self._h, _ptr(embed), self._ld(embed, lde), _ptr(w), _ptr(b), _ptr(u), float(noise_scale), float(frac),
+                                                     C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), int(it), _ptr(scores), rows, D, self._s()))
+        return scores
+
+    def op_ar_pick(self, logits, V, *, top_k=0, temperature=1.0, u=None, step=None, forced=None, ldl=None, out_all=None, fwd_idx=None, tok_emb=None, img_embed=None,
+                   pos_emb=None, x=None, C_=0, T=0):
+        """tokens [rows] of logits [rows, ldl >= V]; u / forced [steps, rows] with `step` a device int32 counter (None: their first row).  Tail: out_all [rows, N] and
+        x [rows, D] are written in place (kernels.h ArPickTail)."""
+        rows = logits.shape[0]
+        out = torch.empty((rows,), dtype=torch.int64, device=self.device)
+        self._check(self.lib.bevgen_op_ar_pick(self._h, _ptr(logits), self._ld(logits, ldl), _ptr(u), _ptr(step), _ptr(forced), _ptr(out), rows, int(V), int(top_k),
+                                               float(temperature), _ptr(out_all), _ptr(fwd_idx), 0 if out_all is None else out_all.shape[1], _ptr(tok_emb), _ptr(img_embed),
+                                               _ptr(pos_emb), _ptr(x), int(C_), int(T), 0 if x is None else x.shape[1], 0 if tok_emb is None else tok_emb.shape[0], self._s()))
+        return out
+
+    def op_ar_score_rows(self, logits, V, fwd_idx, *, target=None, weight=None, b=0, s0=0, rows=None, N=None, nll=None, wnll=None, ldl=None):
+        """nll / wnll [rows] (written in place where given) of decode positions [s0, s0 + rows) of sequence b; target / weight [B, N] camera-major."""
+        rows = logits.shape[0] if rows is None else int(rows)
+        N = fwd_idx.numel() if N is None else int(N)
+        self._check(self.lib.bevgen_op_ar_score_rows(self._h, _ptr(logits), self._ld(logits, ldl), _ptr(target), _ptr(weight), _ptr(fwd_idx), int(b), int(s0), rows, N, int(V),
+                                                     _ptr(nll), _ptr(wnll), self._s()))
+        return nll, wnll
+
+    def op_mean_fixed_order(self, x):
+        out = torch.empty((), dtype=torch.float32, device=self.device)
+        self._check(self.lib.bevgen_op_mean_fixed_order(self._h, _ptr(x), x.numel(), _ptr(out), self._s()))
+        return out
+
     def op_layernorm(self, x, gamma, beta=None, eps=1e-5):
         y = torch.empty_like(x)
         self._check(self.lib.bevgen_op_layernorm(self._h, _ptr(x), _ptr(gamma), _ptr(beta), _ptr(y), x.shape[0], x.shape[1], float(eps), self._s()))

@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define BEVGEN_ABI_VERSION 6   /* 6: device status word (bevgen_synchronize, bevgen_status, BEVGEN_ERR_NUMERIC, BEVGEN_STATUS_*).  5: bevgen_op_mlp_fused; a context without max_batch <= 4 packs the split decode layer lazily (see Conventions).  4: 4: BEVGEN_PROFILE_KINDS 5 -> 6 (bevgen_profile_end writes 18 doubles), bevgen_cfg.decode_chains, decode_path values 2 / 3 */
+#define BEVGEN_ABI_VERSION 7   /* 7: operator entries of the token samplers (bevgen_op_remask, _maskgit_pick, _critic_scores, _ar_pick, _ar_score_rows, _mean_fixed_order).  6: device status word (bevgen_synchronize, bevgen_status, BEVGEN_ERR_NUMERIC, BEVGEN_STATUS_*).  5: bevgen_op_mlp_fused; a context without max_batch <= 4 packs the split decode layer lazily (see Conventions).  4: 4: BEVGEN_PROFILE_KINDS 5 -> 6 (bevgen_profile_end writes 18 doubles), bevgen_cfg.decode_chains, decode_path values 2 / 3 */
 
 enum { BEVGEN_ROUTE_MASKGIT = 0, BEVGEN_ROUTE_AR = 1 };
 /* FP32  : every product and accumulation in exact fp32 on the matrix cores (v_mfma_f32_32x32x2_f32) - bit-exact greedy tokens vs the CPU reference.
@@ -286,6 +286,31 @@ int bevgen_op_mlp_fused(bevgen_ctx* ctx, const float* d_x, const float* d_ln_w, 
 /* d_out[i] = the uniform the MaskGit samplers draw for element i of noise stream `stream_id` (0 gumbel, 1 critic) at iteration `iter` under `seed`. */
 int bevgen_op_philox_uniform(bevgen_ctx* ctx, unsigned long long seed, unsigned iter, unsigned stream_id, int V /* vocabulary size: row layout of stream 0 */, long n,
                              float* d_out, void* stream);
+/* Token samplers and scorers (sampler.hip), one entry per kernel; every pointer marked "or NULL" stays optional.  Non-finite logits / scores raise BEVGEN_STATUS_NONFINITE_LOGITS.
+ * remask: the n_mask highest scores of each row of d_ids [rows, T] (ties: lower index first) become mask_id, then d_init_ids entries != mask_id are re-imposed; T <= 16384. */
+int bevgen_op_remask(bevgen_ctx* ctx, int64_t* d_ids, const float* d_scores, const int64_t* d_init_ids /* or NULL */, int rows, int T, int n_mask, int64_t mask_id, void* stream);
+/* maskgit_pick: d_ids [rows] == mask_id are replaced by argmax(topk_k(logits) / max(temperature, 1e-10) + gumbel(u)); u = d_gumbel_u [rows, V], else Philox(seed, iter) when
+ * seed != 0, else none (plain arg-max, lowest index on ties).  V <= 1024, 1 <= k.  conf_mode 1 / 2: d_conf_scores [rows] = 1 - softmax(logits)[pred] at masked positions
+ * (-1e5 elsewhere) / at every position. */
+int bevgen_op_maskgit_pick(bevgen_ctx* ctx, int64_t* d_ids, const float* d_logits, int ldl, const float* d_gumbel_u /* or NULL */, int rows, int V, int k, float temperature,
+                           int64_t mask_id, unsigned long long seed, unsigned iter, float* d_conf_scores /* or NULL */, int conf_mode, void* stream);
+/* critic_scores: d_scores[r] = d_embed[r, :D] . d_w + d_b[0] + ((u[r] - 0.5) * noise_scale) * frac; u = d_u, else Philox stream 1 of (seed, iter) when seed != 0, else 0.5.
+ * D % 4 == 0, lde % 4 == 0, d_embed and d_w 16-byte aligned. */
+int bevgen_op_critic_scores(bevgen_ctx* ctx, const float* d_embed, int lde, const float* d_w, const float* d_b, const float* d_u /* or NULL */, float noise_scale, float frac,
+                            unsigned long long seed, unsigned iter, float* d_scores, int rows, int D, void* stream);
+/* ar_pick: d_out[r] = token of row r of d_logits [rows, ldl]: logits / temperature, top_k (0 = off, ties kept), arg-max (d_u NULL) or inverse-CDF draw with
+ * d_u [steps, rows]; d_step (device int, or NULL = step 0) selects the row of d_u / d_forced [steps, rows] (entries >= 0 are emitted verbatim).  Optional tail (d_out_all
+ * non-NULL; needs d_step): d_out_all[r, d_fwd_idx[step]] = token, and with d_x non-NULL d_x[r, :D] = (d_tok_emb[min(token, vocab_rows - 1)] + d_img_embed[r, fwd_idx[step]])
+ * + d_pos_emb[fwd_idx[step]] with d_img_embed [rows, C * T, D] or NULL; D % 4 == 0. */
+int bevgen_op_ar_pick(bevgen_ctx* ctx, const float* d_logits, int ldl, const float* d_u /* or NULL */, const int* d_step /* or NULL */, const int64_t* d_forced /* or NULL */,
+                      int64_t* d_out, int rows, int V, int top_k, float temperature, int64_t* d_out_all /* or NULL */, const int64_t* d_fwd_idx, int N, const float* d_tok_emb,
+                      const float* d_img_embed /* or NULL */, const float* d_pos_emb, float* d_x /* or NULL */, int C, int T, int D, int vocab_rows, void* stream);
+/* ar_score_rows: rows [s0, s0 + rows) in decode order of sequence b: d_nll[r] (or NULL) = logsumexp(d_logits[r, :V]) - d_logits[r, t], t = d_target[b, d_fwd_idx[s0 + r]]
+ * (outside [0, V): NaN), d_wnll[r] = d_weight[b, d_fwd_idx[s0 + r]] (NULL = 1) * nll; d_target NULL: only the finiteness check of the rows. */
+int bevgen_op_ar_score_rows(bevgen_ctx* ctx, const float* d_logits, int ldl, const int64_t* d_target /* [B, N] or NULL */, const float* d_weight /* or NULL */,
+                            const int64_t* d_fwd_idx, int b, int s0, int rows, int N, int V, float* d_nll /* or NULL */, float* d_wnll, void* stream);
+/* d_out[0] = sum(d_x[0..n)) / n, accumulated in double in a fixed order: two calls give the same bits. */
+int bevgen_op_mean_fixed_order(bevgen_ctx* ctx, const float* d_x, long n, float* d_out, void* stream);
 int bevgen_op_layernorm(bevgen_ctx* ctx, const float* d_x, const float* d_gamma, const float* d_beta, float* d_y, int rows, int D, float eps, void* stream);
 int bevgen_op_geglu_layernorm(bevgen_ctx* ctx, const float* d_h, const float* d_gamma, float* d_y, int rows, int F, int ldy, void* stream);
 int bevgen_op_attention(bevgen_ctx* ctx, const float* d_q, const float* d_k, const float* d_v, const float* d_bias, int ldbias,
