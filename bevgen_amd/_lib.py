@@ -13,7 +13,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("BEVGEN_LIB_PATH") or os.path.join(_HERE, "csrc", "libbevgen_hip.so")   # override: A/B runs of two builds on one GPU box
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "bevgen_hip.h")
 
-ABI_VERSION = 7
+ABI_VERSION = 8
 ROUTE_MASKGIT, ROUTE_AR = 0, 1
 PRECISION_FP32, PRECISION_BF16, PRECISION_F16X3 = 0, 1, 2
 KV_F32, KV_F16 = 0, 1
@@ -41,7 +41,7 @@ class bevgen_cfg(C.Structure):
         ("ff_inner", C.c_int32), ("max_batch", C.c_int32),
         ("vq_ch", C.c_int32), ("vq_num_res_blocks", C.c_int32), ("vq_z_channels", C.c_int32), ("vq_embed_dim", C.c_int32),
         ("vq_n_embed", C.c_int32), ("vq_resolution", C.c_int32), ("vq_out_ch", C.c_int32), ("vq_num_levels", C.c_int32),
-        ("vq_ch_mult", C.c_int32 * 8), ("vq_attn_resolution", C.c_int32), ("vq_in_channels", C.c_int32), ("kv_cache_dtype", C.c_int32), ("decode_path", C.c_int32), ("decode_weight_dtype", C.c_int32), ("weight_dtype", C.c_int32), ("decode_chains", C.c_int32), ("reserved", C.c_int32 * 10),
+        ("vq_ch_mult", C.c_int32 * 8), ("vq_attn_resolution", C.c_int32), ("vq_in_channels", C.c_int32), ("kv_cache_dtype", C.c_int32), ("decode_path", C.c_int32), ("decode_weight_dtype", C.c_int32), ("weight_dtype", C.c_int32), ("decode_chains", C.c_int32), ("vq_range", C.c_int32), ("reserved", C.c_int32 * 9),
     ]
 
 
@@ -75,6 +75,7 @@ SIGNATURES = {
     "bevgen_vq_decode": (_i, [_p, _p, _i, _i, _i, _i, _p, _p]),
     "bevgen_vq_decode_latents": (_i, [_p, _p, _i, _i, _i, _i, _p, _p]),
     "bevgen_vq_encode": (_i, [_p, _p, _i, _i, _i, _p, _p]),
+    "bevgen_vq_range_exponents": (_i, [_p, C.POINTER(C.c_int32), _i, C.POINTER(_i)]),
     "bevgen_op_gemm": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _p]),
     "bevgen_op_ln_gemm": (_i, [_p, _p, _p, _p, _f, _p, _p, _p, _i, _i, _i, _i, _i, C.POINTER(_i), _p]),
     "bevgen_op_mlp_fused": (_i, [_p, _p, _p, _p, _f, _p, _p, _p, _p, _i, _p, _i, _i, _p]),
@@ -92,6 +93,7 @@ SIGNATURES = {
     "bevgen_op_ar_attn_fused": (_i, [_p, _p, _p, _i, _p, _p, _p, _p, _p, _i, _p, _p, _i, _p, _i, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _p, _p]),
     "bevgen_op_conv3x3": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p]),
     "bevgen_op_groupnorm": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _p]),
+    "bevgen_op_range_split": (_i, [_p, _p, _i, _i, _i, _p, _p, _p]),
     "bevgen_decode_attention_splits": (_i, [_i, _i, _i]),
     "bevgen_profile_begin": (_i, [_p]),
     "bevgen_profile_end": (_i, [_p, C.POINTER(C.c_double)]),

@@ -53,6 +53,7 @@ int bevgen_create(const bevgen_cfg* cfg, int device, bevgen_ctx** out) {
         BG_REQUIRE(cfg->precision == BEVGEN_PRECISION_FP32 || cfg->precision == BEVGEN_PRECISION_F16X3, "bevgen_create: precision must be BEVGEN_PRECISION_FP32 or BEVGEN_PRECISION_F16X3");
         BG_REQUIRE(cfg->weight_dtype == BEVGEN_W_F32 || (cfg->weight_dtype == BEVGEN_W_F16 && cfg->precision == BEVGEN_PRECISION_F16X3),
                    "bevgen_create: weight_dtype must be BEVGEN_W_F32, or BEVGEN_W_F16 together with BEVGEN_PRECISION_F16X3");
+        BG_REQUIRE(cfg->vq_range == 0 || cfg->vq_range == 1, "bevgen_create: vq_range must be 0 (refuse) or 1 (rescale), got %d", cfg->vq_range);
         int ndev = 0;
         HIP_CHECK(hipGetDeviceCount(&ndev));
         BG_REQUIRE(device >= 0 && device < ndev, "bevgen_create: device %d not present (%d visible)", device, ndev);
@@ -255,6 +256,13 @@ int bevgen_vq_decode_latents(bevgen_ctx* ctx, const float* zq, int n, int lat_h,
         BG_REQUIRE(zq && out && n >= 1 && out_mode >= 0 && out_mode <= 2, "vq_decode_latents: bad arguments");
         vq_default_grid(ctx, lat_h, lat_w);
         vq_decode(*ctx, nullptr, zq, n, lat_h, lat_w, out_mode, out, (hipStream_t)stream);
+    });
+}
+
+int bevgen_vq_range_exponents(bevgen_ctx* ctx, int32_t* h_out, int cap, int* count) {
+    return guarded(ctx, [&] {
+        BG_REQUIRE(count && cap >= 0 && (h_out || cap == 0), "vq_range_exponents: bad arguments");
+        *count = vq_range_exponents(*ctx, h_out, cap);
     });
 }
 
@@ -615,6 +623,19 @@ int bevgen_op_groupnorm(bevgen_ctx* ctx, const float* x, const float* gamma, con
         void* ws = ctx->arena.alloc(groupnorm_ws_bytes(n, hw));
         launch_groupnorm_stats(x, stats, ws, n, hw, C, 1e-6f, (hipStream_t)stream);
         launch_groupnorm_apply(x, stats, gamma, beta, y, n, hw, C, swish, (hipStream_t)stream);
+    });
+}
+
+int bevgen_op_range_split(bevgen_ctx* ctx, const float* x, int n, int hw, int C, void* planes, int32_t* d_exp, void* stream) {
+    return guarded(ctx, [&] {
+        BG_REQUIRE(x && planes && d_exp && n >= 1 && hw >= 1 && C >= 32 && C % 32 == 0, "op_range_split: bad arguments (C must be a multiple of 32)");
+        hipStream_t s = (hipStream_t)stream;
+        ctx->arena.reserve(4096);
+        ctx->arena.reset();
+        unsigned* amax = ctx->arena.get<unsigned>(1);
+        HIP_CHECK(hipMemsetAsync(amax, 0, sizeof(unsigned), s));
+        launch_range_exponent(x, (long)n * hw * C, amax, d_exp, s);
+        launch_range_split(x, planes, (long)n * hw, C, d_exp, s);
     });
 }
 

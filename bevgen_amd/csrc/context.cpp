@@ -72,6 +72,7 @@ Ctx::~Ctx() {
     for (void* p : owned) (void)hipFree(p);
     arena.release();
     persist.release();
+    vq_range_slots.release();
     if (status_host) (void)hipHostFree(status_host);
 }
 
@@ -87,7 +88,8 @@ void Ctx::check_status(const char* when) {
         m += "  A sampler read a NaN / inf logit or critic score (the reference asserts finite logits every step: mingpt_sparse.py:383,388, cond_transformer_multi_view.py:202).";
     if (e & BG_ST_F16_RANGE)
         m += "  A value written as an f16 operand (hi / lo planes of precision='f16x3', fp16 KV cache, fp16 decode activations) was NaN or had |v| >= 65520: the f16 split has a "
-             "5-bit exponent where the reference's bf16 / fp32 arithmetic has 8.  Run this checkpoint with precision='fp32' (and kv_cache='f32').";
+             "5-bit exponent where the reference's bf16 / fp32 arithmetic has 8.  Run this checkpoint with precision='fp32' (and kv_cache='f32'); the VQGAN decoder alone also "
+             "with precision='f16x3r', which rescales its un-normalised activations instead of refusing them.";
     if (e & BG_ST_NONFINITE_PIXELS) m += "  The VQGAN decoder produced a NaN / inf pixel.";
     if (e & (BG_ST_MLP_BARRIER | BG_ST_MLP_PLACEMENT)) {
         m += std::string("  The fused MLP launch of the decode step failed:") + ((e & BG_ST_MLP_BARRIER) ? " an XCD-local barrier timed out - the launch did not have the GPU to itself;" : "") +

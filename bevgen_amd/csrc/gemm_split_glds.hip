@@ -34,14 +34,6 @@ namespace bevgen {
 
 typedef _Float16 half8 __attribute__((ext_vector_type(8)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-// sum over an aligned row of 16 lanes with DPP row operations (every lane of the row ends with the row's sum)
-__device__ __forceinline__ float row16_sum(float d) {
-    d += __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(d), 0xB1, 0xf, 0xf, true));    // quad_perm [1,0,3,2]
-    d += __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(d), 0x4E, 0xf, 0xf, true));    // quad_perm [2,3,0,1]
-    d += __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(d), 0x141, 0xf, 0xf, true));   // row_half_mirror
-    d += __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(d), 0x140, 0xf, 0xf, true));   // row_mirror
-    return d;
-}
 
 // x / d for many x and ONE d (a row's l2norm): the compiler's IEEE division is ten instructions per quotient (v_div_scale x 2, v_rcp, four fma, v_div_fmas, v_div_fixup)
 // and the fused q / k epilogues do 128 of them per lane - 5 of the 8 us that epilogue held the CU's VALUs with every matrix pipe idle.  The scaling and fix-up steps only

@@ -416,6 +416,14 @@ void launch_codebook_gather(const int64_t* ids, const float* codebook, float* ou
 void launch_nhwc_to_nchw(const float* x, float* y, int n, int hw, int C, int ldc, const float* mean, const float* stdv, int clamp01, hipStream_t s,
                          uint8_t* y8 = nullptr /* non-null: write round(v*255) as uint8 here instead of fp32 y */);
 void launch_nchw_to_nhwc(const float* x, float* y, int n, int hw, int C, hipStream_t s);
+// range-safe split precision (bevgen_cfg.vq_range): per-tensor power-of-two rescale of an un-normalised activation around a split-precision convolution.
+// e[0] = 0 where max |x| < 32768, else the smallest e with max |x| 2^-e < 32768 (`amax`: one zeroed device word; NaN / inf raise BG_ST_F16_RANGE and stay out of the max)
+void launch_range_exponent(const float* x, long elems /* % 4 == 0 */, unsigned* amax, int* e, hipStream_t s);
+void launch_range_split(const float* x, void* planes, long pixels, int C, const int* e, hipStream_t s);   // x 2^-e as the (hi, lo) plane image (C % 32 == 0)
+void launch_range_scale(const float* x, float* y, long elems, const int* e, hipStream_t s);                // x 2^-e in fp32
+// in place y [rows, C] = 2^e y + bias[c] (+ residual); gn_part non-null: also the GroupNorm partial sums of the result as the LDS-DMA convolution's epilogue leaves them
+// (GemmArgs::gn_part; needs groupnorm_partials_supported, a bias and no residual)
+void launch_range_unscale(float* y, const float* bias, const float* residual, long rows, int C, const int* e, float* gn_part, hipStream_t s);
 void launch_row_softmax(float* x, int rows, int cols, float scale, hipStream_t s, int ld = 0 /* row stride (0 = cols); columns [cols, ld) are zero-filled */);
 
 // misc

@@ -132,6 +132,10 @@ struct Ctx {
     std::vector<UpLevelW> up;  // index = level (0 = full resolution)
     const float *norm_out_w = nullptr, *norm_out_b = nullptr;
     float *denorm_mean = nullptr, *denorm_std = nullptr;
+    // range-safe mode (cfg.vq_range with the split precision): one (exponent, absmax word) slot per site and pass of the most recent decode call, device memory that is
+    // only grown; the host reads the exponents in bevgen_vq_range_exponents and nowhere else
+    Arena vq_range_slots;
+    int vq_range_used = 0;
     // ---- VQGAN encoder + quantizer (stage1/model.py:342-433, vqgan.py:84-116, quantize.py:271-312)
     bool has_vq_enc = false;
     int enc_cin_pad = 0;
@@ -214,6 +218,7 @@ void ar_forward(Ctx& c, const int64_t* cond, const float* I_inv, const float* E_
 void vq_finalize(Ctx& c);
 void vq_decode(Ctx& c, const int64_t* ids, const float* latents_nchw, int n, int lat_h, int lat_w, int out_mode, void* out, hipStream_t s);
 void vq_encode(Ctx& c, const float* x_nchw, int n, int RH, int RW, int64_t* ids, hipStream_t s);
+int vq_range_exponents(Ctx& c, int32_t* h_out, int cap);   // range-safe mode: exponents of the most recent vq_decode in site order (synchronises); returns their number
 // vqenc_kernels.hip
 void launch_nchw_to_nhwc_pad(const float* x, float* y, int n, int hw, int C, int Cpad, hipStream_t s);
 void launch_relayout_conv_weight_pad(const float* w, float* o, int cout, int cin, int cin_pad, int kh, int kw, hipStream_t s);

@@ -134,6 +134,132 @@ void launch_vq_out_conv(const float* x, const float* stats, const float* gamma, 
     LAUNCH_CHECK();
 }
 
+// ------------------------------------------------------------------------------------------------ range-safe split precision (precision = 'f16x3r')
+// The decoder's UN-normalised residual stream becomes an f16 operand in front of a few convolutions (upsample, nin_shortcut, conv_in).  A convolution is linear in its
+// input, so W x + b = 2^e (W (x 2^-e)) + b for any e; with e a per-tensor power of two both scalings are exact in every bit the (hi, lo) split keeps:
+//   range_absmax_kernel    max |x| of the tensor (one atomic max per wave on a zeroed word); NaN / inf raise BG_ST_F16_RANGE as the plane writers do and stay out of the max
+//   range_exponent_kernel  e = 0 where max |x| < 32768, else the smallest e with max |x| 2^-e < 32768 - ONE int in device memory, never read by the host on the decode path
+//   range_split_kernel     x 2^-e as (hi, lo) planes (the LDS-DMA convolution's operand) / range_scale_kernel: x 2^-e as fp32 (the register-staged kernel splits it itself)
+//   range_unscale_kernel   y = 2^e y + b[c] (+ residual) over the convolution's bias-free output; fmaf(1, y, b) rounds like the epilogue's y + b: e = 0 reproduces precision =
+//                          'f16x3' bit for bit.  Its second form also leaves the GroupNorm partial sums the skipped epilogue would have left (GemmArgs::gn_part), same layout,
+//                          same order of additions.
+__global__ __launch_bounds__(256) void range_absmax_kernel(const float4* __restrict__ x, long n4, unsigned* __restrict__ amax, unsigned* __restrict__ status) {
+    float m = 0.f;
+    unsigned bad = 0;
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x) {
+        const float4 v = x[i];
+        const float in[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            if (nonfinite(in[k])) bad = 1;
+            else m = fmaxf(m, fabsf(in[k]));
+        }
+    }
+    m = wave_max(m);
+    if ((threadIdx.x & 63) == 0 && m > 0.f) atomicMax(amax, __float_as_uint(m));   // (bit patterns of non-negative finite floats order like the floats)
+    if (bad) status_raise(status, BG_ST_F16_RANGE);
+}
+
+__global__ void range_exponent_kernel(const unsigned* __restrict__ amax, int* __restrict__ e_out) {
+    const int k = (int)(*amax >> 23) - 127;   // max |x| in [2^k, 2^(k+1)) (finite by construction: k <= 127)
+    *e_out = min(max(k - 14, 0), 113);        // 2^(k+1-e) <= 2^15; 2^-113 and 2^113 are normal floats
+}
+
+__device__ __forceinline__ float range_pow2(int e) { return __uint_as_float((unsigned)(127 + e) << 23); }
+
+__global__ __launch_bounds__(256) void range_split_kernel(const float4* __restrict__ x, _Float16* __restrict__ planes, long n4, int q4, const int* __restrict__ e,
+                                                          unsigned* __restrict__ status) {
+    const float sc = range_pow2(-*e);
+    unsigned bad = 0;
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x) {
+        const long pix = i / q4;
+        const int cq = (int)(i - pix * q4);
+        const float4 v = x[i];
+        // (x sc + 0 like launch_to_planes' x 1 + 0: the same bits at e = 0, the sign of a zero included)
+        store_planes4(planes + pix * 8 * q4, cq * 4, make_float4(fmaf(v.x, sc, 0.f), fmaf(v.y, sc, 0.f), fmaf(v.z, sc, 0.f), fmaf(v.w, sc, 0.f)), bad);
+    }
+    if (bad) status_raise(status, BG_ST_F16_RANGE);
+}
+
+__global__ __launch_bounds__(256) void range_scale_kernel(const float4* __restrict__ x, float4* __restrict__ y, long n4, const int* __restrict__ e) {
+    const float sc = range_pow2(-*e);
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x) {
+        const float4 v = x[i];
+        y[i] = make_float4(v.x * sc, v.y * sc, v.z * sc, v.w * sc);
+    }
+}
+
+__device__ __forceinline__ float4 range_unscale4(float4 v, float up, float4 b, const float4* __restrict__ R, long i) {
+    float4 o = make_float4(fmaf(up, v.x, b.x), fmaf(up, v.y, b.y), fmaf(up, v.z, b.z), fmaf(up, v.w, b.w));
+    if (R) { const float4 r = R[i]; o.x += r.x; o.y += r.y; o.z += r.z; o.w += r.w; }
+    return o;
+}
+
+__global__ __launch_bounds__(256) void range_unscale_kernel(float4* __restrict__ y, const float* __restrict__ bias, const float4* __restrict__ R, long n4, int q4,
+                                                            const int* __restrict__ e) {
+    const float up = range_pow2(*e);
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x) {
+        const int cq = (int)(i % q4);
+        const float4 b = bias ? reinterpret_cast<const float4*>(bias)[cq] : make_float4(0.f, 0.f, 0.f, 0.f);
+        y[i] = range_unscale4(y[i], up, b, R, i);
+    }
+}
+
+// One workgroup = 32 rows (pixels); lane = (row, one of two neighbouring channel quads), exactly the epilogue's assignment (gemm_split_glds.hip: r = lane & 31, h = lane >> 5),
+// the four waves share the 128-byte lines of an iteration.  rows % 32 == 0 and C % 32 == 0 (launcher): every lane is active in the DPP sums.
+__global__ __launch_bounds__(256) void range_unscale_gn_kernel(float* __restrict__ y, const float* __restrict__ bias, int C, const int* __restrict__ e, float* __restrict__ gn_part) {
+    const float up = range_pow2(*e);
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, r = lane & 31, h = lane >> 5;
+    const long m = (long)blockIdx.x * 32 + r;
+    for (int o = wave; o < (C >> 3); o += 4) {
+        const int n = 8 * o + 4 * h;
+        float4* p = reinterpret_cast<float4*>(y + m * C + n);
+        const float4 t = range_unscale4(*p, up, *reinterpret_cast<const float4*>(bias + n), nullptr, 0);
+        *p = t;
+        const float v[4] = {t.x, t.y, t.z, t.w};
+        float s4 = (v[0] + v[1]) + (v[2] + v[3]);
+        float q4 = fmaf(v[0], v[0], v[1] * v[1]) + fmaf(v[2], v[2], v[3] * v[3]);
+        s4 = row16_sum(s4); q4 = row16_sum(q4);
+        s4 += xor16(s4); q4 += xor16(q4);
+        if (r == 0) *reinterpret_cast<float2*>(gn_part + ((m >> 5) * (C >> 2) + (n >> 2)) * 2) = make_float2(s4, q4);
+    }
+}
+
+static dim3 range_grid(long n4) { return dim3((unsigned)std::max<long>(1, std::min<long>((n4 + 255) / 256, 8192))); }
+
+void launch_range_exponent(const float* x, long elems, unsigned* amax, int* e, hipStream_t s) {
+    BG_REQUIRE(elems > 0 && elems % 4 == 0, "range_exponent: element count %ld must be a positive multiple of 4", elems);
+    hipLaunchKernelGGL(range_absmax_kernel, range_grid(elems / 4), dim3(256), 0, s, reinterpret_cast<const float4*>(x), elems / 4, amax, status_current());
+    LAUNCH_CHECK();
+    hipLaunchKernelGGL(range_exponent_kernel, dim3(1), dim3(1), 0, s, amax, e);
+    LAUNCH_CHECK();
+}
+
+void launch_range_split(const float* x, void* planes, long pixels, int C, const int* e, hipStream_t s) {
+    BG_REQUIRE(C % 32 == 0 && pixels > 0, "range_split: C=%d must be a multiple of 32", C);
+    const long n4 = pixels * (C / 4);
+    hipLaunchKernelGGL(range_split_kernel, range_grid(n4), dim3(256), 0, s, reinterpret_cast<const float4*>(x), reinterpret_cast<_Float16*>(planes), n4, C / 4, e, status_current());
+    LAUNCH_CHECK();
+}
+
+void launch_range_scale(const float* x, float* y, long elems, const int* e, hipStream_t s) {
+    BG_REQUIRE(elems > 0 && elems % 4 == 0, "range_scale: element count %ld must be a positive multiple of 4", elems);
+    hipLaunchKernelGGL(range_scale_kernel, range_grid(elems / 4), dim3(256), 0, s, reinterpret_cast<const float4*>(x), reinterpret_cast<float4*>(y), elems / 4, e);
+    LAUNCH_CHECK();
+}
+
+void launch_range_unscale(float* y, const float* bias, const float* residual, long rows, int C, const int* e, float* gn_part, hipStream_t s) {
+    BG_REQUIRE(C % 4 == 0 && rows > 0, "range_unscale: C=%d must be a multiple of 4", C);
+    if (gn_part) {
+        BG_REQUIRE(rows % 32 == 0 && C % 32 == 0 && bias && !residual && rows / 32 <= 0x7FFFFFFFL, "range_unscale: GroupNorm partials need rows %% 32 == 0, C %% 32 == 0 and a bias (rows=%ld C=%d)", rows, C);
+        hipLaunchKernelGGL(range_unscale_gn_kernel, dim3((unsigned)(rows / 32)), dim3(256), 0, s, y, bias, C, e, gn_part);
+    } else {
+        const long n4 = rows * (C / 4);
+        hipLaunchKernelGGL(range_unscale_kernel, range_grid(n4), dim3(256), 0, s, reinterpret_cast<float4*>(y), bias, reinterpret_cast<const float4*>(residual), n4, C / 4, e);
+    }
+    LAUNCH_CHECK();
+}
+
 // x [n, C, hw] -> y [n, hw, C]
 __global__ __launch_bounds__(256) void nchw_to_nhwc_kernel(const float* __restrict__ x, float* __restrict__ y, long total, int hw, int C) {
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {

@@ -59,6 +59,11 @@ struct Act { float* p; int n, h, w, c; long elems() const { return (long)n * h *
 struct GnPart { float* buf = nullptr; const float* of = nullptr; };
 static void note_write(GnPart* gp, const float* y) { if (gp && gp->of == y) gp->of = nullptr; }
 
+static bool gn_epilogue() {
+    static const int gn_epi = getenv("BEVGEN_GN_EPILOGUE") ? atoi(getenv("BEVGEN_GN_EPILOGUE")) : 1;   // (0: always the statistics pass, for A/B runs)
+    return gn_epi != 0;
+}
+
 // planes: x.p holds the interleaved (hi, lo) f16 plane image of the activation (written by gn(..., planes = true)) instead of fp32
 void conv3(const Act& x, const ConvW& w, float* y, const float* residual, int up, hipStream_t s, bool planes = false, GnPart* gp = nullptr) {
     GemmArgs g;
@@ -72,8 +77,7 @@ void conv3(const Act& x, const ConvW& w, float* y, const float* residual, int up
     g.lda = w.cin; g.ldb = 9 * w.cin; g.ldc = w.cout; g.ldr = w.cout;
     g.conv_h = oh; g.conv_w = ow; g.conv_cin = w.cin; g.conv_up = up;
     // the LDS-DMA kernel (plane input) also leaves the GroupNorm partial sums of its output where the shape allows: the consumer's statistics pass disappears
-    static const int gn_epi = getenv("BEVGEN_GN_EPILOGUE") ? atoi(getenv("BEVGEN_GN_EPILOGUE")) : 1;   // (0: always the statistics pass, for A/B runs)
-    if (gn_epi && gp && gp->buf && planes && groupnorm_partials_supported(oh * ow, w.cout)) { g.gn_part = gp->buf; gp->of = y; }
+    if (gn_epilogue() && gp && gp->buf && planes && groupnorm_partials_supported(oh * ow, w.cout)) { g.gn_part = gp->buf; gp->of = y; }
     launch_gemm(g, s);
 }
 
@@ -86,13 +90,40 @@ void conv1(const float* x, long rows, const ConvW& w, float* y, const float* res
     launch_gemm(g, s);
 }
 
+// Range-safe mode (cfg.vq_range, split precision, decoder only): the sites where an UN-normalised activation becomes an f16 operand - conv_in (reads post_quant_conv's
+// output), every nin_shortcut and every upsample convolution (both read the residual stream) - take a per-tensor exponent from the next slot (kernels.h launch_range_*).
+// Everything else on the path reads a GroupNorm output or softmax-weighted values of one; the codebook and the weights are parameters, refused as before.
+struct RangeSites { int* exps = nullptr; unsigned* amax = nullptr; int used = 0, cap = 0; };
+
 struct DecWs {
     float *a, *b, *t;   // ping-pong activations + temp (each max_act floats)
     float* stats;       // [n*32*2]
     void* gn_ws;
     float *q, *k, *vT, *S;
     GnPart part;        // epilogue partials of the most recent convolution output (buf: groupnorm_part_floats of the widest level, or null)
+    RangeSites* range = nullptr;   // non-null: range-safe mode
 };
+
+const int* range_exponent(DecWs& ws, const Act& x, hipStream_t s) {
+    RangeSites& r = *ws.range;
+    BG_REQUIRE(r.used < r.cap, "vq_decode: more range-safe sites than counted (%d)", r.cap);
+    launch_range_exponent(x.p, x.elems(), r.amax + r.used, r.exps + r.used, s);
+    return r.exps + r.used++;
+}
+
+// range-safe form of a convolution that reads the un-normalised fp32 tensor x itself: x 2^-e into `tmp` (x's size), W x' without the bias, then y = 2^e y + b.
+// k = 1: 1x1, k = 3: 3x3 (up: fused nearest-2x upsample)
+void conv_ranged(const Act& x, const ConvW& w, int k, int up, float* tmp, float* y, DecWs& ws, hipStream_t s) {
+    const int* e = range_exponent(ws, x, s);
+    note_write(&ws.part, tmp);
+    launch_range_scale(x.p, tmp, x.elems(), e, s);
+    ConvW wb = w;
+    wb.b = nullptr;
+    const long rows = (long)x.n * x.h * x.w * (up ? 4 : 1);
+    if (k == 1) conv1(tmp, rows, wb, y, nullptr, s, &ws.part);
+    else conv3(Act{tmp, x.n, x.h, x.w, x.c}, wb, y, nullptr, up, s, false, &ws.part);
+    launch_range_unscale(y, w.b, nullptr, rows, w.cout, e, nullptr, s);
+}
 
 // statistics of x: from the producing convolution's epilogue partials when they describe exactly this tensor, else the pass over the tensor
 void gn_stats(const Act& x, DecWs& ws, hipStream_t s) {
@@ -118,7 +149,8 @@ void resblock(const ResBlockW& r, Act& x, float* y, float* scratch, DecWs& ws, h
     Act t2{ws.t, x.n, x.h, x.w, r.cout};
     const float* shortcut = x.p;
     if (r.has_nin) {  // x = nin_shortcut(x)  (1x1), written over h1 (no longer needed after norm2)
-        conv1(x.p, (long)x.n * x.h * x.w, r.nin, scratch, nullptr, s, &ws.part);
+        if (ws.range) conv_ranged(x, r.nin, 1, 0, y, scratch, ws, s);   // (y is free until conv2 writes it)
+        else conv1(x.p, (long)x.n * x.h * x.w, r.nin, scratch, nullptr, s, &ws.part);
         shortcut = scratch;
     }
     conv3(t2, r.c2, y, shortcut, 0, s, planes, &ws.part);  // y = x + conv2(...); its epilogue also leaves the statistics the next block's norm1 needs
@@ -243,10 +275,27 @@ void vq_decode(Ctx& c, const int64_t* ids, const float* latents_nchw, int n_tota
                         (size_t)chunk * attn_hwp * (3 * attn_c + attn_hwp) * sizeof(float) + (size_t)chunk * lat_hw * g.vq_embed_dim * sizeof(float) +
                         (size_t)chunk * RH * RW * 4 * sizeof(float) + 34 * 256;
     c.arena.reserve(need);
+    RangeSites sites;
+    c.vq_range_used = 0;
+    if (planes && g.vq_range) {
+        int per_pass = 1;   // conv_in
+        auto count = [&](const ResBlockW& r) { per_pass += r.has_nin ? 1 : 0; };
+        count(c.mid1); count(c.mid2);
+        for (const UpLevelW& u : c.up) {
+            for (const ResBlockW& r : u.blocks) count(r);
+            per_pass += u.has_up ? 1 : 0;
+        }
+        sites.cap = per_pass * cdiv(n_total, chunk);
+        c.vq_range_slots.reserve((size_t)sites.cap * 8);
+        sites.exps = reinterpret_cast<int*>(c.vq_range_slots.base);
+        sites.amax = reinterpret_cast<unsigned*>(sites.exps + sites.cap);
+        HIP_CHECK(hipMemsetAsync(sites.exps, 0, (size_t)sites.cap * 8, s));
+    }
     for (int i0 = 0; i0 < n_total; i0 += chunk) {
         const int n = std::min(chunk, n_total - i0);
         c.arena.reset();
         DecWs ws;
+        if (sites.cap) ws.range = &sites;
         if (planes) ws.part.buf = c.arena.get<float>((size_t)per_img * n / 64 + 64);   // GroupNorm partials of one tensor: (pixels / 32) x (channels / 4) x 2
         ws.a = c.arena.get<float>((size_t)per_img * n);
         ws.b = c.arena.get<float>((size_t)per_img * n);
@@ -265,7 +314,8 @@ void vq_decode(Ctx& c, const int64_t* ids, const float* latents_nchw, int n_tota
         else launch_nchw_to_nhwc(latents_nchw + (long)i0 * g.vq_embed_dim * lat_hw, zq, n, (int)lat_hw, g.vq_embed_dim, s);
         conv1(zq, lrows, c.post_quant, ws.t, nullptr, s);                       // post_quant_conv
         Act x{ws.t, n, lat_h, lat_w, g.vq_z_channels};
-        conv3(x, c.conv_in, ws.a, nullptr, 0, s, false, &ws.part);               // conv_in
+        if (ws.range) conv_ranged(x, c.conv_in, 3, 0, ws.b, ws.a, ws, s);
+        else conv3(x, c.conv_in, ws.a, nullptr, 0, s, false, &ws.part);          // conv_in
         x = Act{ws.a, n, lat_h, lat_w, c.conv_in.cout};
         // three rotating activation buffers (input / scratch / output of a block) + ws.t for the normalised tensor
         float* o = c.arena.get<float>((size_t)per_img * n);
@@ -302,9 +352,25 @@ void vq_decode(Ctx& c, const int64_t* ids, const float* latents_nchw, int n_tota
                 const int q4 = x.c >> 2;
                 if (planes && up_planes && (q4 & (q4 - 1)) == 0 && x.c % 32 == 0) {
                     note_write(&ws.part, ws.t);
-                    launch_to_planes(x.p, ws.t, x.n, x.h * x.w, x.c, s);
                     Act xp{ws.t, x.n, x.h, x.w, x.c};
-                    conv3(xp, u.up, y, nullptr, 1, s, true, &ws.part);
+                    if (ws.range) {
+                        // x 2^-e as planes, the convolution without its bias and without the epilogue statistics (they would describe the unscaled sums), then
+                        // y = 2^e y + b in one pass that also leaves those statistics where the epilogue would have
+                        const int* e = range_exponent(ws, x, s);
+                        launch_range_split(x.p, ws.t, (long)x.n * x.h * x.w, x.c, e, s);
+                        ConvW wb = u.up;
+                        wb.b = nullptr;
+                        conv3(xp, wb, y, nullptr, 1, s, true, nullptr);
+                        note_write(&ws.part, y);
+                        const bool part = gn_epilogue() && ws.part.buf && groupnorm_partials_supported(4 * x.h * x.w, u.up.cout);
+                        launch_range_unscale(y, u.up.b, nullptr, 4L * x.n * x.h * x.w, u.up.cout, e, part ? ws.part.buf : nullptr, s);
+                        if (part) ws.part.of = y;
+                    } else {
+                        launch_to_planes(x.p, ws.t, x.n, x.h * x.w, x.c, s);
+                        conv3(xp, u.up, y, nullptr, 1, s, true, &ws.part);
+                    }
+                } else if (ws.range) {
+                    conv_ranged(x, u.up, 3, 1, ws.t, y, ws, s);
                 } else {
                     conv3(x, u.up, y, nullptr, 1, s, false, &ws.part);
                 }
@@ -326,6 +392,15 @@ void vq_decode(Ctx& c, const int64_t* ids, const float* latents_nchw, int n_tota
         launch_nhwc_to_nchw(img, out_mode == 2 ? nullptr : reinterpret_cast<float*>(out) + o_off, n, RH * RW, g.vq_out_ch, g.vq_out_ch, denorm ? c.denorm_mean : nullptr,
                             denorm ? c.denorm_std : nullptr, denorm ? 1 : 0, s, out_mode == 2 ? reinterpret_cast<uint8_t*>(out) + o_off : nullptr);
     }
+    c.vq_range_used = sites.used;
+}
+
+// exponents of the most recent decode call (host array); synchronises
+int vq_range_exponents(Ctx& c, int32_t* out, int cap) {
+    HIP_CHECK(hipDeviceSynchronize());
+    const int n = std::min(c.vq_range_used, cap);
+    if (n > 0) HIP_CHECK(hipMemcpy(out, c.vq_range_slots.base, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost));
+    return c.vq_range_used;
 }
 
 // =====================================================================================================

@@ -5,7 +5,10 @@ every reference constructor on the path ends in ``**kwargs`` (gpt:270, ar_lm:55,
 option is: a key next to the ``_target_`` (``+model.transformer.kv_cache=f16`` on the command line), or process-wide by an environment variable.
 
     key             env var                  values                 drop-in default
-    precision       $BEVGEN_PRECISION        fp32 | f16x3           f16x3   (3 f16 MFMAs per product on hi/lo splits, fp32 accumulate; token-exact on every fixture)
+    precision       $BEVGEN_PRECISION        fp32 | f16x3 | f16x3r  f16x3   (3 f16 MFMAs per product on hi/lo splits, fp32 accumulate; token-exact on every fixture;
+                                                                            f16x3r = f16x3 whose VQGAN DECODER rescales an un-normalised activation outside the f16 range by
+                                                                            a per-tensor power of two instead of refusing the checkpoint - MaskGit, Route A and vq_encode
+                                                                            treat it exactly as f16x3)
     weights         $BEVGEN_WEIGHTS          f32 | f16              f32     (f16: GEMM / conv matrices rounded once at load, two MFMAs per product)
     kv_cache        $BEVGEN_KV_CACHE         f32 | f16              f32     (Route A; f16 = fp16 storage / fp32 accumulate: BASELINE config 4)
     decode_weights  $BEVGEN_DECODE_WEIGHTS   f32 | f16              f32     (Route A decode step streams 2-byte q/k/v, MLP and head weights)
@@ -20,7 +23,7 @@ import os
 from typing import Dict, Mapping, MutableMapping, Optional
 
 CHOICES = {
-    "precision": ("fp32", "f16x3"),
+    "precision": ("fp32", "f16x3", "f16x3r"),
     "weights": ("f32", "f16"),
     "kv_cache": ("f32", "f16"),
     "decode_weights": ("f32", "f16"),

@@ -73,10 +73,13 @@ class Context:
                              ("decode_weights", decode_weights, ("f32", "f16"))):
             if val not in ok:
                 raise ValueError(f"{key} must be one of {ok}, got {val!r}")
-        if precision not in ("fp32", "f16x3"):
-            raise ValueError(f"precision must be 'fp32' or 'f16x3', got {precision!r}")
+        if precision not in ("fp32", "f16x3", "f16x3r"):
+            raise ValueError(f"precision must be 'fp32', 'f16x3' or 'f16x3r', got {precision!r}")
         self.precision = precision
-        c.precision = {"fp32": _lib.PRECISION_FP32, "f16x3": _lib.PRECISION_F16X3}[precision]
+        # 'f16x3r' ("range-safe") = f16x3 whose VQGAN decoder rescales its un-normalised activations by a per-tensor power of two instead of refusing a checkpoint whose
+        # residual stream leaves the f16 range (bevgen_cfg.vq_range); the transformer routes and vq_encode behave exactly as under 'f16x3'
+        c.precision = {"fp32": _lib.PRECISION_FP32, "f16x3": _lib.PRECISION_F16X3, "f16x3r": _lib.PRECISION_F16X3}[precision]
+        c.vq_range = 1 if precision == "f16x3r" else 0
         c.max_batch = max_batch
         # Route A KV-cache storage: 'f32' (bit-exact tokens) or 'f16' (fp16 storage / fp32 accumulate, BASELINE config 4: half the decode traffic)
         c.kv_cache_dtype = {"f32": _lib.KV_F32, "f16": _lib.KV_F16}[kv_cache]
@@ -411,6 +414,14 @@ class Context:
         self._done(check)
         return out
 
+    def vq_range_exponents(self, cap: int = 4096):
+        """precision='f16x3r': the exponents the most recent vq_decode / vq_decode_latents chose, in site order (per pass of up to 48 images: conv_in, then every
+        nin_shortcut and upsample convolution as executed), as an int32 numpy array; empty in every other mode.  Synchronises."""
+        buf = (C.c_int32 * cap)()
+        n = C.c_int(0)
+        self._check(self.lib.bevgen_vq_range_exponents(self._h, buf, cap, C.byref(n)))
+        return np.frombuffer(buf, dtype=np.int32, count=min(n.value, cap)).copy()
+
     # ------------------------------------------------------------------------------------------ per-kernel HIP-event timing
     PROFILE_KINDS = ("gemm", "conv3x3", "attention", "decode_attention", "gemm_skinny", "gemm_small")
 
@@ -586,3 +597,15 @@ class Context:
         y = torch.empty_like(x_nhwc)
         self._check(self.lib.bevgen_op_groupnorm(self._h, _ptr(x_nhwc), _ptr(gamma), _ptr(beta), _ptr(y), n, H * W, Cc, int(swish), self._s()))
         return y
+
+    def op_range_split(self, x_nhwc, check=True):
+        """The range-safe operand preparation of precision='f16x3r' on its own: x [n, hw, C] fp32 (C % 32 == 0) -> (planes, e) with e the exponent (0 where max |x| < 32768,
+        else the smallest e with max |x| 2^-e < 32768; a one-element int32 tensor) and planes [n * hw, C / 32, 2, 32] float16 = the (hi, lo) image of x 2^-e:
+        x = (hi + lo 2^-11) 2^e.  NaN / inf in x raise BevgenError (ERR_NUMERIC)."""
+        x = _req(x_nhwc, torch.float32, self.device, "x")
+        n, hw, Cc = x.shape
+        planes = torch.empty((n * hw, Cc // 32, 2, 32), dtype=torch.float16, device=self.device)
+        e = torch.zeros((1,), dtype=torch.int32, device=self.device)
+        self._check(self.lib.bevgen_op_range_split(self._h, _ptr(x), n, hw, Cc, _ptr(planes), _ptr(e), self._s()))
+        self._done(check)
+        return planes, e

@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define BEVGEN_ABI_VERSION 7   /* 7: operator entries of the token samplers (bevgen_op_remask, _maskgit_pick, _critic_scores, _ar_pick, _ar_score_rows, _mean_fixed_order).  6: device status word (bevgen_synchronize, bevgen_status, BEVGEN_ERR_NUMERIC, BEVGEN_STATUS_*).  5: bevgen_op_mlp_fused; a context without max_batch <= 4 packs the split decode layer lazily (see Conventions).  4: 4: BEVGEN_PROFILE_KINDS 5 -> 6 (bevgen_profile_end writes 18 doubles), bevgen_cfg.decode_chains, decode_path values 2 / 3 */
+#define BEVGEN_ABI_VERSION 8   /* 8: bevgen_cfg.vq_range (taken out of reserved[]: the struct size is unchanged), bevgen_vq_range_exponents, bevgen_op_range_split.  7: operator entries of the token samplers (bevgen_op_remask, _maskgit_pick, _critic_scores, _ar_pick, _ar_score_rows, _mean_fixed_order).  6: device status word (bevgen_synchronize, bevgen_status, BEVGEN_ERR_NUMERIC, BEVGEN_STATUS_*).  5: bevgen_op_mlp_fused; a context without max_batch <= 4 packs the split decode layer lazily (see Conventions).  4: 4: BEVGEN_PROFILE_KINDS 5 -> 6 (bevgen_profile_end writes 18 doubles), bevgen_cfg.decode_chains, decode_path values 2 / 3 */
 
 enum { BEVGEN_ROUTE_MASKGIT = 0, BEVGEN_ROUTE_AR = 1 };
 /* FP32  : every product and accumulation in exact fp32 on the matrix cores (v_mfma_f32_32x32x2_f32) - bit-exact greedy tokens vs the CPU reference.
@@ -60,7 +60,11 @@ enum {
  *   - in bevgen_finalize (weights outside the f16 range of the chosen precision) and, as a message on stderr, in bevgen_destroy.
  * A raised word is returned as BEVGEN_ERR_NUMERIC (bits 4, 8, 16) or BEVGEN_ERR_INTERNAL (bits 1, 2) and then cleared.
  * Policy for precision = F16X3 / fp16 storage modes: an operand whose f16 image would be inf / NaN (|v| >= 65520) is an ERROR, not rescaled - the split keeps fp32-class
- * mantissas but f16's exponent range, where the reference's bf16 / fp32 arithmetic has 8 exponent bits; such a checkpoint must run with BEVGEN_PRECISION_FP32. */
+ * mantissas but f16's exponent range, where the reference's bf16 / fp32 arithmetic has 8 exponent bits; such a checkpoint must run with BEVGEN_PRECISION_FP32.
+ * One opt-in exception, stage-1 DECODE only: with bevgen_cfg.vq_range = 1 the un-normalised activation tensors of the decoder that become f16 operands (in front of the
+ * upsample convolutions, the nin_shortcut convolutions and conv_in) are rescaled by a per-tensor power of two chosen on the device (exact in every bit the split keeps), so
+ * BEVGEN_STATUS_F16_RANGE is then raised by the decoder only for NaN / inf activations and for a codebook entry outside the range.  Weights outside the range are refused by
+ * bevgen_finalize in either setting; the transformer routes and bevgen_vq_encode ignore vq_range. */
 enum {
     BEVGEN_STATUS_MLP_BARRIER = 1,        /* fused MLP launch of the decode step: an XCD-local barrier timed out (the GPU was shared); the context falls back to two launches */
     BEVGEN_STATUS_MLP_PLACEMENT = 2,      /* ...: a workgroup was not placed on the XCD its index implies */
@@ -112,7 +116,12 @@ typedef struct bevgen_cfg {
                                                           layer kernels are enqueued on separate HIP streams (one fork / join per step inside the captured graph), so
                                                           that one chain's weight-streaming projections run under another chain's K/V stream instead of every short
                                                           dependent kernel paying its ramp alone.  0 = the library's choice for the batch, 1 = a single chain */
-    int32_t reserved[10];
+    int32_t vq_range;                                  /* stage-1 decoder with BEVGEN_PRECISION_F16X3: 0 (default) = an un-normalised activation outside the f16 operand range
+                                                          is refused (BEVGEN_STATUS_F16_RANGE); 1 = "range-safe": per call and per site, a device-side absmax of the tensor, an
+                                                          exponent e (0 where absmax < 32768, else the smallest e with absmax 2^-e < 32768), the operand split as x 2^-e and the
+                                                          convolution's result formed as 2^e (W x') + bias (+ residual).  No host synchronisation; e = 0 everywhere gives the bits
+                                                          of vq_range = 0.  The encoder is not covered yet; ignored with BEVGEN_PRECISION_FP32 */
+    int32_t reserved[9];
 } bevgen_cfg;
 
 typedef struct bevgen_ctx bevgen_ctx;
@@ -268,6 +277,11 @@ int bevgen_vq_encode(bevgen_ctx* ctx, const float* d_x, int n, int H, int W, int
 /* VQModel.decode(quant) (stage1/vqgan.py:118-121) for already looked-up latents: d_zq [n, embed_dim, lat_h, lat_w] (NCHW, like the reference). */
 int bevgen_vq_decode_latents(bevgen_ctx* ctx, const float* d_zq, int n, int lat_h, int lat_w, int out_mode, void* d_out, void* stream);
 
+/* vq_range = 1: the exponents the most recent bevgen_vq_decode / bevgen_vq_decode_latents call on this context chose, in site order (per pass of up to 48 images: conv_in,
+ * then every nin_shortcut and upsample convolution in execution order), written to the HOST array h_out[cap]; *count = their number (may exceed cap; 0 with vq_range = 0
+ * or before the first call).  Synchronises the device. */
+int bevgen_vq_range_exponents(bevgen_ctx* ctx, int32_t* h_out, int cap, int* count);
+
 /* ---------------------------------------------------------------------------------------------------------------
  * Operator-level entry points (parity tests and roofline measurements call the kernels through these)             */
 int bevgen_op_gemm(bevgen_ctx* ctx, const float* d_a, const float* d_w, const float* d_bias, const float* d_residual, float* d_c,
@@ -341,6 +355,9 @@ int bevgen_op_conv3x3(bevgen_ctx* ctx, const float* d_x_nhwc, const float* d_w_o
                       float* d_y_nhwc, int n, int H, int W, int Cin, int Cout, int upsample2x, void* stream);
 int bevgen_op_groupnorm(bevgen_ctx* ctx, const float* d_x_nhwc, const float* d_gamma, const float* d_beta, float* d_y, int n, int hw, int C,
                         int swish, void* stream);
+/* The range-safe operand preparation on its own (vq_range = 1): d_x [n, hw, C] fp32 (C % 32 == 0) -> d_exp[0] = e (the rule at bevgen_cfg.vq_range) and
+ * d_planes = the interleaved (hi, lo) f16 plane image [n * hw][C / 32][2][32] of x 2^-e (x = (hi + lo 2^-11) 2^e).  NaN / inf in d_x raise BEVGEN_STATUS_F16_RANGE. */
+int bevgen_op_range_split(bevgen_ctx* ctx, const float* d_x, int n, int hw, int C, void* d_planes, int32_t* d_exp, void* stream);
 
 /* Per-kernel timing support for bench.py's roofline leg: number of workgroup splits the decode-attention kernel uses. */
 int bevgen_decode_attention_splits(int B, int H, int n);
