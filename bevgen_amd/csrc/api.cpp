@@ -639,6 +639,44 @@ int bevgen_op_range_split(bevgen_ctx* ctx, const float* x, int n, int hw, int C,
     });
 }
 
+int bevgen_op_conv3x3_down(bevgen_ctx* ctx, const float* x, const float* w, const float* bias, float* y, int n, int H, int W, int Cin, int Cout, void* stream) {
+    return guarded(ctx, [&] {
+        BG_REQUIRE(x && w && y, "op_conv3x3_down: null argument");
+        vq_op_conv3x3_down(*ctx, x, w, bias, y, n, H, W, Cin, Cout, (hipStream_t)stream);
+    });
+}
+
+int bevgen_op_vq_attn_block(bevgen_ctx* ctx, const float* x, const float* norm_w, const float* norm_b, const float* wq, const float* bq, const float* wk, const float* bk,
+                            const float* wv, const float* bv, const float* wp, const float* bp, float* y, int n, int h, int w, int C, void* stream) {
+    return guarded(ctx, [&] {
+        BG_REQUIRE(x && norm_w && norm_b && wq && bq && wk && bk && wv && bv && wp && bp && y, "op_vq_attn_block: null argument");
+        vq_op_attn_block(*ctx, x, norm_w, norm_b, wq, bq, wk, bk, wv, bv, wp, bp, y, n, h, w, C, (hipStream_t)stream);
+    });
+}
+
+int bevgen_op_vq_out_tail(bevgen_ctx* ctx, const float* x, const float* norm_w, const float* norm_b, const float* w, const float* bias, const float* mean, const float* stdv,
+                          int out_mode, int three_kernels, void* out, int n, int H, int W, int C, void* stream) {
+    return guarded(ctx, [&] {
+        BG_REQUIRE(x && norm_w && norm_b && w && out, "op_vq_out_tail: null argument");
+        vq_op_out_tail(*ctx, x, norm_w, norm_b, w, bias, mean, stdv, out_mode, three_kernels, out, n, H, W, C, (hipStream_t)stream);
+    });
+}
+
+int bevgen_op_vq_quantize(bevgen_ctx* ctx, const float* z, const float* codebook, int64_t* ids, float* zz, float* ee, long rows, int n_e, int D, void* stream) {
+    return guarded(ctx, [&] {
+        BG_REQUIRE(z && codebook && ids, "op_vq_quantize: null argument");
+        vq_op_quantize(*ctx, z, codebook, ids, zz, ee, rows, n_e, D, (hipStream_t)stream);
+    });
+}
+
+int bevgen_op_conv3x3_gn_stats(bevgen_ctx* ctx, const float* x, const float* w, const float* bias, int range_route, float* y, float* part, float* stats, int n, int H, int W,
+                               int Cin, int Cout, void* stream) {
+    return guarded(ctx, [&] {
+        BG_REQUIRE(x && w && y && part && stats, "op_conv3x3_gn_stats: null argument");
+        vq_op_conv3x3_gn_stats(*ctx, x, w, bias, range_route, y, part, stats, n, H, W, Cin, Cout, (hipStream_t)stream);
+    });
+}
+
 int bevgen_decode_attention_splits(int B, int H, int n) { return decode_attention_splits(B, H, n); }
 
 int bevgen_profile_begin(bevgen_ctx* ctx) {

@@ -90,7 +90,8 @@ enum : unsigned {
     BG_ST_NONFINITE_LOGITS = 4u, // a sampler saw a NaN / inf logit or critic score (the reference: assert (~logits.isfinite()).sum() == 0)
     BG_ST_F16_RANGE = 8u,        // a value written as an f16 operand (hi/lo planes of precision = f16x3, fp16 KV cache, fp16 decode activations) was NaN or |v| >= 65520:
                                  // the f16 image is inf / NaN where the reference's bf16 / fp32 arithmetic has an 8-bit exponent
-    BG_ST_NONFINITE_PIXELS = 16u // the VQGAN decoder produced a NaN / inf pixel
+    BG_ST_NONFINITE_PIXELS = 16u,// the VQGAN decoder produced a NaN / inf pixel
+    BG_ST_NONFINITE_LATENTS = 32u // the VQGAN quantizer met a row without a finite distance to any codebook entry (its id is written as 0)
 };
 // device address of the status word of the context whose C-ABI call is executing on this host thread (null outside a call): the launchers of the flagged kernels read it
 unsigned* status_current();

@@ -191,6 +191,46 @@ void attnblock(const AttnBlockW& a, Act& x, float* y, DecWs& ws, hipStream_t s) 
     x = Act{y, n, x.h, x.w, C};
 }
 
+// Downsample (stage1/model.py:56-75): F.pad(x, (0,1,0,1)) + 3x3 convolution, stride 2, padding 0; x.h and x.w even.  The bottom / right zero padding is the gather's bounds test.
+void conv3_down(const Act& x, const ConvW& w, float* y, hipStream_t s) {
+    GemmArgs ga;
+    ga.mode = MODE_CONV3;
+    ga.A = x.p; ga.B = w.w; ga.C = y; ga.bias_n = w.b;
+    ga.M = x.n * (x.h / 2) * (x.w / 2); ga.N = w.cout; ga.K = 9 * w.cin;
+    ga.lda = w.cin; ga.ldb = 9 * w.cin; ga.ldc = w.cout;
+    ga.conv_h = x.h / 2; ga.conv_w = x.w / 2; ga.conv_cin = w.cin; ga.conv_up = 0;
+    ga.conv_hin = x.h; ga.conv_win = x.w; ga.conv_stride = 2; ga.conv_pad = 0;
+    launch_gemm(ga, s);
+}
+
+// VectorQuantizer2.forward (stage1/quantize.py:271-312): ids = argmin_j (|z|^2 + |e_j|^2) - 2 z.e_j, exact fp32 products (the codebook is never split); ee = |e_j|^2
+void quantize(const float* z, const float* codebook, const float* ee, float* zz, float* dots, int64_t* ids, long rows, int n_e, int D, hipStream_t s) {
+    launch_row_sqnorm(z, zz, rows, D, s);
+    GemmArgs gd;
+    gd.A = z; gd.B = codebook; gd.C = dots;
+    gd.M = (int)rows; gd.N = n_e; gd.K = D; gd.lda = D; gd.ldb = D; gd.ldc = n_e;
+    launch_gemm(gd, s);
+    launch_vq_argmin(dots, zz, ee, ids, rows, n_e, s);
+}
+
+// Decoder.forward's last operators (norm_out, swish, conv_out) + denormalise + NCHW / uint8 store: one kernel, or (fused = false, or a shape it does not take) three.
+// out_mode as in vq_decode; mean / stdv are read for out_mode != 0 only; img: [n, h w, cout] scratch of the three-kernel form
+void out_tail(const Act& x, const float* nw, const float* nb, const ConvW& co, const float* mean, const float* stdv, int out_mode, bool fused, void* out, float* img, DecWs& ws,
+              bool planes, hipStream_t s) {
+    const int denorm = out_mode != 0;
+    float* of = out_mode == 2 ? nullptr : reinterpret_cast<float*>(out);
+    uint8_t* o8 = out_mode == 2 ? reinterpret_cast<uint8_t*>(out) : nullptr;
+    if (fused && vq_out_conv_supported(x.c, co.cout)) {   // norm_out + swish + conv_out + denormalise + layout in one kernel
+        gn_stats(x, ws, s);
+        launch_vq_out_conv(x.p, ws.stats, nw, nb, co.w, co.b, denorm ? mean : nullptr, denorm ? stdv : nullptr, denorm ? 1 : 0, of, o8, x.n, x.h, x.w, x.c, co.cout, s);
+        return;
+    }
+    gn(x, nw, nb, ws.t, 1, ws, s, planes);
+    Act t{ws.t, x.n, x.h, x.w, x.c};
+    conv3(t, co, img, nullptr, 0, s, planes);  // [n, h w, cout]
+    launch_nhwc_to_nchw(img, of, x.n, x.h * x.w, co.cout, co.cout, denorm ? mean : nullptr, denorm ? stdv : nullptr, denorm ? 1 : 0, s, o8);
+}
+
 }  // namespace
 
 static void vq_enc_finalize(Ctx& c);
@@ -379,18 +419,8 @@ void vq_decode(Ctx& c, const int64_t* ids, const float* latents_nchw, int n_tota
         }
         const long o_off = (long)i0 * g.vq_out_ch * RH * RW;
         static const bool tail_off = getenv("BEVGEN_VQ_TAIL") && atoi(getenv("BEVGEN_VQ_TAIL")) == 0;   // (A/B switch: 0 = the three-kernel tail)
-        if (!tail_off && vq_out_conv_supported(x.c, g.vq_out_ch)) {   // norm_out + swish + conv_out + denormalise + layout in one kernel
-            gn_stats(x, ws, s);
-            launch_vq_out_conv(x.p, ws.stats, c.norm_out_w, c.norm_out_b, c.conv_out.w, c.conv_out.b, denorm ? c.denorm_mean : nullptr, denorm ? c.denorm_std : nullptr, denorm ? 1 : 0,
-                               out_mode == 2 ? nullptr : reinterpret_cast<float*>(out) + o_off, out_mode == 2 ? reinterpret_cast<uint8_t*>(out) + o_off : nullptr, x.n, x.h, x.w, x.c,
-                               g.vq_out_ch, s);
-            continue;
-        }
-        gn(x, c.norm_out_w, c.norm_out_b, ws.t, 1, ws, s, planes);
-        Act t{ws.t, x.n, x.h, x.w, x.c};
-        conv3(t, c.conv_out, img, nullptr, 0, s, planes);  // [n, RH*RW, out_ch]
-        launch_nhwc_to_nchw(img, out_mode == 2 ? nullptr : reinterpret_cast<float*>(out) + o_off, n, RH * RW, g.vq_out_ch, g.vq_out_ch, denorm ? c.denorm_mean : nullptr,
-                            denorm ? c.denorm_std : nullptr, denorm ? 1 : 0, s, out_mode == 2 ? reinterpret_cast<uint8_t*>(out) + o_off : nullptr);
+        void* o_ptr = out_mode == 2 ? static_cast<void*>(reinterpret_cast<uint8_t*>(out) + o_off) : static_cast<void*>(reinterpret_cast<float*>(out) + o_off);
+        out_tail(x, c.norm_out_w, c.norm_out_b, c.conv_out, c.denorm_mean, c.denorm_std, out_mode, !tail_off, o_ptr, img, ws, planes, s);
     }
     c.vq_range_used = sites.used;
 }
@@ -521,14 +551,7 @@ void vq_encode(Ctx& c, const float* x_nchw, int n_total, int RH, int RW, int64_t
             }
             if (d.has_down) {  // F.pad(x, (0,1,0,1)) + conv 3x3 stride 2 padding 0
                 float *sc, *y; pick2(sc, y);
-                GemmArgs ga;
-                ga.mode = MODE_CONV3;
-                ga.A = x.p; ga.B = d.down.w; ga.C = y; ga.bias_n = d.down.b;
-                ga.M = x.n * (x.h / 2) * (x.w / 2); ga.N = d.down.cout; ga.K = 9 * d.down.cin;
-                ga.lda = d.down.cin; ga.ldb = 9 * d.down.cin; ga.ldc = d.down.cout;
-                ga.conv_h = x.h / 2; ga.conv_w = x.w / 2; ga.conv_cin = d.down.cin; ga.conv_up = 0;
-                ga.conv_hin = x.h; ga.conv_win = x.w; ga.conv_stride = 2; ga.conv_pad = 0;
-                launch_gemm(ga, s);
+                conv3_down(x, d.down, y, s);
                 x = Act{y, x.n, x.h / 2, x.w / 2, d.down.cout};
             }
         }
@@ -540,14 +563,147 @@ void vq_encode(Ctx& c, const float* x_nchw, int n_total, int RH, int RW, int64_t
         float *sc, *y; pick2(sc, y);
         conv3(t, c.enc_conv_out, y, nullptr, 0, s, planes);                     // [n, lat*lat, z_channels]
         conv1(y, lrows, c.quant_conv, zq, nullptr, s);                  // quant_conv (1x1)
-        // distances to the codebook: (|z|^2 + |e|^2) - 2 z.e, arg-min (exact fp32 products: the codebook is never split)
-        launch_row_sqnorm(zq, zz, lrows, g.vq_embed_dim, s);
-        GemmArgs gd;
-        gd.A = zq; gd.B = c.codebook; gd.C = dots;
-        gd.M = (int)lrows; gd.N = g.vq_n_embed; gd.K = g.vq_embed_dim; gd.lda = g.vq_embed_dim; gd.ldb = g.vq_embed_dim; gd.ldc = g.vq_n_embed;
-        launch_gemm(gd, s);
-        launch_vq_argmin(dots, zz, c.codebook_sqnorm, ids + (long)i0 * lat_hw, lrows, g.vq_n_embed, s);
+        quantize(zq, c.codebook, c.codebook_sqnorm, zz, dots, ids + (long)i0 * lat_hw, lrows, g.vq_n_embed, g.vq_embed_dim, s);
     }
+}
+
+// =====================================================================================================
+// Operator entries (bevgen_op_* in api.cpp): the pieces above on caller-supplied device tensors, at shapes of their own.  They forward to the launchers / helpers the model
+// path uses and add no arithmetic.  Weights arrive as the checkpoint stores them ([Cout][Cin][kh][kw]) and are prepared the way load_conv prepares them, into the arena.
+// =====================================================================================================
+namespace {
+
+// The weights of one operator call: re-laid out into the arena and, in split-precision mode, registered as split weights FOR THE DURATION OF THE CALL (the registry is
+// keyed by pointer and the arena hands the same addresses to the next call: a registration that outlived the call would serve stale planes).
+struct OpWeights {
+    Ctx& c;
+    hipStream_t s;
+    std::vector<const float*> keys;
+    OpWeights(Ctx& c_, hipStream_t s_) : c(c_), s(s_) {}
+    ~OpWeights() { for (const float* k : keys) c.split.erase(k); }
+    static size_t bytes(int cout, int cin, int k) { return 2 * ((size_t)cout * cin * k * k * sizeof(float) + 256); }
+    ConvW conv(const float* w_oihw, const float* b, int cout, int cin, int k) {
+        ConvW cw;
+        cw.cout = cout; cw.cin = cin; cw.k = k; cw.b = b;
+        const long n = (long)cout * cin * k * k;
+        cw.w = c.arena.get<float>((size_t)n);
+        launch_relayout_conv_weight(w_oihw, cw.w, cout, cin, k, k, s);
+        if (c.cfg.precision == BEVGEN_PRECISION_F16X3) {
+            void* planes = c.arena.alloc((size_t)n * 4);
+            const bool w16 = c.cfg.weight_dtype == BEVGEN_W_F16;
+            if (w16) launch_round_to_f16(cw.w, nullptr, n, s);
+            launch_split_weight(cw.w, planes, n, s);
+            c.split[cw.w] = SplitPlanes{reinterpret_cast<const uint16_t*>(planes), reinterpret_cast<const uint16_t*>(planes) + 32, w16};
+            keys.push_back(cw.w);
+        }
+        return cw;
+    }
+};
+
+}  // namespace
+
+void vq_op_conv3x3_down(Ctx& c, const float* x, const float* w, const float* bias, float* y, int n, int H, int W, int Cin, int Cout, hipStream_t s) {
+    BG_REQUIRE(n >= 1 && H >= 2 && W >= 2 && H % 2 == 0 && W % 2 == 0 && Cin >= 32 && Cin % 32 == 0 && Cout >= 1,
+               "op_conv3x3_down: needs even H, W and Cin %% 32 == 0 (H=%d W=%d Cin=%d)", H, W, Cin);
+    c.arena.reserve(OpWeights::bytes(Cout, Cin, 3) + 4096);
+    c.arena.reset();
+    OpWeights ow(c, s);
+    const ConvW cw = ow.conv(w, bias, Cout, Cin, 3);
+    conv3_down(Act{const_cast<float*>(x), n, H, W, Cin}, cw, y, s);
+}
+
+void vq_op_attn_block(Ctx& c, const float* x, const float* norm_w, const float* norm_b, const float* wq, const float* bq, const float* wk, const float* bk, const float* wv,
+                      const float* bv, const float* wp, const float* bp, float* y, int n, int h, int w, int C, hipStream_t s) {
+    BG_REQUIRE(n >= 1 && h >= 1 && w >= 1 && C >= 32 && C % 32 == 0 && C <= 1024, "op_vq_attn_block: C=%d must be a multiple of 32 (at most 1024)", C);
+    BG_REQUIRE(x != y, "op_vq_attn_block: the output must not alias the input (the residual is read by the last GEMM)");
+    const long hw = (long)h * w, hwp = round_up(hw, 32);
+    const size_t f = sizeof(float);
+    const size_t qb = (size_t)n * hwp * C * f, sb = (size_t)n * hwp * hwp * f;
+    c.arena.reserve(4 * OpWeights::bytes(C, C, 1) + (size_t)n * hw * C * f + (size_t)n * 64 * f + groupnorm_ws_bytes(n, (int)hw) + 3 * qb + sb + 16 * 256);
+    c.arena.reset();
+    OpWeights ow(c, s);
+    AttnBlockW a;
+    a.nw = norm_w; a.nb = norm_b; a.c = C;
+    a.q = ow.conv(wq, bq, C, C, 1); a.k = ow.conv(wk, bk, C, C, 1); a.v = ow.conv(wv, bv, C, C, 1); a.proj = ow.conv(wp, bp, C, C, 1);
+    DecWs ws{};
+    ws.t = c.arena.get<float>((size_t)n * hw * C);
+    ws.stats = c.arena.get<float>((size_t)n * 64);
+    ws.gn_ws = c.arena.alloc(groupnorm_ws_bytes(n, (int)hw));
+    ws.q = c.arena.get<float>(qb / f);
+    ws.k = c.arena.get<float>(qb / f);
+    ws.vT = c.arena.get<float>(qb / f);
+    ws.S = c.arena.get<float>(sb / f);
+    // the model's workspace holds whatever the previous kernels left there: NaN bit patterns here, so that a pad column that is read without having been written shows
+    HIP_CHECK(hipMemsetAsync(ws.q, 0xFF, qb, s));
+    HIP_CHECK(hipMemsetAsync(ws.k, 0xFF, qb, s));
+    HIP_CHECK(hipMemsetAsync(ws.vT, 0xFF, qb, s));
+    HIP_CHECK(hipMemsetAsync(ws.S, 0xFF, sb, s));
+    Act xa{const_cast<float*>(x), n, h, w, C};
+    attnblock(a, xa, y, ws, s);
+}
+
+void vq_op_out_tail(Ctx& c, const float* x, const float* norm_w, const float* norm_b, const float* w, const float* bias, const float* mean, const float* stdv, int out_mode,
+                    int three_kernels, void* out, int n, int H, int W, int C, hipStream_t s) {
+    const int cout = 3;
+    BG_REQUIRE(n >= 1 && H >= 1 && W >= 1 && C >= 32 && C % 32 == 0 && C <= 1024, "op_vq_out_tail: C=%d must be a multiple of 32 (at most 1024)", C);
+    BG_REQUIRE(out_mode >= 0 && out_mode <= 2 && (out_mode == 0 || (mean && stdv)), "op_vq_out_tail: out_mode 0 / 1 / 2; 1 and 2 need mean and std");
+    const bool planes = c.cfg.precision == BEVGEN_PRECISION_F16X3;
+    const long hw = (long)H * W;
+    const size_t f = sizeof(float);
+    c.arena.reserve(OpWeights::bytes(cout, C, 3) + (size_t)n * hw * C * f + (size_t)n * 64 * f + groupnorm_ws_bytes(n, (int)hw) + (size_t)n * hw * 4 * f + 8 * 256);
+    c.arena.reset();
+    OpWeights ow(c, s);
+    const ConvW co = ow.conv(w, bias, cout, C, 3);
+    DecWs ws{};
+    ws.t = c.arena.get<float>((size_t)n * hw * C);
+    ws.stats = c.arena.get<float>((size_t)n * 64);
+    ws.gn_ws = c.arena.alloc(groupnorm_ws_bytes(n, (int)hw));
+    float* img = c.arena.get<float>((size_t)n * hw * 4);
+    out_tail(Act{const_cast<float*>(x), n, H, W, C}, norm_w, norm_b, co, mean, stdv, out_mode, three_kernels == 0, out, img, ws, planes, s);
+}
+
+void vq_op_quantize(Ctx& c, const float* z, const float* codebook, int64_t* ids, float* zz_out, float* ee_out, long rows, int n_e, int D, hipStream_t s) {
+    BG_REQUIRE(rows >= 1 && rows <= 0x7FFFFFFFL && n_e >= 1 && D >= 32 && D % 32 == 0, "op_vq_quantize: needs D %% 32 == 0 (rows=%ld n_e=%d D=%d)", rows, n_e, D);
+    c.arena.reserve(((size_t)rows * n_e + (size_t)rows + (size_t)n_e) * sizeof(float) + 8 * 256);
+    c.arena.reset();
+    float* dots = c.arena.get<float>((size_t)rows * n_e);
+    float* zz = c.arena.get<float>((size_t)rows);
+    float* ee = c.arena.get<float>((size_t)n_e);
+    launch_row_sqnorm(codebook, ee, n_e, D, s);   // (the model: once, at finalize)
+    quantize(z, codebook, ee, zz, dots, ids, rows, n_e, D, s);
+    if (zz_out) HIP_CHECK(hipMemcpyAsync(zz_out, zz, (size_t)rows * sizeof(float), hipMemcpyDeviceToDevice, s));
+    if (ee_out) HIP_CHECK(hipMemcpyAsync(ee_out, ee, (size_t)n_e * sizeof(float), hipMemcpyDeviceToDevice, s));
+}
+
+void vq_op_conv3x3_gn_stats(Ctx& c, const float* x, const float* w, const float* bias, int range_route, float* y, float* part, float* stats, int n, int H, int W, int Cin,
+                            int Cout, hipStream_t s) {
+    BG_REQUIRE(c.cfg.precision == BEVGEN_PRECISION_F16X3, "op_conv3x3_gn_stats: the convolution epilogue that leaves GroupNorm partials belongs to the split-precision mode (precision = f16x3)");
+    BG_REQUIRE(gn_epilogue(), "op_conv3x3_gn_stats: the epilogue statistics are switched off (BEVGEN_GN_EPILOGUE=0)");
+    const int hw = H * W, q4 = Cin >> 2;
+    BG_REQUIRE(n >= 1 && H >= 1 && W >= 1 && Cin >= 32 && Cin % 32 == 0 && (q4 & (q4 - 1)) == 0 && bias, "op_conv3x3_gn_stats: needs a bias and Cin / 4 a power of two >= 8 (Cin=%d)", Cin);
+    BG_REQUIRE(groupnorm_partials_supported(hw, Cout), "groupnorm from partials: unsupported shape hw=%d C=%d", hw, Cout);
+    c.arena.reserve(OpWeights::bytes(Cout, Cin, 3) + (size_t)n * hw * Cin * sizeof(float) + 4 * 256);
+    c.arena.reset();
+    OpWeights ow(c, s);
+    ConvW cw = ow.conv(w, bias, Cout, Cin, 3);
+    float* planes = c.arena.get<float>((size_t)n * hw * Cin);
+    Act xp{planes, n, H, W, Cin};
+    if (range_route) {   // the upsample site of the range-safe mode without the upsample, exponent 0: planes, the convolution without its bias, then bias + statistics in one pass
+        int* e = c.arena.get<int>(1);
+        HIP_CHECK(hipMemsetAsync(e, 0, sizeof(int), s));
+        launch_range_split(x, planes, (long)n * hw, Cin, e, s);
+        ConvW wb = cw;
+        wb.b = nullptr;
+        conv3(xp, wb, y, nullptr, 0, s, true, nullptr);
+        launch_range_unscale(y, cw.b, nullptr, (long)n * hw, Cout, e, part, s);
+    } else {
+        launch_to_planes(x, planes, n, hw, Cin, s);
+        GnPart gp;
+        gp.buf = part;
+        conv3(xp, cw, y, nullptr, 0, s, true, &gp);
+        BG_REQUIRE(gp.of == y, "op_conv3x3_gn_stats: the convolution did not leave partials");
+    }
+    launch_groupnorm_stats_from_partials(part, stats, n, hw, Cout, 1e-6f, s);
 }
 
 }  // namespace bevgen

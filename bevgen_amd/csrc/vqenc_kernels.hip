@@ -54,9 +54,10 @@ void launch_row_sqnorm(const float* x, float* out, long rows, int D, hipStream_t
     LAUNCH_CHECK();
 }
 
-// ids[row] = argmin_j (zz[row] + ee[j]) - 2 * dots[row, j]; ties -> lowest index (torch.argmin)
+// ids[row] = argmin_j (zz[row] + ee[j]) - 2 * dots[row, j]; ties -> lowest index (torch.argmin).  A NaN distance never wins.  A row without any finite distance (NaN / inf
+// in the image, an overflow in the encoder: `d < best` is false for NaN and for inf < inf) has no minimum: BG_ST_NONFINITE_LATENTS is raised and the in-range id 0 written.
 __global__ __launch_bounds__(256) void vq_argmin_kernel(const float* __restrict__ dots, const float* __restrict__ zz, const float* __restrict__ ee, int64_t* __restrict__ ids,
-                                                        long rows, int n_e) {
+                                                        long rows, int n_e, unsigned* __restrict__ status) {
     const int lane = threadIdx.x & 63;
     const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (row >= rows) return;
@@ -73,10 +74,14 @@ __global__ __launch_bounds__(256) void vq_argmin_kernel(const float* __restrict_
         const int oi = __shfl_xor(bidx, o, 64);
         if (ob < best || (ob == best && oi < bidx)) { best = ob; bidx = oi; }
     }
-    if (lane == 0) ids[row] = bidx;
+    if (lane == 0) {
+        const bool none = bidx == 0x7fffffff;
+        if (none) status_raise(status, BG_ST_NONFINITE_LATENTS);
+        ids[row] = none ? 0 : bidx;
+    }
 }
 void launch_vq_argmin(const float* dots, const float* zz, const float* ee, int64_t* ids, long rows, int n_e, hipStream_t s) {
-    hipLaunchKernelGGL(vq_argmin_kernel, dim3((int)((rows + 3) / 4)), dim3(256), 0, s, dots, zz, ee, ids, rows, n_e);
+    hipLaunchKernelGGL(vq_argmin_kernel, dim3((int)((rows + 3) / 4)), dim3(256), 0, s, dots, zz, ee, ids, rows, n_e, status_current());
     LAUNCH_CHECK();
 }
 

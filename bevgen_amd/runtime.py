@@ -143,7 +143,7 @@ class Context:
             self.lib.bevgen_destroy(self._h)
             self._h = None
             if pending:
-                raise _lib.BevgenError(_lib.ERR_NUMERIC if pending & 28 else -4, f"context closed with device status word {pending} pending: results of its last calls were invalid "
+                raise _lib.BevgenError(_lib.ERR_NUMERIC if pending & 60 else -4, f"context closed with device status word {pending} pending: results of its last calls were invalid "
                                        "(include/bevgen_hip.h BEVGEN_STATUS_*)")
 
     def __del__(self):
@@ -609,3 +609,52 @@ class Context:
         self._check(self.lib.bevgen_op_range_split(self._h, _ptr(x), n, hw, Cc, _ptr(planes), _ptr(e), self._s()))
         self._done(check)
         return planes, e
+
+    # building blocks of the stage-1 VQGAN (vqdec.cpp): NHWC activations, convolution weights as the checkpoint stores them ([Cout, Cin, kh, kw])
+    def op_conv3x3_down(self, x_nhwc, w_oihw, bias=None):
+        """The encoder's Downsample: F.pad(x, (0, 1, 0, 1)) + 3x3 convolution, stride 2, padding 0 -> [n, H / 2, W / 2, Cout]."""
+        n, H, W, Cin = x_nhwc.shape
+        Cout = w_oihw.shape[0]
+        y = torch.empty((n, H // 2, W // 2, Cout), dtype=torch.float32, device=self.device)
+        self._check(self.lib.bevgen_op_conv3x3_down(self._h, _ptr(x_nhwc), _ptr(w_oihw), _ptr(bias), _ptr(y), n, H, W, Cin, Cout, self._s()))
+        return y
+
+    def op_vq_attn_block(self, x_nhwc, norm_w, norm_b, wq, bq, wk, bk, wv, bv, wp, bp):
+        """AttnBlock.forward: x + proj_out(softmax(q k^T C^-0.5) v) over the h w pixels of each image; the four weights are [C, C] (1x1 convolutions)."""
+        n, h, w, Cc = x_nhwc.shape
+        y = torch.empty_like(x_nhwc)
+        self._check(self.lib.bevgen_op_vq_attn_block(self._h, _ptr(x_nhwc), _ptr(norm_w), _ptr(norm_b), _ptr(wq), _ptr(bq), _ptr(wk), _ptr(bk), _ptr(wv), _ptr(bv), _ptr(wp),
+                                                     _ptr(bp), _ptr(y), n, h, w, Cc, self._s()))
+        return y
+
+    def op_vq_out_tail(self, x_nhwc, norm_w, norm_b, w_oihw, bias, mode="raw", mean=None, std=None, fused=True):
+        """The decoder's tail conv_out(swish(norm_out(x))) -> NCHW [n, 3, H, W]: mode 'raw' fp32, 'denorm' (x std + mean, clamped to [0, 1]) or 'u8' (round(255 x) of that);
+        fused=False: the three-kernel form."""
+        n, H, W, Cc = x_nhwc.shape
+        out_mode = {"raw": _lib.VQ_OUT_RAW, "denorm": _lib.VQ_OUT_DENORM, "u8": _lib.VQ_OUT_U8}[mode]
+        out = torch.empty((n, 3, H, W), dtype=torch.uint8 if mode == "u8" else torch.float32, device=self.device)
+        self._check(self.lib.bevgen_op_vq_out_tail(self._h, _ptr(x_nhwc), _ptr(norm_w), _ptr(norm_b), _ptr(w_oihw), _ptr(bias), _ptr(mean), _ptr(std), out_mode, int(not fused),
+                                                   _ptr(out), n, H, W, Cc, self._s()))
+        return out
+
+    def op_vq_quantize(self, z, codebook, want_norms=False):
+        """ids [rows] = argmin_j |z - e_j|^2 as the quantizer forms it ((|z|^2 + |e_j|^2) - 2 z.e_j, lowest index on ties); want_norms: also (|z|^2 [rows], |e|^2 [n_e])."""
+        rows, D = z.shape
+        n_e = codebook.shape[0]
+        ids = torch.empty((rows,), dtype=torch.int64, device=self.device)
+        zz = torch.empty((rows,), dtype=torch.float32, device=self.device) if want_norms else None
+        ee = torch.empty((n_e,), dtype=torch.float32, device=self.device) if want_norms else None
+        self._check(self.lib.bevgen_op_vq_quantize(self._h, _ptr(z), _ptr(codebook), _ptr(ids), _ptr(zz), _ptr(ee), rows, n_e, D, self._s()))
+        return (ids, zz, ee) if want_norms else ids
+
+    def op_conv3x3_gn_stats(self, x_nhwc, w_oihw, bias, range_route=False):
+        """precision='f16x3': the LDS-DMA 3x3 convolution whose epilogue leaves the GroupNorm partial sums of its output -> (y [n, H, W, Cout], partials
+        [n H W / 32, Cout / 4, 2], stats [n, 32, 2] = (mean, rstd)); range_route: the bias + statistics pass of the range-safe mode (exponent 0) instead of the epilogue."""
+        n, H, W, Cin = x_nhwc.shape
+        Cout = w_oihw.shape[0]
+        y = torch.empty((n, H, W, Cout), dtype=torch.float32, device=self.device)
+        part = torch.zeros((max(n * H * W // 32, 1), max(Cout // 4, 1), 2), dtype=torch.float32, device=self.device)
+        stats = torch.zeros((n, 32, 2), dtype=torch.float32, device=self.device)
+        self._check(self.lib.bevgen_op_conv3x3_gn_stats(self._h, _ptr(x_nhwc), _ptr(w_oihw), _ptr(bias), int(range_route), _ptr(y), _ptr(part), _ptr(stats), n, H, W, Cin, Cout,
+                                                        self._s()))
+        return y, part, stats

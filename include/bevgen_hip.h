@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define BEVGEN_ABI_VERSION 8   /* 8: bevgen_cfg.vq_range (taken out of reserved[]: the struct size is unchanged), bevgen_vq_range_exponents, bevgen_op_range_split.  7: operator entries of the token samplers (bevgen_op_remask, _maskgit_pick, _critic_scores, _ar_pick, _ar_score_rows, _mean_fixed_order).  6: device status word (bevgen_synchronize, bevgen_status, BEVGEN_ERR_NUMERIC, BEVGEN_STATUS_*).  5: bevgen_op_mlp_fused; a context without max_batch <= 4 packs the split decode layer lazily (see Conventions).  4: 4: BEVGEN_PROFILE_KINDS 5 -> 6 (bevgen_profile_end writes 18 doubles), bevgen_cfg.decode_chains, decode_path values 2 / 3 */
+#define BEVGEN_ABI_VERSION 9   /* 9: operator entries of the VQGAN building blocks (bevgen_op_conv3x3_down, _vq_attn_block, _vq_out_tail, _vq_quantize, _conv3x3_gn_stats), BEVGEN_STATUS_NONFINITE_LATENTS.  8: bevgen_cfg.vq_range (taken out of reserved[]: the struct size is unchanged), bevgen_vq_range_exponents, bevgen_op_range_split.  7: operator entries of the token samplers (bevgen_op_remask, _maskgit_pick, _critic_scores, _ar_pick, _ar_score_rows, _mean_fixed_order).  6: device status word (bevgen_synchronize, bevgen_status, BEVGEN_ERR_NUMERIC, BEVGEN_STATUS_*).  5: bevgen_op_mlp_fused; a context without max_batch <= 4 packs the split decode layer lazily (see Conventions).  4: 4: BEVGEN_PROFILE_KINDS 5 -> 6 (bevgen_profile_end writes 18 doubles), bevgen_cfg.decode_chains, decode_path values 2 / 3 */
 
 enum { BEVGEN_ROUTE_MASKGIT = 0, BEVGEN_ROUTE_AR = 1 };
 /* FP32  : every product and accumulation in exact fp32 on the matrix cores (v_mfma_f32_32x32x2_f32) - bit-exact greedy tokens vs the CPU reference.
@@ -58,7 +58,7 @@ enum {
  *   - in bevgen_synchronize (after waiting for the stream: the call a caller makes before it trusts / copies the results),
  *   - at the entry of EVERY later entry point on the context (no synchronisation: an error raised by an earlier asynchronous call is reported by the next call at the latest),
  *   - in bevgen_finalize (weights outside the f16 range of the chosen precision) and, as a message on stderr, in bevgen_destroy.
- * A raised word is returned as BEVGEN_ERR_NUMERIC (bits 4, 8, 16) or BEVGEN_ERR_INTERNAL (bits 1, 2) and then cleared.
+ * A raised word is returned as BEVGEN_ERR_NUMERIC (bits 4, 8, 16, 32) or BEVGEN_ERR_INTERNAL (bits 1, 2) and then cleared.
  * Policy for precision = F16X3 / fp16 storage modes: an operand whose f16 image would be inf / NaN (|v| >= 65520) is an ERROR, not rescaled - the split keeps fp32-class
  * mantissas but f16's exponent range, where the reference's bf16 / fp32 arithmetic has 8 exponent bits; such a checkpoint must run with BEVGEN_PRECISION_FP32.
  * One opt-in exception, stage-1 DECODE only: with bevgen_cfg.vq_range = 1 the un-normalised activation tensors of the decoder that become f16 operands (in front of the
@@ -70,7 +70,9 @@ enum {
     BEVGEN_STATUS_MLP_PLACEMENT = 2,      /* ...: a workgroup was not placed on the XCD its index implies */
     BEVGEN_STATUS_NONFINITE_LOGITS = 4,   /* a sampler read a NaN / inf logit or critic score */
     BEVGEN_STATUS_F16_RANGE = 8,          /* a value written as an f16 operand (hi / lo planes, fp16 KV cache, fp16 decode activations, fp16 weights) was NaN or |v| >= 65520 */
-    BEVGEN_STATUS_NONFINITE_PIXELS = 16   /* the VQGAN decoder produced a NaN / inf pixel */
+    BEVGEN_STATUS_NONFINITE_PIXELS = 16,  /* the VQGAN decoder produced a NaN / inf pixel */
+    BEVGEN_STATUS_NONFINITE_LATENTS = 32  /* the VQGAN quantizer met a latent row without a finite distance to any codebook entry (NaN / inf in the image or an overflow in the
+                                             encoder): that row's token id is written as 0 */
 };
 
 /* Sizes of the stage-2 transformer (mirror of GPTConfig, modules/transformer/mingpt_sparse.py:26-102) and of the
@@ -358,6 +360,31 @@ int bevgen_op_groupnorm(bevgen_ctx* ctx, const float* d_x_nhwc, const float* d_g
 /* The range-safe operand preparation on its own (vq_range = 1): d_x [n, hw, C] fp32 (C % 32 == 0) -> d_exp[0] = e (the rule at bevgen_cfg.vq_range) and
  * d_planes = the interleaved (hi, lo) f16 plane image [n * hw][C / 32][2][32] of x 2^-e (x = (hi + lo 2^-11) 2^e).  NaN / inf in d_x raise BEVGEN_STATUS_F16_RANGE. */
 int bevgen_op_range_split(bevgen_ctx* ctx, const float* d_x, int n, int hw, int C, void* d_planes, int32_t* d_exp, void* stream);
+/* Building blocks of the stage-1 VQGAN at shapes of their own (vqdec.cpp; the model reaches them only through bevgen_vq_encode / bevgen_vq_decode).  Activations are NHWC fp32,
+ * convolution weights arrive as the checkpoint stores them ([Cout][Cin][kh][kw]) and are re-laid out (and, with precision = F16X3, split) inside the call.
+ * conv3x3_down: the encoder's Downsample, F.pad(x, (0,1,0,1)) + 3x3 convolution with stride 2 and padding 0: d_y [n, H/2, W/2, Cout]; H, W even, Cin % 32 == 0. */
+int bevgen_op_conv3x3_down(bevgen_ctx* ctx, const float* d_x_nhwc, const float* d_w_oihw, const float* d_bias /* or NULL */, float* d_y_nhwc, int n, int H, int W, int Cin,
+                           int Cout, void* stream);
+/* vq_attn_block: AttnBlock.forward (stage1/model.py:168-192): d_y = x + proj_out(softmax(q k^T C^-0.5) v) with q, k, v = 1x1 convolutions [C][C] of GroupNorm(x); C % 32 == 0;
+ * d_y must not alias d_x. */
+int bevgen_op_vq_attn_block(bevgen_ctx* ctx, const float* d_x_nhwc, const float* d_norm_w, const float* d_norm_b, const float* d_wq, const float* d_bq, const float* d_wk,
+                            const float* d_bk, const float* d_wv, const float* d_bv, const float* d_wp, const float* d_bp, float* d_y_nhwc, int n, int h, int w, int C, void* stream);
+/* vq_out_tail: the decoder's last operators, conv_out(swish(norm_out(x))) with d_w [3][C][3][3], then out_mode 0: raw fp32 NCHW [n, 3, H, W]; 1: x std + mean clamped to [0, 1];
+ * 2: round(255 x) of that as uint8 (d_out then points to uint8).  three_kernels = 0: the fused kernel; 1: GroupNorm-apply, implicit-GEMM convolution and layout kernel.
+ * A NaN / inf pixel raises BEVGEN_STATUS_NONFINITE_PIXELS. */
+int bevgen_op_vq_out_tail(bevgen_ctx* ctx, const float* d_x_nhwc, const float* d_norm_w, const float* d_norm_b, const float* d_w_oihw, const float* d_bias /* or NULL */,
+                          const float* d_mean /* [3], or NULL with out_mode 0 */, const float* d_std, int out_mode, int three_kernels, void* d_out, int n, int H, int W, int C,
+                          void* stream);
+/* vq_quantize: VectorQuantizer2.forward's arg-min, d_ids[r] = argmin_j (|z_r|^2 + |e_j|^2) - 2 z_r . e_j with the lowest index on ties; d_z [rows, D], d_codebook [n_e, D],
+ * D % 32 == 0; d_zz [rows] / d_ee [n_e] (or NULL) receive the squared norms.  A row without a finite distance gets id 0 and raises BEVGEN_STATUS_NONFINITE_LATENTS. */
+int bevgen_op_vq_quantize(bevgen_ctx* ctx, const float* d_z, const float* d_codebook, int64_t* d_ids, float* d_zz /* or NULL */, float* d_ee /* or NULL */, long rows, int n_e,
+                          int D, void* stream);
+/* conv3x3_gn_stats (precision = F16X3 contexts): the LDS-DMA 3x3 convolution (stride 1, padding 1) on (hi, lo) planes of d_x whose epilogue leaves the GroupNorm(32) partial sums
+ * of its output, d_part [n H W / 32][Cout / 4][2] fp32 (sum, sum of squares), and the statistics made of them, d_stats [n, 32, 2] = (mean, rstd) at eps 1e-6.
+ * range_route != 0: the form of the range-safe mode instead (convolution without the bias, then the bias + statistics pass at exponent 0).  H W % 256 == 0 and
+ * Cout % 128 == 0, else BEVGEN_ERR_INVALID. */
+int bevgen_op_conv3x3_gn_stats(bevgen_ctx* ctx, const float* d_x_nhwc, const float* d_w_oihw, const float* d_bias, int range_route, float* d_y_nhwc, float* d_part, float* d_stats,
+                               int n, int H, int W, int Cin, int Cout, void* stream);
 
 /* Per-kernel timing support for bench.py's roofline leg: number of workgroup splits the decode-attention kernel uses. */
 int bevgen_decode_attention_splits(int B, int H, int n);
