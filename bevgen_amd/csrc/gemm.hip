@@ -16,6 +16,7 @@
 // inside one tap.
 #include "common.h"
 #include "kernels.h"
+#include "gemm_plan.h"   // conv_defaults
 #include "profiler.h"
 #include <unordered_map>
 
@@ -178,17 +179,6 @@ __global__ __launch_bounds__(256, 2) void gemm_f32_kernel(GemmArgs g) {
                 C[(long)m * g.ldc + n] = v;
             }
         }
-}
-
-static GemmArgs conv_defaults(const GemmArgs& g0) {
-    GemmArgs g = g0;
-    if (g.mode == MODE_CONV3) {
-        if (g.conv_stride == 0) g.conv_stride = 1;
-        if (g.conv_pad < 0) g.conv_pad = 1;
-        if (g.conv_hin == 0) g.conv_hin = g.conv_up ? g.conv_h / 2 : g.conv_h;
-        if (g.conv_win == 0) g.conv_win = g.conv_up ? g.conv_w / 2 : g.conv_w;
-    }
-    return g;
 }
 
 // per calling thread (like the profiler hook): set by every entry point for the context it runs, so two contexts driven from two host threads do not see each other's table

@@ -1207,240 +1207,80 @@ namespace bevgen {
 #endif
 size_t gemm_sk_ws_bytes() { return 1024 * sizeof(float) + (size_t)256 * (8 * 4 * 16 * 64) * sizeof(float); }   // 1024 flag words + 256 workgroup slots of 128 KiB
 
-// Does the stream-K form pay?  T tiles of 256 x 128 cost ceil(T / 256) rounds of the chip; the form removes the empty part of the last round (and the second launch of a
-// row-split problem) at the price of one partial-tile exchange per workgroup (~3 us) - worth it when at least 15 % of the rounds would be empty and every workgroup still
-// gets a few k-tiles.  One scene (rows 1536): q|k|v 144 tiles (44 % empty), the 1024-wide projections 48 (81 %), the up-projection 258 (50 % of two rounds); two scenes:
-// 288 / 96 / 516; sixteen scenes: 2304 = 9 rounds exactly, 768 = 3, 4128 = 16.1 (its row-split form stays).
-bool gemm_sk_pays(long rows, int N, int K) {
-    static const int sk_env = getenv("BEVGEN_GEMM_SK") ? atoi(getenv("BEVGEN_GEMM_SK")) : 0;   // (default off: see launch_gemm_split_glds)
-    if (!sk_env) return false;
-    const long T = (long)cdiv(rows, 256) * cdiv(N, GBN), rounds = (T + 255) / 256;
-    const double empty = 1.0 - (double)T / (double)(rounds * 256);
-    // ... and only while a tile is shared by two or three workgroups (T >= 128): with fewer tiles every tile's last workgroup merges five or more 128 KiB partials while
-    // the others idle - measured slower than the 64-row blocks of the data-parallel launch at every such shape (profiles/r06_ab_gemm_sk_ops.txt)
-    (void)K;
-    return T >= 128 && empty >= 0.15;
+}  // namespace bevgen
+// ---- host side.  WHICH instantiation runs a problem, on which grid and with how much LDS is decided in gemm_plan.h (a pure function, tested on the CPU); below are the
+// switches it takes, the table that maps its variant tuples to the kernels above, and the driver that executes a plan.
+#include "gemm_plan.h"
+namespace bevgen {
+static_assert(kGldsBN == GBN && kGldsBK == GBK, "gemm_plan.h plans for the block tile of this file's kernels");
+
+// The launcher's A/B switches: read once per process (the tests that pin one run in subprocesses).  Meaning and measurements: with each rule in gemm_plan.h; table in DESIGN.md.
+static const GldsSwitches& glds_switches() {
+    static const GldsSwitches sw = [] {
+        const auto env = [](const char* name, int dflt) { const char* v = getenv(name); return v ? atoi(v) : dflt; };
+        GldsSwitches s;
+        s.sk = env("BEVGEN_GEMM_SK", 0);                  // stream-K form: 0 never (unless forced per call), 1 where gemm_sk_pays, 2 whenever a workspace is given
+        s.rpf = env("BEVGEN_GEMM_RPF", 1);                // residual prefetch in the k loop's tail (0: off, for A/B runs; profiles/r06_ab_gemm_rpf.txt)
+        s.rme = env("BEVGEN_GEMM_RME", 1);                // row-major store form of the plain epilogue (0: accumulator-layout stores, A/B runs)
+        s.band = env("BEVGEN_GEMM_BAND", 0);              // > 0: band height of the XCD-aware tile order (default 4)
+        s.wm = env("BEVGEN_GEMM_WM", 0);                  // 2 | 4: pins the block rows (128 | 256) for A/B runs
+        s.top_wm = env("BEVGEN_GEMM_TOPWM", 4);           // != 4: a caller's (or the row split's) pin of 256-row blocks is ignored
+        s.rowsplit = env("BEVGEN_GEMM_ROWSPLIT", 1);      // 0: no row split of a problem whose last round of tiles would be nearly empty
+        s.bot_wm = env("BEVGEN_ROWSPLIT_BOT_WM", 0);      // 4: the rest of a row-split problem keeps the caller's pin of 256-row blocks
+        s.stages = env("BEVGEN_GEMM_STAGES", 0);          // 2 | 8 | 16: pins the small-problem block shape (four waves two stages | eight waves four stages | 64-row blocks)
+        s.conv_thin = env("BEVGEN_CONV_THIN", 1);         // 0: convolutions never take the eight-wave small-problem block
+        s.half8 = env("BEVGEN_GEMM_HALF8", 1);            // 0: the 64-row block keeps four waves of 32x64 patches with the plain epilogue too
+        s.conv_fast = env("BEVGEN_CONV_FAST", 1);         // 0: stride-1 / pad-1 convolutions keep the general variant (MODE_CONV3)
+        return s;
+    }();
+    return sw;
 }
 
+bool gemm_sk_pays(long rows, int N, int K) {
+    (void)K;
+    return glds_sk_pays(glds_switches(), rows, N);
+}
+
+// gemm_plan.h's variant list as kernels: entry i runs kGldsVariants[i]
+typedef void (*GldsKernel)(GemmArgs);
+template <int MODE, int WM, int S, bool W16, bool KS, int TI, int TJ, bool SK>
+constexpr GldsKernel glds_kernel() {
+    if constexpr (SK) return gemm_split_glds_sk_kernel<WM, S, W16>;
+    else return gemm_split_glds_kernel<MODE, WM, S, W16, KS, TI, TJ>;
+}
+#define BG_GLDS_KERNEL(...) glds_kernel<__VA_ARGS__>(),
+static const GldsKernel kGldsKernels[kGldsVariantCount] = {BG_GLDS_VARIANTS(BG_GLDS_KERNEL)};
+#undef BG_GLDS_KERNEL
+
 void launch_gemm_split_glds(const GemmArgs& g_in, hipStream_t stream) {
-    GemmArgs g = g_in;
-    if (g.mode == MODE_CONV3) {
-        if (g.conv_stride == 0) g.conv_stride = 1;
-        if (g.conv_pad < 0) g.conv_pad = 1;
-        if (g.conv_hin == 0) g.conv_hin = g.conv_up ? g.conv_h / 2 : g.conv_h;
-        if (g.conv_win == 0) g.conv_win = g.conv_up ? g.conv_w / 2 : g.conv_w;
-        BG_REQUIRE(g.conv_cin % GBK == 0 && g.K == 9 * g.conv_cin, "conv3x3: Cin=%d must be a multiple of 32", g.conv_cin);
-        const long a_bytes = (long)(g.M / (g.conv_h * g.conv_w)) * g.conv_hin * g.conv_win * g.conv_cin * 4;
-        BG_REQUIRE(a_bytes < 0xFFFFFF00L, "conv3x3 (LDS-DMA): the activation planes (%ld bytes) must stay below 4 GiB per launch", a_bytes);
-        g.a_bytes = (int)(unsigned)a_bytes;
-    }
-    BG_REQUIRE(g.A_hi && g.A_lo && g.B_hi && g.B_lo, "gemm_split_glds: both operands must be pre-split");
-    g.status = status_current();
-    static const int rpf_env = getenv("BEVGEN_GEMM_RPF") ? atoi(getenv("BEVGEN_GEMM_RPF")) : 1;   // residual prefetch in the k loop's tail (0: off, for A/B runs; profiles/r06_ab_gemm_rpf.txt)
-    static const int rme_env = getenv("BEVGEN_GEMM_RME") ? atoi(getenv("BEVGEN_GEMM_RME")) : 1;   // row-major store form of the plain epilogue (0: accumulator-layout stores, A/B runs)
-    g.row_major_epi = rme_env != 0;
-    g.r_prefetch = rpf_env && g.mode == MODE_PLAIN && g.R && (g.ldr & 3) == 0 && (reinterpret_cast<uintptr_t>(g.R) & 15) == 0 && (long)g.M * g.ldr * 4 < 0x7FFFFFFFL && g.N >= 64;
-    if (g.gn_part)
-        BG_REQUIRE(g.mode == MODE_CONV3 && g.epi == 0 && g.ksplit <= 1 && g.M % 256 == 0 && g.m_base == 0 && g.N % GBN == 0 && g.ldc == g.N && (g.ldc & 3) == 0 &&
-                       (!g.R || (g.ldr & 3) == 0) && (reinterpret_cast<uintptr_t>(g.C) & 15) == 0 && (!g.R || (reinterpret_cast<uintptr_t>(g.R) & 15) == 0) && !g.bias_m,
-                   "gemm_split_glds: GroupNorm partials need whole 256 x 128 tiles of a convolution with the plain epilogue (M=%d N=%d)", g.M, g.N);
-    BG_REQUIRE(g.K % GBK == 0 && g.lda % GBK == 0 && g.ldb % GBK == 0, "gemm_split_glds: K, lda, ldb must be multiples of 32 (K=%d lda=%d ldb=%d)", g.K, g.lda, g.ldb);
-    BG_REQUIRE(g.batch == 1, "gemm_split_glds: batched form not provided");
-    if (g.epi == EPI_MUSE_KV)
-        BG_REQUIRE(g.mode == MODE_PLAIN && g.N == 2 * g.epi_heads * 64 && g.epi_hi && g.epi_lo && g.epi_hi2 && g.epi_lo2 && g.epi_aux && g.epi_scale && g.epi_rows > 0 &&
-                       g.epi_ld >= g.epi_rows + 1 && !g.R && !g.bias_n && !g.bias_m && g.act == ACT_NONE && (g.no_row_split || g.M % g.epi_rows == 0),
-                   "gemm_split_glds: bad fused k/v-preparation arguments");
-    if (g.epi == EPI_GEGLU)
-        BG_REQUIRE(g.mode == MODE_PLAIN && g.N % GBN == 0 && (g.ldc % 4 == 0 && g.ldc >= g.N / 2) && !g.R && !g.bias_n && !g.bias_m && g.act == ACT_NONE,
-                   "gemm_split_glds: bad fused GEGLU arguments (N=%d ldc=%d)", g.N, g.ldc);
-    if (g.epi == EPI_MUSE_QKV)
-        BG_REQUIRE(g.mode == MODE_PLAIN && g.N == 3 * g.epi_heads * 64 && g.epi_hi && g.epi_lo && g.epi_hi2 && g.epi_lo2 && g.epi_aux && g.epi_scale && g.epi_qh && g.epi_ql &&
-                       g.epi_qscale && g.epi_rows > 0 && g.epi_ld >= g.epi_rows + 1 && !g.R && !g.bias_n && !g.bias_m && g.act == ACT_NONE &&
-                       (g.no_row_split || g.M % g.epi_rows == 0) && g.ksplit <= 1,
-                   "gemm_split_glds: bad fused q/k/v-preparation arguments");
-    if (g.epi == EPI_MUSE_Q)
-        BG_REQUIRE(g.mode == MODE_PLAIN && g.N % 64 == 0 && g.epi_hi && g.epi_lo && g.epi_scale && g.epi_rows > 0 && g.epi_heads * 64 == g.N && !g.R && !g.bias_n && !g.bias_m,
-                   "gemm_split_glds: bad fused q-preparation arguments");
-    if (g.ln_in_stats || g.ln_in_gsums)
-        BG_REQUIRE(g.mode == MODE_PLAIN && g.ln_in_cs && g.N % 4 == 0 && g.ksplit <= 1 && !(g.ln_in_stats && g.ln_in_gsums) &&
-                       (!g.ln_in_gsums || (g.ln_in_groups > 0 && g.ln_in_count > 0 && g.ln_rows >= g.M)),
-                   "gemm_split_glds: bad folded-LayerNorm consumer arguments (N=%d ksplit=%d groups=%d)", g.N, g.ksplit, g.ln_in_groups);
-    if (g.ln_out_planes)
-        BG_REQUIRE(g.mode == MODE_PLAIN && g.ln_out_stats && g.ln_rows >= g.M && g.ln_out_ld % 32 == 0 && g.ksplit <= 1 &&
-                       (g.epi == EPI_GEGLU ? g.ln_out_ld * 2 >= g.N : (g.epi == 0 && g.ln_out_ld >= g.N && g.N % 32 == 0 && (g.ldc & 3) == 0 && (!g.R || (g.ldr & 3) == 0) &&
-                                                                        (reinterpret_cast<uintptr_t>(g.C) & 15) == 0 && (!g.R || (reinterpret_cast<uintptr_t>(g.R) & 15) == 0))),
-                   "gemm_split_glds: bad folded-LayerNorm producer arguments (ld=%d N=%d epi=%d)", g.ln_out_ld, g.N, g.epi);
-    // ---- stream-K route (the caller provided a workspace: Route M's projections): problems whose 256 x 128 tiles would leave much of their last round of the chip empty
-    // DEFAULT OFF: measured slower than the launcher's other choices at every Route-M shape of one, two and four scenes (profiles/r06_ab_gemm_sk_ops.txt: +4 .. +27 us per
-    // projection; one scene 163.8 -> 168.5 ms with the routing rule below, 214 ms with every projection): a partial 256 x 128 tile is 128 KiB to publish and to read back,
-    // every segment refills the three-stage ring, and the workgroup that holds a tile's last k range merges while its peers idle - together more than the empty part of
-    // the last round they remove.  $BEVGEN_GEMM_SK=1 routes by gemm_sk_pays, 2 takes the form whenever a workspace is given (the operator tests force it per call)
-    static const int sk_env = getenv("BEVGEN_GEMM_SK") ? atoi(getenv("BEVGEN_GEMM_SK")) : 0;
-    if (g.sk_ws && (sk_env || g.sk_force) && g.mode == MODE_PLAIN && g.ksplit <= 1 && g.m_base == 0 && !g.no_row_split && !g.bias_m && !g.ln_in_gsums && xcd_placement_verified() &&
-        (sk_env == 2 || g.sk_force || gemm_sk_pays(g.M, g.N, g.K))) {
-        static std::atomic<int> cu_count[kMaxDevices];
-        static std::atomic<bool> sk_attr[kMaxDevices];
-        const int ds = device_slot();
-        int cus = cu_count[ds].load(std::memory_order_acquire);
-        if (cus == 0) {
-            int dev = 0;
-            HIP_CHECK(hipGetDevice(&dev));
-            HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-            cu_count[ds].store(cus, std::memory_order_release);
-        }
-        const size_t lds_sk = (size_t)3 * 384 * 2 * GBK * 2 + 4096;
-        if (!sk_attr[ds].load(std::memory_order_acquire)) {
-            HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_split_glds_sk_kernel<4, 3, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_sk));
-            HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_split_glds_sk_kernel<4, 3, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_sk));
-            sk_attr[ds].store(true, std::memory_order_release);
-        }
-        g.sk_tiles = cdiv(g.M, 256) * cdiv(g.N, GBN);
-        const long units = (long)g.sk_tiles * (g.K / GBK);
-        const int G = (int)std::max<long>(8, std::min<long>(std::min(cus, 256), units / 2)) & ~7;   // (a multiple of 8: whole tiles per XCD; >= two k-tiles per workgroup; 256 slots)
-        g.tile_band = 0;
-        ProfScope prof(PROF_GEMM_SMALL, 2.0 * g.M * (double)g.N * g.K, stream);
-        if (g.b_lo_zero) hipLaunchKernelGGL((gemm_split_glds_sk_kernel<4, 3, true>), dim3(G), dim3(512), lds_sk, stream, g);
-        else hipLaunchKernelGGL((gemm_split_glds_sk_kernel<4, 3, false>), dim3(G), dim3(512), lds_sk, stream, g);
-        LAUNCH_CHECK();
-        return;
-    }
-    g.tile_band = 4;   // band height of the XCD-aware tile order (measured optimum for 256 x 128 tiles)
-    static const int band_env = getenv("BEVGEN_GEMM_BAND") ? atoi(getenv("BEVGEN_GEMM_BAND")) : 0;   // A/B switch (tools/ab.sh m env BEVGEN_GEMM_BAND=2,4,8)
-    if (band_env > 0) g.tile_band = band_env;
-    static const int force_wm = getenv("BEVGEN_GEMM_WM") ? atoi(getenv("BEVGEN_GEMM_WM")) : 0;   // 2 | 4: pins the block rows (128 | 256) for A/B runs
-    // 256-row tiles (8 waves, 3 stages, one block per CU) unless the problem is too small to give every CU one of them; then 128-row tiles
-    // with 2 stages (64 KiB) so that two independent 4-wave blocks share a CU
-    const int rows = g.M - g.m_base;   // (g.M is the END row of this launch, g.m_base its first)
-    static const int top_wm_env = getenv("BEVGEN_GEMM_TOPWM") ? atoi(getenv("BEVGEN_GEMM_TOPWM")) : 4;
-    const int wm = (force_wm == 2 || force_wm == 4) ? force_wm : (g.force_wm == 4 && top_wm_env == 4) ? 4 : ((long)cdiv(rows, 256) * cdiv(g.N, GBN) >= 256 ? 4 : 2);
-    // Tile quantisation: T tiles of 256 x 128 on 256 CUs cost ceil(T / 256) rounds - the up-projection of sixteen scenes is 4128 tiles = 16.1 rounds and pays 17, of one
-    // scene 258 tiles and pays 2, a [12288, 1024] projection of the three-camera shape 384 tiles and pays 2.  When the last round would hold at most 128 tiles, the launch
-    // is cut at a row-tile boundary: the first part fills whole rounds, the rest (<= 128 tiles' worth of rows) runs as 128-row blocks, one short round of its own
-    // (about 0.45 of a full one).  Same kernels, same per-row arithmetic: results are bit-identical to the single launch.  $BEVGEN_GEMM_ROWSPLIT=0 turns it off (A/B runs)
-    static const int rowsplit_env = getenv("BEVGEN_GEMM_ROWSPLIT") ? atoi(getenv("BEVGEN_GEMM_ROWSPLIT")) : 1;
-    if (rowsplit_env && !g.no_row_split && wm == 4 && g.mode == MODE_PLAIN && g.ksplit <= 1) {
-        const long gx = cdiv(g.N, GBN), gy = cdiv(rows, 256), T = gx * gy;
-        const long full = T / 256;                       // whole rounds
-        const long gy_top = full * 256 / gx;             // row tiles that fit them
-        const long rest = (gy - gy_top) * gx;            // tiles left for the last round
-        if (T % 256 != 0 && full >= 1 && gy_top >= 1 && gy_top < gy && rest <= 128) {
-            GemmArgs top = g, bot = g;
-            top.no_row_split = bot.no_row_split = true;
-            top.force_wm = 4;                            // the part that was sized to fill whole rounds of 256-row blocks keeps them
-            top.M = g.m_base + (int)gy_top * 256;        // end row of the first part
-            bot.m_base = top.M;
-            // ... and the rest picks its block by its OWN size even when the caller pinned 256-row blocks for the whole problem (q | k | v of two scenes: 288 tiles = 240 +
-            // 48; the 48 as 256-row blocks kept 48 CUs busy for 33.5 us, as 192 blocks of 64 rows ~18 us; profiles/r06_ab_rowsplit_bot.txt).  $BEVGEN_ROWSPLIT_BOT_WM=4: as before
-            static const int bot_wm_env = getenv("BEVGEN_ROWSPLIT_BOT_WM") ? atoi(getenv("BEVGEN_ROWSPLIT_BOT_WM")) : 0;
-            if (bot_wm_env != 4) bot.force_wm = 0;
-            // (the rest on a side stream BESIDE a first part that leaves CUs idle - one scene: 215 blocks on 256 CUs - was measured and rejected: the fork / join events cost
-            // more than the overlap buys, one scene 162.9 -> 173.4 ms, sixteen scenes 10.34 -> 10.30 scenes/s; profiles/r05_ab_rowsplit_side_*.txt)
-            launch_gemm_split_glds(top, stream);
-            launch_gemm_split_glds(bot, stream);
-            return;
-        }
-    }
-    // ... unless even those leave CUs without a second block (a batch of one or two scenes): then nothing shares the CU, and the block becomes eight waves with
-    // 32x64 patches on a four-stage ring (three k-tiles in flight instead of one; the kernel's TI note).  Measured on the Route M step (tools/ab_env_m.sh): one scene
-    // 236 -> 199 ms, two scenes 303 -> 270 ms; at three and four scenes (288 / 384 blocks: two four-wave blocks per CU) the eight-wave block is 2-3 % slower.
-    // $BEVGEN_GEMM_STAGES = 2 | 8 | 16 pins the small-problem shape for A/B runs and tests (2: four waves, two stages; 8: eight waves, four stages; 16: 64-row blocks)
-    static const int stages_env = getenv("BEVGEN_GEMM_STAGES") ? atoi(getenv("BEVGEN_GEMM_STAGES")) : 0;
-    static const int conv_thin_env = getenv("BEVGEN_CONV_THIN") ? atoi(getenv("BEVGEN_CONV_THIN")) : 1;
-    const bool lone = (g.mode == MODE_PLAIN || conv_thin_env) && (long)cdiv(g.N, GBN) * cdiv(rows, 128) * g.ksplit <= 256;
-    // ... and when even the 128-row blocks cover at most half of the CUs (a [1536, 1024] projection: 96), 64-row blocks of four waves (32x64 patches, four stages): twice
-    // the blocks, a shorter k-tile each (16 = that shape): 21.4 -> 18.4 us at K = 1024, one-scene step 195.7 -> 187.4 ms on the same box (profiles/r03_ab_b1_half_rows.txt)
-    const bool half_rows = lone && g.mode == MODE_PLAIN && g.ksplit == 1 && (long)cdiv(g.N, GBN) * cdiv(rows, 128) <= 128;
-    int shape = lone ? (half_rows ? 16 : 8) : 2;
-    if (g.mode == MODE_PLAIN && (stages_env == 2 || stages_env == 8 || (stages_env == 16 && g.ksplit == 1))) shape = stages_env;
-    const int stages = wm == 4 ? 3 : (shape == 2 ? 2 : 4);
-    const bool thin = wm == 2 && shape == 8, half = wm == 2 && shape == 16;
-    // ... and with the plain epilogue (bias / activation / residual: the fused ones need 64-column wave patches) the 64-row block runs on eight waves of 32x32 patches
-    static const int half8_env = getenv("BEVGEN_GEMM_HALF8") ? atoi(getenv("BEVGEN_GEMM_HALF8")) : 1;
-    const bool half8 = half && half8_env && g.epi == 0;
-    const int tbm = half ? 64 : wm * 64;
-    BG_REQUIRE(g.ksplit >= 1 && (g.ksplit == 1 || (g.kpart && g.epi == 0 && g.mode == MODE_PLAIN && wm == 2 && !half && g.K / GBK >= 2 * g.ksplit && !g.bias_m)),
-               "gemm_split_glds: split-K needs a workspace, the plain epilogue, the 128-row tile and >= 2 k-tiles per slice (ksplit=%d K=%d)", g.ksplit, g.K);
-    dim3 grid(cdiv(g.N, GBN), cdiv(rows, tbm), g.ksplit);
-    const size_t lds = (size_t)stages * (tbm + GBN) * 2 * GBK * sizeof(_Float16) + ((g.ln_in_stats || g.ln_in_gsums || g.r_prefetch) ? 4096 : 0) + ((g.r_prefetch || g.ln_in_gsums) ? 2048 : 0) +
-                       (g.ln_in_gsums ? 8192 : 0);   // LayerNorm (mean, rstd) slots | prefetch sink | the block merge's fp64 partial sums   // (+ the folded LayerNorm's per-row (mean, rstd) slots)
+    static std::atomic<int> cu_count[kMaxDevices];
     static std::atomic<bool> attr_set[kMaxDevices];
     const int dslot = device_slot();
-    if (!attr_set[dslot].load(std::memory_order_acquire)) {
-#define BG_SET(K, BYTES) HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&K), hipFuncAttributeMaxDynamicSharedMemorySize, BYTES))
-        BG_SET((gemm_split_glds_kernel<MODE_PLAIN, 2, 2>), 2 * 256 * 2 * GBK * 2 + 14336);
-        BG_SET((gemm_split_glds_kernel<MODE_CONV3, 2, 2>), 2 * 256 * 2 * GBK * 2);
-        BG_SET((gemm_split_glds_kernel<MODE_CONV3S, 2, 2>), 2 * 256 * 2 * GBK * 2);
-        BG_SET((gemm_split_glds_kernel<MODE_PLAIN, 4, 3>), 3 * 384 * 2 * GBK * 2 + 14336);
-        BG_SET((gemm_split_glds_kernel<MODE_CONV3, 4, 3>), 3 * 384 * 2 * GBK * 2);
-        BG_SET((gemm_split_glds_kernel<MODE_CONV3S, 4, 3>), 3 * 384 * 2 * GBK * 2);
-        BG_SET((gemm_split_glds_kernel<MODE_PLAIN, 2, 2, true>), 2 * 256 * 2 * GBK * 2 + 14336);
-        BG_SET((gemm_split_glds_kernel<MODE_CONV3, 2, 2, true>), 2 * 256 * 2 * GBK * 2);
-        BG_SET((gemm_split_glds_kernel<MODE_CONV3S, 2, 2, true>), 2 * 256 * 2 * GBK * 2);
-        BG_SET((gemm_split_glds_kernel<MODE_PLAIN, 4, 3, true>), 3 * 384 * 2 * GBK * 2 + 14336);
-        BG_SET((gemm_split_glds_kernel<MODE_CONV3, 4, 3, true>), 3 * 384 * 2 * GBK * 2);
-        BG_SET((gemm_split_glds_kernel<MODE_CONV3S, 4, 3, true>), 3 * 384 * 2 * GBK * 2);
-        BG_SET((gemm_split_glds_kernel<MODE_PLAIN, 2, 2, false, true>), 2 * 256 * 2 * GBK * 2 + 14336);
-        BG_SET((gemm_split_glds_kernel<MODE_PLAIN, 2, 2, true, true>), 2 * 256 * 2 * GBK * 2 + 14336);
-        BG_SET((gemm_split_glds_kernel<MODE_PLAIN, 2, 4, false, false, 1>), 4 * 256 * 2 * GBK * 2 + 14336);
-        BG_SET((gemm_split_glds_kernel<MODE_PLAIN, 2, 4, true, false, 1>), 4 * 256 * 2 * GBK * 2 + 14336);
-        BG_SET((gemm_split_glds_kernel<MODE_PLAIN, 2, 4, false, true, 1>), 4 * 256 * 2 * GBK * 2 + 14336);
-        BG_SET((gemm_split_glds_kernel<MODE_PLAIN, 2, 4, true, true, 1>), 4 * 256 * 2 * GBK * 2 + 14336);
-        BG_SET((gemm_split_glds_kernel<MODE_CONV3, 2, 4, false, false, 1>), 4 * 256 * 2 * GBK * 2);
-        BG_SET((gemm_split_glds_kernel<MODE_CONV3S, 2, 4, false, false, 1>), 4 * 256 * 2 * GBK * 2);
-        BG_SET((gemm_split_glds_kernel<MODE_CONV3, 2, 4, true, false, 1>), 4 * 256 * 2 * GBK * 2);
-        BG_SET((gemm_split_glds_kernel<MODE_CONV3S, 2, 4, true, false, 1>), 4 * 256 * 2 * GBK * 2);
-        BG_SET((gemm_split_glds_kernel<MODE_PLAIN, 1, 4, false, false, 1>), 4 * 192 * 2 * GBK * 2 + 14336);
-        BG_SET((gemm_split_glds_kernel<MODE_PLAIN, 1, 4, true, false, 1>), 4 * 192 * 2 * GBK * 2 + 14336);
-        BG_SET((gemm_split_glds_kernel<MODE_PLAIN, 1, 4, false, false, 1, 1>), 4 * 192 * 2 * GBK * 2 + 14336);
-        BG_SET((gemm_split_glds_kernel<MODE_PLAIN, 1, 4, true, false, 1, 1>), 4 * 192 * 2 * GBK * 2 + 14336);
-#undef BG_SET
+    int cus = g_in.sk_ws ? cu_count[dslot].load(std::memory_order_acquire) : 256;   // (only the stream-K grid depends on it, and that form needs a workspace)
+    if (cus == 0) {
+        int dev = 0;
+        HIP_CHECK(hipGetDevice(&dev));
+        HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
+        cu_count[dslot].store(cus, std::memory_order_release);
+    }
+    GldsPlan plan = plan_gemm_split_glds(g_in, glds_switches(), cus, &xcd_placement_verified);
+    if (!attr_set[dslot].load(std::memory_order_acquire)) {   // the > 64 KB dynamic-LDS opt-in of every variant, once per device
+        for (int i = 0; i < kGldsVariantCount; ++i)
+            HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kGldsKernels[i]), hipFuncAttributeMaxDynamicSharedMemorySize, (int)glds_lds_max(kGldsVariants[i])));
         attr_set[dslot].store(true, std::memory_order_release);
     }
-    ProfScope prof(g.mode == MODE_CONV3 ? PROF_CONV3 : (wm == 4 ? PROF_GEMM : PROF_GEMM_SMALL), 2.0 * rows * (double)g.N * g.K, stream);
-    const bool conv = g.mode == MODE_CONV3;
-    // stride 1, padding 1, no fused upsample: the variant with wave-uniform tap displacements (MODE_CONV3S; $BEVGEN_CONV_FAST=0 keeps the general one, for A/B runs)
-    static const int conv_fast_env = getenv("BEVGEN_CONV_FAST") ? atoi(getenv("BEVGEN_CONV_FAST")) : 1;
-    const bool convs = conv && conv_fast_env && !g.conv_general && !g.conv_up && g.conv_stride == 1 && g.conv_pad == 1 && g.conv_hin == g.conv_h && g.conv_win == g.conv_w;
-#define BG_LAUNCH(MODE_, WM_, S_, THREADS)                                                                                           \
-    do {                                                                                                                             \
-        if (g.b_lo_zero) hipLaunchKernelGGL((gemm_split_glds_kernel<MODE_, WM_, S_, true>), grid, dim3(THREADS), lds, stream, g);    \
-        else hipLaunchKernelGGL((gemm_split_glds_kernel<MODE_, WM_, S_, false>), grid, dim3(THREADS), lds, stream, g);               \
-    } while (0)
-    if (half8) {
-        if (g.b_lo_zero) hipLaunchKernelGGL((gemm_split_glds_kernel<MODE_PLAIN, 1, 4, true, false, 1, 1>), grid, dim3(512), lds, stream, g);
-        else hipLaunchKernelGGL((gemm_split_glds_kernel<MODE_PLAIN, 1, 4, false, false, 1, 1>), grid, dim3(512), lds, stream, g);
-    } else if (half) {
-        if (g.b_lo_zero) hipLaunchKernelGGL((gemm_split_glds_kernel<MODE_PLAIN, 1, 4, true, false, 1>), grid, dim3(256), lds, stream, g);
-        else hipLaunchKernelGGL((gemm_split_glds_kernel<MODE_PLAIN, 1, 4, false, false, 1>), grid, dim3(256), lds, stream, g);
-    } else if (thin && convs) {
-        if (g.b_lo_zero) hipLaunchKernelGGL((gemm_split_glds_kernel<MODE_CONV3S, 2, 4, true, false, 1>), grid, dim3(512), lds, stream, g);
-        else hipLaunchKernelGGL((gemm_split_glds_kernel<MODE_CONV3S, 2, 4, false, false, 1>), grid, dim3(512), lds, stream, g);
-    } else if (thin && conv) {
-        if (g.b_lo_zero) hipLaunchKernelGGL((gemm_split_glds_kernel<MODE_CONV3, 2, 4, true, false, 1>), grid, dim3(512), lds, stream, g);
-        else hipLaunchKernelGGL((gemm_split_glds_kernel<MODE_CONV3, 2, 4, false, false, 1>), grid, dim3(512), lds, stream, g);
-    } else if (thin) {
-        if (g.ksplit > 1) {
-            if (g.b_lo_zero) hipLaunchKernelGGL((gemm_split_glds_kernel<MODE_PLAIN, 2, 4, true, true, 1>), grid, dim3(512), lds, stream, g);
-            else hipLaunchKernelGGL((gemm_split_glds_kernel<MODE_PLAIN, 2, 4, false, true, 1>), grid, dim3(512), lds, stream, g);
-        } else {
-            if (g.b_lo_zero) hipLaunchKernelGGL((gemm_split_glds_kernel<MODE_PLAIN, 2, 4, true, false, 1>), grid, dim3(512), lds, stream, g);
-            else hipLaunchKernelGGL((gemm_split_glds_kernel<MODE_PLAIN, 2, 4, false, false, 1>), grid, dim3(512), lds, stream, g);
-        }
-    } else if (g.ksplit > 1) {
-        if (g.b_lo_zero) hipLaunchKernelGGL((gemm_split_glds_kernel<MODE_PLAIN, 2, 2, true, true>), grid, dim3(256), lds, stream, g);
-        else hipLaunchKernelGGL((gemm_split_glds_kernel<MODE_PLAIN, 2, 2, false, true>), grid, dim3(256), lds, stream, g);
-    } else if (wm == 2) {
-        if (convs) BG_LAUNCH(MODE_CONV3S, 2, 2, 256);
-        else if (conv) BG_LAUNCH(MODE_CONV3, 2, 2, 256);
-        else BG_LAUNCH(MODE_PLAIN, 2, 2, 256);
-    } else {
-        if (convs) BG_LAUNCH(MODE_CONV3S, 4, 3, 512);
-        else if (conv) BG_LAUNCH(MODE_CONV3, 4, 3, 512);
-        else BG_LAUNCH(MODE_PLAIN, 4, 3, 512);
+    unsigned* const status = status_current();
+    for (int i = 0; i < plan.n; ++i) {
+        GldsLaunch& l = plan.l[i];
+        const int k = glds_variant_index(l.v);
+        BG_REQUIRE(k >= 0, "gemm_split_glds: no instantiation <%d,%d,%d,w16=%d,ks=%d,%d,%d>%s", l.v.mode, l.v.wm, l.v.s, (int)l.v.w16, (int)l.v.ks, l.v.ti, l.v.tj, l.v.sk ? " (stream-K)" : "");
+        l.g.status = status;
+        ProfScope prof(l.prof_kind, l.work, stream);
+        void* args[] = {&l.g};
+        HIP_CHECK(hipLaunchKernel(reinterpret_cast<const void*>(kGldsKernels[k]), l.grid, dim3(l.threads), args, l.lds, stream));
+        LAUNCH_CHECK();
+        if (l.reduce_after) launch_splitk_reduce(l.g, l.g.kpart, l.g.ksplit, stream);
     }
-#undef BG_LAUNCH
-    LAUNCH_CHECK();
-    if (g.ksplit > 1) launch_splitk_reduce(g, g.kpart, g.ksplit, stream);
 }
 
 }  // namespace bevgen

@@ -686,3 +686,23 @@ for (M, N, K, mode) in [(8448 + 37, 1024, 256, 3), (66 * 256, 1024, 128, 4), (30
         assert res.returncode == 0, res.stdout[-2000:] + res.stderr[-2000:]
         outs.append([l for l in res.stdout.splitlines() if l.startswith("digest")])
     assert len(outs[0]) == 3 and outs[0] == outs[1], (outs[0], outs[1])
+
+
+@pytest.mark.parametrize("M,N,K,mode", [(4097, 1024, 64, 4),     # <PLAIN, 2, 2> x W16: 264 blocks of 128 rows, two per CU - four waves on two stages, ragged last block
+                                        (12288, 1024, 64, 3)])   # row split whose rest (rows 8192..12288) runs as eight-wave 128-row blocks <PLAIN, 2, 4, TI = 1>
+def test_gemm_plan_variants_run(gpu_ctx, M, N, K, mode):
+    """Rows of the launcher's variant table (gemm_plan.h) that no other operator test selects under default switches (tests/host/gemm_plan_dump.cpp shows which row a shape
+    gets), at the smallest shape that selects them: bias + GELU + residual against the fp64 product.  The output starts as NaN, so a row no launch covered shows."""
+    g = torch.Generator().manual_seed(M + N + K)
+    a = torch.randn(M, K, generator=g) * 3.0
+    w = torch.randn(N, K, generator=g) / math.sqrt(K)
+    if mode == 4:
+        w = w.half().float()
+    b = torch.randn(N, generator=g)
+    r = torch.randn(M, N, generator=g)
+    ref = F.gelu((a.double() @ w.double().t()) + b.double()) + r.double()
+    from bevgen_amd.runtime import _ptr, _stream
+    da, dw, db, dr = dev(a), dev(w), dev(b), dev(r)
+    out = torch.full((M, N), float("nan"), device="cuda")
+    gpu_ctx._check(gpu_ctx.lib.bevgen_op_gemm(gpu_ctx._h, _ptr(da), _ptr(dw), _ptr(db), _ptr(dr), _ptr(out), M, N, K, 1, mode, _stream()))
+    assert rel(out.cpu().double(), ref) < 2e-6
