@@ -279,19 +279,21 @@ int bevgen_op_gemm(bevgen_ctx* ctx, const float* a, const float* w, const float*
         const bool stream_k = skinny_in == 6;
         if (skinny == 4 || skinny == 3 || skinny == 2) {  // split-precision paths with on-the-fly operand splits (tests / roofline probes): 3 = LDS-DMA kernel, 4 = the same for
                                                           // an f16-representable w (two MFMAs per product: the weights='f16' mode's kernel)
-            ctx->arena.reserve(((size_t)N * K + (size_t)M * K) * 4 + (ksplit3 ? (size_t)3 * M * N * 4 : 0) + (stream_k ? gemm_sk_ws_bytes() : 0) + 8192);
-            ctx->arena.reset();
-            uint16_t* bp = reinterpret_cast<uint16_t*>(ctx->arena.alloc((size_t)N * K * 4));
+            uint16_t *bp, *ap;
+            ctx->arena.carve([&](Arena& ar) {
+                bp = ar.get<uint16_t>((size_t)N * K * 2);
+                ap = skinny >= 3 ? ar.get<uint16_t>((size_t)M * K * 2) : nullptr;
+                g.kpart = skinny >= 3 && ksplit3 ? ar.get<float>((size_t)3 * M * N) : nullptr;
+                g.sk_ws = skinny >= 3 && stream_k ? ar.alloc(gemm_sk_ws_bytes()) : nullptr;
+            });
             launch_split_weight(w, bp, (long)N * K, (hipStream_t)stream);
             g.B_hi = bp; g.B_lo = bp + 32;
             if (skinny >= 3) {
                 g.b_lo_zero = skinny == 4;
-                uint16_t* ap = reinterpret_cast<uint16_t*>(ctx->arena.alloc((size_t)M * K * 4));
                 launch_split_weight(a, ap, (long)M * K, (hipStream_t)stream);
                 g.A_hi = ap; g.A_lo = ap + 32;
-                if (ksplit3) { g.ksplit = 3; g.kpart = ctx->arena.get<float>((size_t)3 * M * N); }
+                if (ksplit3) g.ksplit = 3;
                 if (stream_k) {
-                    g.sk_ws = ctx->arena.alloc(gemm_sk_ws_bytes());
                     HIP_CHECK(hipMemsetAsync(g.sk_ws, 0, 1024 * sizeof(unsigned), (hipStream_t)stream));
                     g.sk_epoch = 1; g.sk_force = true;
                 }
@@ -300,9 +302,9 @@ int bevgen_op_gemm(bevgen_ctx* ctx, const float* a, const float* w, const float*
                 launch_gemm_split(g, (hipStream_t)stream);
             }
         } else if (skinny) {   // split-K workspace from this context's arena (one per context / device)
-            ctx->arena.reserve(gemm_skinny_ws_bytes(M, N, K) + 4096);
-            ctx->arena.reset();
-            launch_gemm_skinny_ws(g, reinterpret_cast<float*>(ctx->arena.alloc(gemm_skinny_ws_bytes(M, N, K))), (hipStream_t)stream);
+            float* ws;
+            ctx->arena.carve([&](Arena& ar) { ws = reinterpret_cast<float*>(ar.alloc(gemm_skinny_ws_bytes(M, N, K))); });
+            launch_gemm_skinny_ws(g, ws, (hipStream_t)stream);
         }
         else launch_gemm(g, (hipStream_t)stream);
     });
@@ -314,17 +316,18 @@ int bevgen_op_ln_gemm(bevgen_ctx* ctx, const float* a, const float* ln_w, const 
         BG_REQUIRE(skinny_fused_supported(M, N, K, ln_w != nullptr), "op_ln_gemm: unsupported shape M=%d N=%d K=%d", M, N, K);
         SkinnyFusedArgs g;
         g.A = a; g.lda = K; g.ln_w = ln_w; g.ln_b = ln_b; g.eps = eps;
-        ctx->arena.reserve((skinny_packed_floats(N, K) + 2 * (size_t)N) * sizeof(float) + 8192);
-        ctx->arena.reset();
-        float* wp = ctx->arena.get<float>(skinny_packed_floats(N, K));
+        float *wp, *cs, *ds;
+        ctx->arena.carve([&](Arena& ar) {
+            wp = ar.get<float>(skinny_packed_floats(N, K));
+            cs = ksplit == -1 ? ar.get<float>((size_t)N) : nullptr;
+            ds = ksplit == -1 ? ar.get<float>((size_t)N) : nullptr;
+        });
         launch_pack_skinny_weight(w, wp, N, K, (hipStream_t)stream);
         g.Wp = wp; g.bias = bias; g.C = c; g.ldc = N;
         g.M = M; g.N = N; g.K = K; g.act = act_gelu ? ACT_GELU : ACT_NONE;
         g.ksplit = ksplit > 0 ? ksplit : (ln_w ? 1 : skinny_fused_ksplit(N, K));
         if (ksplit == -1) {   // the form the decode step launches for ln2 + MLP-up: LayerNorm folded into the product, row constants from launch_ar_ln_fold
             BG_REQUIRE(ln_w && ln_b && bias, "op_ln_gemm: ksplit = -1 (folded LayerNorm) needs gamma, beta and a bias");
-            float* cs = ctx->arena.get<float>((size_t)N);
-            float* ds = ctx->arena.get<float>((size_t)N);
             launch_ar_ln_fold(w, bias, ln_w, ln_b, cs, ds, N, K, (hipStream_t)stream);
             g.ln_cs = cs; g.ln_ds = ds;
         }
@@ -341,22 +344,23 @@ int bevgen_op_mlp_fused(bevgen_ctx* ctx, const float* x, const float* ln_w, cons
         BG_REQUIRE(x && ln_w && ln_b && w1 && b1 && w2 && b2 && out, "op_mlp_fused: missing operand");
         BG_REQUIRE(mlp_fused_supported(M, D, w_f16 != 0), "op_mlp_fused: unsupported shape M=%d D=%d (or a device with fewer CUs than workgroups / BEVGEN_MLP_FUSE=0)", M, D);
         const size_t eb = w_f16 ? sizeof(_Float16) : sizeof(float);
-        const size_t wbytes = (skinny_packed_floats(4 * D, D) + skinny_packed_floats(D, 4 * D)) * eb;
-        const size_t fl = (size_t)8 * D + (size_t)M * 4 * D + (size_t)MLP_FUSED_PLANES * M * D + (size_t)M * D + 2 * (size_t)4 * D * D;
-        ctx->arena.reserve(wbytes + fl * sizeof(float) + mlp_fused_sync_words() * sizeof(unsigned) + 64 * 256);
-        ctx->arena.reset();
-        void* w1p = ctx->arena.alloc(skinny_packed_floats(4 * D, D) * eb);
-        void* w2p = ctx->arena.alloc(skinny_packed_floats(D, 4 * D) * eb);
-        float* cs = ctx->arena.get<float>((size_t)4 * D);
-        float* ds = ctx->arena.get<float>((size_t)4 * D);
-        float* hidden = ctx->arena.get<float>((size_t)M * 4 * D);
-        float* part = ctx->arena.get<float>((size_t)MLP_FUSED_PLANES * M * D);
-        float* zero = ctx->arena.get<float>((size_t)M * D);
-        unsigned* sync = ctx->arena.get<unsigned>(mlp_fused_sync_words());
+        void *w1p, *w2p;
+        float *cs, *ds, *hidden, *part, *zero, *w1r, *w2r;
+        unsigned* sync;
+        ctx->arena.carve([&](Arena& ar) {
+            w1p = ar.alloc(skinny_packed_floats(4 * D, D) * eb);
+            w2p = ar.alloc(skinny_packed_floats(D, 4 * D) * eb);
+            cs = ar.get<float>((size_t)4 * D);
+            ds = ar.get<float>((size_t)4 * D);
+            hidden = ar.get<float>((size_t)M * 4 * D);
+            part = ar.get<float>((size_t)MLP_FUSED_PLANES * M * D);
+            zero = ar.get<float>((size_t)M * D);
+            sync = ar.get<unsigned>(mlp_fused_sync_words());
+            w1r = w_f16 ? ar.get<float>((size_t)4 * D * D) : nullptr;
+            w2r = w_f16 ? ar.get<float>((size_t)4 * D * D) : nullptr;
+        });
         const float *w1u = w1, *w2u = w2;
         if (w_f16) {   // the model decode_weights = f16 defines: matrices rounded to fp16-representable values (row constants from the rounded matrix, as bevgen_finalize does)
-            float* w1r = ctx->arena.get<float>((size_t)4 * D * D);
-            float* w2r = ctx->arena.get<float>((size_t)4 * D * D);
             HIP_CHECK(hipMemcpyAsync(w1r, w1, (size_t)4 * D * D * sizeof(float), hipMemcpyDeviceToDevice, s));
             HIP_CHECK(hipMemcpyAsync(w2r, w2, (size_t)4 * D * D * sizeof(float), hipMemcpyDeviceToDevice, s));
             launch_round_to_f16(w1r, nullptr, (long)4 * D * D, s);
@@ -464,24 +468,27 @@ int bevgen_op_attention_ex(bevgen_ctx* ctx, const float* q, const float* k, cons
             const size_t bpk = bias ? (size_t)attn_bias_packed_floats(Nq, Nk_pad) : 0, braw = bias ? (size_t)Nq * ldbias : 0;
             BG_REQUIRE(key_splits >= 1 && key_splits <= 8 && Nk_pad / 32 >= key_splits, "op_attention: key_splits=%d out of range for Nk_pad=%d", key_splits, Nk_pad);
             const size_t kws = key_splits > 1 ? (size_t)attn_split_ws_floats(B, H, Nq, key_splits) : 0;
-            ctx->arena.reserve((nq + 2 * nk) * 4 + (bpk + braw + kws) * 4 + 8192);
-            ctx->arena.reset();
-            _Float16* Qp = reinterpret_cast<_Float16*>(ctx->arena.alloc(nq * 4));
-            _Float16* Kp = reinterpret_cast<_Float16*>(ctx->arena.alloc(nk * 4));
-            _Float16* Vp = reinterpret_cast<_Float16*>(ctx->arena.alloc(nk * 4));
-            launch_attn_split_operands(q, k, v, Qp, Qp + nq, Kp, Kp + nk, Vp, Vp + nk, B, H, Nq, Nk_pad, scale * kLog2e, s);
+            _Float16 *Qp, *Kp, *Vp;
+            float *b2, *pk;
             AttnSplitArgs sa{};
+            ctx->arena.carve([&](Arena& ar) {
+                Qp = ar.get<_Float16>(nq * 2);
+                Kp = ar.get<_Float16>(nk * 2);
+                Vp = ar.get<_Float16>(nk * 2);
+                b2 = bias ? ar.get<float>(braw) : nullptr;
+                pk = bias ? ar.get<float>(bpk) : nullptr;
+                sa.kws = key_splits > 1 ? ar.get<float>(kws) : nullptr;
+            });
+            launch_attn_split_operands(q, k, v, Qp, Qp + nq, Kp, Kp + nk, Vp, Vp + nk, B, H, Nq, Nk_pad, scale * kLog2e, s);
             sa.Qh = Qp; sa.Ql = Qp + nq; sa.Kh = Kp; sa.Kl = Kp + nk; sa.VTh = Vp; sa.VTl = Vp + nk;
             if (bias) {
-                float* b2 = reinterpret_cast<float*>(ctx->arena.alloc(braw * 4));
-                float* pk = reinterpret_cast<float*>(ctx->arena.alloc(bpk * 4));
                 HIP_CHECK(hipMemcpyAsync(b2, bias, braw * 4, hipMemcpyDeviceToDevice, s));
                 launch_scale(b2, (long)braw, kLog2e, s);
                 launch_pack_attn_bias(b2, ldbias, Nq, Nk_pad, pk, s);
                 sa.bias = b2; sa.bias_pk = pk; sa.ldbias = ldbias;
             }
             sa.bias_head_stride = 0;
-            if (key_splits > 1) { sa.ksplit = key_splits; sa.kws = reinterpret_cast<float*>(ctx->arena.alloc(kws * 4)); }
+            if (key_splits > 1) sa.ksplit = key_splits;
             sa.O = out; sa.Op = nullptr; sa.B = B; sa.H = H; sa.Nq = Nq; sa.Nk_pad = Nk_pad; sa.scale = scale * kLog2e;
             sa.o_bstride = (long)Nq * H * 64; sa.o_qstride = (long)H * 64; sa.o_hstride = 64;
             launch_attention_split(sa, s);
@@ -507,9 +514,9 @@ int bevgen_op_decode_attention(bevgen_ctx* ctx, const float* q, const void* kc, 
         a.vis.allowed = keep; a.vis.ldallowed = ldkeep; a.vis.allowed_head_stride = keep_head_stride;   // a dense per-head plane is an element mask with a head stride
         a.O = out; a.ldo = H * 64; a.B = B; a.H = H; a.n = n; a.Lmax = Lmax; a.scale = scale;
         const int S = decode_attention_splits(a.B, a.H, a.n);
-        ctx->arena.reserve(decode_attention_ws_bytes(a.B, a.H, S) + 4096);
-        ctx->arena.reset();
-        launch_decode_attention_ws(a, reinterpret_cast<float*>(ctx->arena.alloc(decode_attention_ws_bytes(a.B, a.H, S))), S, (hipStream_t)stream);
+        float* ws;
+        ctx->arena.carve([&](Arena& ar) { ws = reinterpret_cast<float*>(ar.alloc(decode_attention_ws_bytes(a.B, a.H, S))); });
+        launch_decode_attention_ws(a, ws, S, (hipStream_t)stream);
     });
 }
 
@@ -523,38 +530,46 @@ int bevgen_op_ar_attn_fused(bevgen_ctx* ctx, const float* x, const float* partia
         BG_REQUIRE(ar_attn_fused_supported(B, G, D, H), "op_ar_attn_fused: unsupported shape B=%d G=%d D=%d H=%d", B, G, D, H);
         BG_REQUIRE(!layout || (block >= 1 && L % block == 0), "op_ar_attn_fused: Lmax %d is not a multiple of the block size %d", L, block);
         const int nb = layout ? L / block : 0, cld = (int)cdiv(L, 16) + 1;
-        ctx->arena.reserve((size_t)L * L + (size_t)H * nb * nb + (size_t)H * nb * cld * 2 + (size_t)3 * D * D * 6 + (size_t)6 * D * 4 + (split ? skinny_packed_floats(3 * D, D) * 4 + (size_t)B * 4 * D * 4 + (size_t)B * H * (split > 1 ? split : 0) * 66 * 4 : 0) + 14 * 256);
-        ctx->arena.reset();
         ArAttnFusedArgs a;
+        if (split == -1) { a.stage_cap = 0; split = 0; }                       // the fused kernel without K/V pieces staged in LDS
+        void* h;
+        float *tmp, *cs, *ds, *wp, *qkv, *xn;
+        uint8_t *al, *lay;
+        uint16_t* ch;
+        ctx->arena.carve([&](Arena& ar) {
+            h = w_f16 ? ar.alloc((size_t)3 * D * D * 2) : nullptr;
+            tmp = w_f16 ? ar.get<float>((size_t)3 * D * D) : nullptr;   // round_to_f16 rounds in place: work on a copy of the caller's matrix (arena: no allocation, no sync)
+            cs = ar.get<float>((size_t)3 * D);   // row constants of the folded ln1
+            ds = ar.get<float>((size_t)3 * D);
+            al = attn_mask ? ar.get<uint8_t>((size_t)L * L) : nullptr;
+            lay = layout ? ar.get<uint8_t>((size_t)H * nb * nb) : nullptr;
+            ch = layout ? ar.get<uint16_t>((size_t)H * nb * cld) : nullptr;
+            wp = split ? ar.get<float>(skinny_packed_floats(3 * D, D)) : nullptr;
+            qkv = split ? ar.get<float>((size_t)B * 3 * D) : nullptr;
+            xn = split ? ar.get<float>((size_t)B * D) : nullptr;
+            a.kws = split > 1 ? ar.get<float>((size_t)B * H * split * 66) : nullptr;   // split = k > 1: the partial states of the k key ranges
+        });
         a.x.base = x; a.x.ld = D;
         if (partial && ns > 0) { a.x.partial = partial; a.x.ns = ns; a.x.pstride = (long)B * D; a.x.pld = D; }
         a.x.bias = rbias;
         a.ln_w = ln_w; a.ln_b = ln_b; a.wqkv = wqkv; a.bqkv = bqkv;
         const float* w_rounded = nullptr;
         if (w_f16) {
-            void* h = ctx->arena.alloc((size_t)3 * D * D * 2);
-            float* tmp = ctx->arena.get<float>((size_t)3 * D * D);   // round_to_f16 rounds in place: work on a copy of the caller's matrix (arena: no allocation, no sync)
             HIP_CHECK(hipMemcpyAsync(tmp, wqkv, (size_t)3 * D * D * 4, hipMemcpyDeviceToDevice, s));
             launch_round_to_f16(tmp, h, 3L * D * D, s);
             a.wqkv_h = h;
             w_rounded = tmp;
         }
-        {   // row constants of the folded ln1, on the matrix the kernel multiplies by (the fp16-rounded one with w_f16)
-            float* cs = ctx->arena.get<float>((size_t)3 * D);
-            float* ds = ctx->arena.get<float>((size_t)3 * D);
-            launch_ar_ln_fold(w_f16 ? w_rounded : wqkv, bqkv, ln_w, ln_b, cs, ds, 3 * D, D, s);
-            a.ln_cs = cs; a.ln_ds = ds;
-        }
+        // row constants of the folded ln1, on the matrix the kernel multiplies by (the fp16-rounded one with w_f16)
+        launch_ar_ln_fold(w_f16 ? w_rounded : wqkv, bqkv, ln_w, ln_b, cs, ds, 3 * D, D, s);
+        a.ln_cs = cs; a.ln_ds = ds;
         a.kcache = kc; a.vcache = vc; a.kv_dtype = kv_dtype;
         a.bias = bias; a.ldbias = ldbias;
         if (attn_mask) {
-            uint8_t* al = ctx->arena.get<uint8_t>((size_t)L * L);
             launch_build_allowed(attn_mask, al, (long)L * L, s);
             a.vis.allowed = al; a.vis.ldallowed = L;
         }
         if (layout) {
-            uint8_t* lay = ctx->arena.get<uint8_t>((size_t)H * nb * nb);
-            uint16_t* ch = ctx->arena.get<uint16_t>((size_t)H * nb * cld);
             launch_build_layout(layout, lay, ch, H, nb, block, L, cld, s);
             a.vis.lay = lay; a.vis.lay_head_stride = (long)nb * nb; a.vis.nb = nb; a.vis.blk = block;
             a.vis.chunks = ch; a.vis.chunks_head_stride = (long)nb * cld; a.vis.chunks_ld = cld;
@@ -562,12 +577,8 @@ int bevgen_op_ar_attn_fused(bevgen_ctx* ctx, const float* x, const float* partia
         a.out = out; a.ldo = D;
         a.B = B; a.G = G; a.H = H; a.D = D; a.Lmax = Lmax; a.n = n; a.prefix = prefix; a.scale = 0.125f;
         a.trace = ctx->trace;
-        if (split == -1) { a.stage_cap = 0; split = 0; }                       // the fused kernel without K/V pieces staged in LDS
         if (split) {
             BG_REQUIRE(skinny_fused_supported(B, 3 * D, D, true) && (!w_f16 || skinny_fused_f16_ok(3 * D, D, true)), "op_ar_attn_fused: the split form does not support B=%d D=%d", B, D);
-            float* wp = ctx->arena.get<float>(skinny_packed_floats(3 * D, D));
-            float* qkv = ctx->arena.get<float>((size_t)B * 3 * D);
-            float* xn = ctx->arena.get<float>((size_t)B * D);
             if (w_f16) launch_pack_skinny_weight_f16(wqkv, wp, 3 * D, D, s);   // rounds to fp16 while packing
             else launch_pack_skinny_weight(wqkv, wp, 3 * D, D, s);
             SkinnyFusedArgs pq;
@@ -581,7 +592,6 @@ int bevgen_op_ar_attn_fused(bevgen_ctx* ctx, const float* x, const float* partia
             if (split > 1) {   // split = k > 1: the attention-only kernel with its key walk cut into k ranges (one sequence per workgroup)
                 BG_REQUIRE(G == 1, "op_ar_attn_fused: a key split needs G = 1");
                 a.ksplit = split;
-                a.kws = ctx->arena.get<float>((size_t)B * H * split * 66);
             }
         }
         launch_ar_attn_fused(a, s);
@@ -602,10 +612,11 @@ int bevgen_op_conv3x3(bevgen_ctx* ctx, const float* x, const float* w, const flo
         if (flags & 2) {
             BG_REQUIRE(Cin % 32 == 0, "op_conv3x3: the LDS-DMA kernel needs Cin %% 32 == 0 (Cin=%d)", Cin);
             const size_t xb = (size_t)n * H * W * Cin * 4, wb = (size_t)Cout * 9 * Cin * 4;
-            ctx->arena.reserve(xb + wb + 4096);
-            ctx->arena.reset();
-            uint16_t* ap = reinterpret_cast<uint16_t*>(ctx->arena.alloc(xb));
-            uint16_t* bp = reinterpret_cast<uint16_t*>(ctx->arena.alloc(wb));
+            uint16_t *ap, *bp;
+            ctx->arena.carve([&](Arena& ar) {
+                ap = reinterpret_cast<uint16_t*>(ar.alloc(xb));
+                bp = reinterpret_cast<uint16_t*>(ar.alloc(wb));
+            });
             launch_split_weight(x, ap, (long)n * H * W * Cin, (hipStream_t)stream);
             launch_split_weight(w, bp, (long)Cout * 9 * Cin, (hipStream_t)stream);
             g.A = nullptr; g.A_hi = ap; g.A_lo = ap + 32; g.B_hi = bp; g.B_lo = bp + 32;
@@ -617,10 +628,12 @@ int bevgen_op_conv3x3(bevgen_ctx* ctx, const float* x, const float* w, const flo
 
 int bevgen_op_groupnorm(bevgen_ctx* ctx, const float* x, const float* gamma, const float* beta, float* y, int n, int hw, int C, int swish, void* stream) {
     return guarded(ctx, [&] {
-        ctx->arena.reserve(groupnorm_ws_bytes(n, hw) + (size_t)n * 64 * sizeof(float) + 1024);
-        ctx->arena.reset();
-        float* stats = ctx->arena.get<float>((size_t)n * 64);
-        void* ws = ctx->arena.alloc(groupnorm_ws_bytes(n, hw));
+        float* stats;
+        void* ws;
+        ctx->arena.carve([&](Arena& ar) {
+            stats = ar.get<float>((size_t)n * 64);
+            ws = ar.alloc(groupnorm_ws_bytes(n, hw));
+        });
         launch_groupnorm_stats(x, stats, ws, n, hw, C, 1e-6f, (hipStream_t)stream);
         launch_groupnorm_apply(x, stats, gamma, beta, y, n, hw, C, swish, (hipStream_t)stream);
     });
@@ -630,9 +643,8 @@ int bevgen_op_range_split(bevgen_ctx* ctx, const float* x, int n, int hw, int C,
     return guarded(ctx, [&] {
         BG_REQUIRE(x && planes && d_exp && n >= 1 && hw >= 1 && C >= 32 && C % 32 == 0, "op_range_split: bad arguments (C must be a multiple of 32)");
         hipStream_t s = (hipStream_t)stream;
-        ctx->arena.reserve(4096);
-        ctx->arena.reset();
-        unsigned* amax = ctx->arena.get<unsigned>(1);
+        unsigned* amax;
+        ctx->arena.carve([&](Arena& ar) { amax = ar.get<unsigned>(1); });
         HIP_CHECK(hipMemsetAsync(amax, 0, sizeof(unsigned), s));
         launch_range_exponent(x, (long)n * hw * C, amax, d_exp, s);
         launch_range_split(x, planes, (long)n * hw, C, d_exp, s);

@@ -100,10 +100,10 @@ bool mlp_fused_step(const Ctx& c, int Bc, bool split, int chains) {
            mlp_fused_supported(Bc, c.D, c.cfg.decode_weight_dtype == BEVGEN_W_F16);
 }
 
-StepWs step_ws(Ctx& c, int B) {
-    // fixed layout at the start of the per-call arena (so a captured graph keeps seeing the same addresses)
+// The decode-step buffers: a layout function (arena.h), fixed at the start of the per-call arena so that a captured graph keeps seeing the same addresses.  ar_prefill and
+// ar_forward start their layouts with it; ar_logits, ar_decode_step and ar_sample re-carve it alone after a reset() WITHOUT reserving: they rely on that reservation.
+StepWs step_ws(const Ctx& c, Arena& a, int B) {
     StepWs w;
-    Arena& a = c.arena;
     const int D = c.D;
     w.x = a.get<float>((size_t)B * D);
     w.xn = a.get<float>((size_t)B * D);
@@ -121,15 +121,6 @@ StepWs step_ws(Ctx& c, int B) {
     w.x2b = a.get<float>((size_t)B * D);
     w.part = a.get<float>(part_floats(c, B));
     return w;
-}
-
-size_t step_ws_bytes(const Ctx& c, int B) {
-    const int D = c.D;
-    size_t f = (size_t)B * D * 4 + (size_t)B * 3 * D + (size_t)B * 4 * D + (size_t)B * c.V;
-    const int S = decode_attention_splits(B, c.H, c.L);
-    size_t gw = std::max(std::max(gemm_skinny_ws_bytes(B, 3 * D, D), gemm_skinny_ws_bytes(B, 4 * D, D)),
-                         std::max(gemm_skinny_ws_bytes(B, D, 4 * D), gemm_skinny_ws_bytes(B, c.V, D)));
-    return f * sizeof(float) + decode_attention_ws_bytes(B, c.H, S) + gw + B * sizeof(int64_t) + ((size_t)B * D + part_floats(c, B)) * sizeof(float) + 16 * 256;
 }
 
 void small_gemm(const float* A, int lda, const float* W, int ldb, const float* bias, float* C, int ldc, int M, int N, int K, int act, const float* R, int ldr,
@@ -150,30 +141,30 @@ void sparse_self_attention_op(Ctx& c, const float* q, const float* k, const floa
     BG_REQUIRE(L % block == 0, "Sequence Length, %d, needs to be dividable by Block size %d!", L, block);  // ssa:54-57
     const int Lpad = (int)round_up(L, 32);
     const int nb = L / block;
-    const size_t keep_b = (size_t)L * L + (size_t)H * nb * nb + (size_t)H * nb * (cdiv(L, 16) + 1) * sizeof(uint16_t) + attn_tiles_elems(H, L, Lpad) * sizeof(uint16_t) + 4 * 256;
-    const size_t bias_b = (size_t)H * L * Lpad * sizeof(float);
-    const size_t kv_b = Lpad != L ? (size_t)2 * B * H * Lpad * 64 * sizeof(float) : 0;
-    c.arena.reserve(keep_b + bias_b + kv_b + 8 * 256);
-    c.arena.reset();
+    const bool pad = Lpad != L;
+    struct { uint8_t *allowed, *lay; uint16_t *chunks, *tiles; float *bias, *kpad, *vpad; } w;
+    c.arena.carve([&](Arena& a) {
+        w.allowed = a.get<uint8_t>((size_t)L * L);
+        w.lay = a.get<uint8_t>((size_t)H * nb * nb);
+        w.chunks = a.get<uint16_t>((size_t)H * nb * (cdiv(L, 16) + 1));
+        w.bias = a.get<float>((size_t)H * L * Lpad);
+        w.tiles = a.get<uint16_t>(attn_tiles_elems(H, L, Lpad));
+        w.kpad = pad ? a.get<float>((size_t)B * H * Lpad * 64) : nullptr;
+        w.vpad = pad ? a.get<float>((size_t)B * H * Lpad * 64) : nullptr;
+    });
     SparseVis vis;
-    {
-        uint8_t* allowed = c.arena.get<uint8_t>((size_t)L * L);
-        uint8_t* lay = c.arena.get<uint8_t>((size_t)H * nb * nb);
-        uint16_t* chunks = c.arena.get<uint16_t>((size_t)H * nb * (cdiv(L, 16) + 1));
-        launch_build_allowed(mask, allowed, (long)L * L, s);
-        launch_build_layout(layout, lay, chunks, H, nb, block, L, (int)cdiv(L, 16) + 1, s);
-        vis.allowed = allowed; vis.ldallowed = L;
-        vis.lay = lay; vis.lay_head_stride = (long)nb * nb; vis.nb = nb; vis.blk = block;
-    }
-    float* bias = c.arena.get<float>((size_t)H * L * Lpad);
+    launch_build_allowed(mask, w.allowed, (long)L * L, s);
+    launch_build_layout(layout, w.lay, w.chunks, H, nb, block, L, (int)cdiv(L, 16) + 1, s);
+    vis.allowed = w.allowed; vis.ldallowed = L;
+    vis.lay = w.lay; vis.lay_head_stride = (long)nb * nb; vis.nb = nb; vis.blk = block;
+    float* bias = w.bias;
     launch_build_masked_bias(add, vis, bias, H, L, L, Lpad, L, 0.125f, s);
     // only the key tiles in which some row of a query block sees a key are loaded and multiplied (the reference computes the nonzero layout blocks only, ssa:63-85)
-    uint16_t* tiles = c.arena.get<uint16_t>(attn_tiles_elems(H, L, Lpad));
+    uint16_t* tiles = w.tiles;
     launch_build_attn_tiles(bias, (long)L * Lpad, Lpad, H, L, Lpad, tiles, s);
     const float *kp = k, *vp = v;
-    if (Lpad != L) {
-        float* kpad = c.arena.get<float>((size_t)B * H * Lpad * 64);
-        float* vpad = c.arena.get<float>((size_t)B * H * Lpad * 64);
+    if (pad) {
+        float *kpad = w.kpad, *vpad = w.vpad;
         HIP_CHECK(hipMemsetAsync(kpad, 0, (size_t)B * H * Lpad * 64 * sizeof(float), s));
         HIP_CHECK(hipMemsetAsync(vpad, 0, (size_t)B * H * Lpad * 64 * sizeof(float), s));
         HIP_CHECK(hipMemcpy2DAsync(kpad, (size_t)Lpad * 256, k, (size_t)L * 256, (size_t)L * 256, (size_t)B * H, hipMemcpyDeviceToDevice, s));
@@ -197,18 +188,16 @@ static void ar_state_setup(Ctx& c, int B, hipStream_t s) {
     const int D = c.D, H = c.H, L = c.L;
     auto& st = c.ars;
     const size_t cache_b = (size_t)g.num_layers * B * H * L * 64 * cache_elem_bytes(c);
-    const size_t img_b = g.image_embed ? (size_t)B * g.num_cams * c.T * D * sizeof(float) : 0;
-    const size_t need = 2 * cache_b + img_b + (size_t)B * g.num_cams * D * sizeof(float) + (size_t)B * D * sizeof(float) + 16 * 256;
-    c.persist.reserve(need);
-    c.persist.reset();
     st.B = B;
     st.step = 0;
-    st.kcache = c.persist.alloc(cache_b);
-    st.vcache = c.persist.alloc(cache_b);
-    st.img_embed = g.image_embed ? reinterpret_cast<float*>(c.persist.alloc(img_b)) : nullptr;
-    st.c_embed = c.persist.get<float>((size_t)B * g.num_cams * D);
-    st.hidden = c.persist.get<float>((size_t)B * D);
-    st.d_step = c.persist.get<int>(1);
+    c.persist.carve([&](Arena& a) {
+        st.kcache = a.alloc(cache_b);
+        st.vcache = a.alloc(cache_b);
+        st.img_embed = g.image_embed ? a.get<float>((size_t)B * g.num_cams * c.T * D) : nullptr;
+        st.c_embed = a.get<float>((size_t)B * g.num_cams * D);
+        st.hidden = a.get<float>((size_t)B * D);
+        st.d_step = a.get<int>(1);
+    });
     HIP_CHECK(hipMemsetAsync(st.kcache, 0, cache_b, s));
     HIP_CHECK(hipMemsetAsync(st.vcache, 0, cache_b, s));
     HIP_CHECK(hipMemsetAsync(st.d_step, 0, sizeof(int), s));
@@ -232,31 +221,35 @@ void ar_prefill(Ctx& c, const int64_t* cond, const float* I_inv, const float* E_
 
     // workspace: the decode-step buffers first (stable addresses), then the prefill activations
     const size_t rows = (size_t)G * K;
-    const size_t tmp_kv = cache_dtype(c) ? (size_t)2 * G * H * c.Kpad * 64 : 0;   // fp16 cache: the prefill attention reads exact fp32 K/V from a scratch pair
+    const int kvd = cache_dtype(c);   // fp16 cache: the prefill attention reads exact fp32 K/V from a scratch pair
     const size_t layer_bias = c.prefill_bias ? 0 : (size_t)c.keep_heads * K * c.Kpad;   // per-layer layouts: this layer's masked bias is built on the fly
-    const size_t pre_b = (rows * D * 4 + rows * 3 * D + rows * 4 * D + (size_t)G * H * K * 64 + tmp_kv + layer_bias) * sizeof(float) + (size_t)G * (K * 8 + (size_t)(g.num_cams + 1) * D * 4) +
-                         attn_tiles_elems(c.keep_heads, K, c.Kpad) * sizeof(uint16_t) + 34 * 256;
-    c.arena.reserve(step_ws_bytes(c, B) + pre_b);
-    c.arena.reset();
-    (void)step_ws(c, B);
-    float* x = c.arena.get<float>(rows * D);
-    float* xn = c.arena.get<float>(rows * D);
-    float* x2 = c.arena.get<float>(rows * D);
-    float* h = c.arena.get<float>(rows * D);
-    float* qkv = c.arena.get<float>(rows * 3 * D);
-    float* m1 = c.arena.get<float>(rows * 4 * D);
-    float* Q = c.arena.get<float>((size_t)G * H * K * 64);
-    float* lbias = c.prefill_bias ? nullptr : c.arena.get<float>(layer_bias);
-    uint16_t* ltiles = c.arena.get<uint16_t>(attn_tiles_elems(c.keep_heads, K, c.Kpad));   // key tiles of the condition rows that hold a present block (rebuilt per layer when layouts differ)
+    float *x, *xn, *x2, *h, *qkv, *m1, *Q, *lbias, *eg, *tk, *tv, *hid;
+    uint16_t* ltiles;   // key tiles of the condition rows that hold a present block (rebuilt per layer when layouts differ)
+    int64_t* cg;
+    c.arena.carve([&](Arena& a) {
+        (void)step_ws(c, a, B);
+        x = a.get<float>(rows * D);
+        xn = a.get<float>(rows * D);
+        x2 = a.get<float>(rows * D);
+        h = a.get<float>(rows * D);
+        qkv = a.get<float>(rows * 3 * D);
+        m1 = a.get<float>(rows * 4 * D);
+        Q = a.get<float>((size_t)G * H * K * 64);
+        lbias = c.prefill_bias ? nullptr : a.get<float>(layer_bias);
+        ltiles = a.get<uint16_t>(attn_tiles_elems(c.keep_heads, K, c.Kpad));
+        cg = S > 1 ? a.get<int64_t>((size_t)G * K) : nullptr;   // first sequence of every group -> contiguous [G, ...] inputs of the prefill
+        eg = S > 1 ? a.get<float>((size_t)G * g.num_cams * D) : nullptr;
+        tk = kvd ? a.get<float>((size_t)G * H * c.Kpad * 64) : nullptr;
+        tv = kvd ? a.get<float>((size_t)G * H * c.Kpad * 64) : nullptr;
+        hid = S > 1 ? a.get<float>((size_t)G * D) : nullptr;   // the groups' last condition rows, fanned out into st.hidden at the end
+    });
     if (c.prefill_bias) launch_build_attn_tiles(c.prefill_bias, (long)K * c.Kpad, c.Kpad, c.keep_heads, K, c.Kpad, ltiles, s);
 
     if (g.image_embed)   // per-sequence state of the decode steps: for all B sequences
         launch_camera_embed(I_inv, E_inv, c.image_plane, c.pf("img_embed.weight"), c.pf("cam_embed.weight"), st.img_embed, st.c_embed, B, g.num_cams, c.T, D, s);
     const int64_t* cond_g = cond;
     const float* c_embed_g = st.c_embed;
-    if (S > 1) {   // first sequence of every group -> contiguous [G, ...] inputs of the prefill
-        int64_t* cg = c.arena.get<int64_t>((size_t)G * K);
-        float* eg = c.arena.get<float>((size_t)G * g.num_cams * D);
+    if (S > 1) {
         HIP_CHECK(hipMemcpy2DAsync(cg, (size_t)K * 8, cond, (size_t)S * K * 8, (size_t)K * 8, G, hipMemcpyDeviceToDevice, s));
         HIP_CHECK(hipMemcpy2DAsync(eg, (size_t)g.num_cams * D * 4, st.c_embed, (size_t)S * g.num_cams * D * 4, (size_t)g.num_cams * D * 4, G, hipMemcpyDeviceToDevice, s));
         cond_g = cg; c_embed_g = eg;
@@ -264,11 +257,7 @@ void ar_prefill(Ctx& c, const int64_t* cond, const float* I_inv, const float* E_
     launch_cond_embed(cond_g, c.pf("cond_tok_emb.weight"), c.pf("cond_pos_emb"), g.bev_embed ? c.pf("bev_grid") : nullptr, g.bev_embed ? c.pf("bev_embed.weight") : nullptr,
                       g.bev_embed ? c.pf("bev_embed.bias") : nullptr, g.bev_embed ? c.pf("bev_cam_pos_emb") : nullptr, c_embed_g, x, G, g.num_cams, K, D,
                       g.cond_vocab_size, s);
-    const int kvd = cache_dtype(c);
-    float *tk = nullptr, *tv = nullptr;
     if (kvd) {
-        tk = c.arena.get<float>((size_t)G * H * c.Kpad * 64);
-        tv = c.arena.get<float>((size_t)G * H * c.Kpad * 64);
         HIP_CHECK(hipMemsetAsync(tk, 0, (size_t)G * H * c.Kpad * 64 * sizeof(float), s));   // pad rows K..Kpad stay zero
         HIP_CHECK(hipMemsetAsync(tv, 0, (size_t)G * H * c.Kpad * 64 * sizeof(float), s));
     }
@@ -318,7 +307,6 @@ void ar_prefill(Ctx& c, const int64_t* cond, const float* I_inv, const float* E_
         for (int gi = G - 1; gi >= 0; --gi)
             launch_replicate_prefix(st.kcache, st.vcache, g.num_layers, B, H, L, K, gi, gi * S, S, (int)cache_elem_bytes(c), s);
     }
-    float* hid = c.arena.get<float>((size_t)G * D);
     launch_gather_rows(x, hid, G, K - 1, K, D, s);
     for (int j = 0; j < S; ++j)
         HIP_CHECK(hipMemcpy2DAsync(st.hidden + (size_t)j * D, (size_t)S * D * 4, hid, (size_t)D * 4, (size_t)D * 4, G, hipMemcpyDeviceToDevice, s));
@@ -345,7 +333,7 @@ void ar_logits(Ctx& c, float* logits, hipStream_t s) {
     auto& st = c.ars;
     BG_REQUIRE(st.B > 0, "bevgen_ar_prefill must be called first");
     c.arena.reset();
-    StepWs w = step_ws(c, st.B);
+    StepWs w = step_ws(c, c.arena, st.B);
     head_logits(c, w, st.B, logits, s);
 }
 
@@ -544,7 +532,7 @@ void ar_decode_step(Ctx& c, const int64_t* tok, hipStream_t s) {
     BG_REQUIRE(st.B > 0, "bevgen_ar_prefill must be called first");
     BG_REQUIRE(st.step < c.N, "all %d image tokens have already been decoded", c.N);
     c.arena.reset();
-    StepWs w = step_ws(c, st.B);
+    StepWs w = step_ws(c, c.arena, st.B);
     st.pick_embeds = false;   // the caller's tokens: embed them here
     SpinSerial serial(c, s);
     decode_step_launch(c, w, tok, s);
@@ -559,7 +547,7 @@ void ar_sample(Ctx& c, const int64_t* cond, const float* I_inv, const float* E_i
     auto& st = c.ars;
     c.step_events_used = 0;   // bevgen_ar_step_times describes THIS call: a call that takes the eager path below reports no steps
     c.arena.reset();
-    StepWs w = step_ws(c, B);
+    StepWs w = step_ws(c, c.arena, B);
     launch_fill_i64(out, (long)B * c.N, c.cfg.vocab_size, s);  // x = vocab_size everywhere (ar_lm:157)
 
     // one decode iteration: logits of the newest row -> token -> (optionally) push the token through the stack.
@@ -674,27 +662,26 @@ void ar_forward(Ctx& c, const int64_t* cond, const float* I_inv, const float* E_
     const int CH = std::min(n, 2048);   // head chunk (rows of one sequence)
     const int Hk = c.keep_heads;
     const size_t kv_g = (size_t)Bg * H * Rpad * 64;
-    const size_t fwd_b = ((size_t)B * R * D + (size_t)B * K * D + rows_g * D * 3 + rows_g * 3 * D + rows_g * 4 * D + (size_t)Bg * H * R * 64 + 2 * kv_g + (size_t)Hk * R * Rpad +
-                          (size_t)CH * D + (logits ? 0 : (size_t)CH * V) + (size_t)B * n) * sizeof(float) +
-                         attn_tiles_elems(Hk, R, Rpad) * sizeof(uint16_t) + 32 * 256;
-    c.arena.reserve(step_ws_bytes(c, B) + fwd_b);
-    c.arena.reset();
-    (void)step_ws(c, B);   // the decode-step buffers keep their addresses at the start of the arena
-    float* x = c.arena.get<float>((size_t)B * R * D);
-    float* cx = c.arena.get<float>((size_t)B * K * D);
-    float* xn = c.arena.get<float>(rows_g * D);
-    float* x2 = c.arena.get<float>(rows_g * D);
-    float* h = c.arena.get<float>(rows_g * D);
-    float* qkv = c.arena.get<float>(rows_g * 3 * D);
-    float* m1 = c.arena.get<float>(rows_g * 4 * D);
-    float* Q = c.arena.get<float>((size_t)Bg * H * R * 64);
-    float* tk = c.arena.get<float>(kv_g);   // exact fp32 K / V of the group's rows, padded to the attention's key tile (rows R .. Rpad stay zero)
-    float* tv = c.arena.get<float>(kv_g);
-    float* bias = c.arena.get<float>((size_t)Hk * R * Rpad);
-    uint16_t* tiles = c.arena.get<uint16_t>(attn_tiles_elems(Hk, R, Rpad));
-    float* hn = c.arena.get<float>((size_t)CH * D);
-    float* ltile = logits ? nullptr : c.arena.get<float>((size_t)CH * V);
-    float* wnll = c.arena.get<float>((size_t)B * n);
+    float *x, *cx, *xn, *x2, *h, *qkv, *m1, *Q, *tk, *tv, *bias, *hn, *ltile, *wnll;
+    uint16_t* tiles;
+    c.arena.carve([&](Arena& a) {
+        (void)step_ws(c, a, B);   // the decode-step buffers keep their addresses at the start of the arena
+        x = a.get<float>((size_t)B * R * D);
+        cx = a.get<float>((size_t)B * K * D);
+        xn = a.get<float>(rows_g * D);
+        x2 = a.get<float>(rows_g * D);
+        h = a.get<float>(rows_g * D);
+        qkv = a.get<float>(rows_g * 3 * D);
+        m1 = a.get<float>(rows_g * 4 * D);
+        Q = a.get<float>((size_t)Bg * H * R * 64);
+        tk = a.get<float>(kv_g);   // exact fp32 K / V of the group's rows, padded to the attention's key tile (rows R .. Rpad stay zero)
+        tv = a.get<float>(kv_g);
+        bias = a.get<float>((size_t)Hk * R * Rpad);
+        tiles = a.get<uint16_t>(attn_tiles_elems(Hk, R, Rpad));
+        hn = a.get<float>((size_t)CH * D);
+        ltile = logits ? nullptr : a.get<float>((size_t)CH * V);
+        wnll = a.get<float>((size_t)B * n);
+    });
     HIP_CHECK(hipMemsetAsync(tk, 0, kv_g * sizeof(float), s));
     HIP_CHECK(hipMemsetAsync(tv, 0, kv_g * sizeof(float), s));
 

@@ -3,10 +3,7 @@
 #include <atomic>
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include <string>
-#include <stdexcept>
-#include <cstdio>
-#include <cstdarg>
+#include "error.h"
 
 namespace bevgen {
 
@@ -19,21 +16,7 @@ inline int device_slot() {
     return dev >= 0 && dev < kMaxDevices ? dev : 0;
 }
 
-// -------- error handling: C++ exceptions inside, translated to int codes at the C-ABI --------
-struct Error : std::runtime_error {
-    int code;
-    Error(int c, const std::string& m) : std::runtime_error(m), code(c) {}
-};
-
-[[noreturn]] inline void fail(int code, const char* fmt, ...) {
-    char buf[1024];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    throw Error(code, buf);
-}
-
+// -------- error handling: error.h (Error, fail, BG_REQUIRE); the HIP side of it here --------
 #define HIP_CHECK(expr)                                                                            \
     do {                                                                                           \
         hipError_t _e = (expr);                                                                    \
@@ -41,11 +24,6 @@ struct Error : std::runtime_error {
     } while (0)
 
 #define LAUNCH_CHECK() HIP_CHECK(hipGetLastError())
-
-#define BG_REQUIRE(cond, ...)                      \
-    do {                                           \
-        if (!(cond)) ::bevgen::fail(-1, __VA_ARGS__); \
-    } while (0)
 
 inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
 inline long round_up(long a, long b) { return (a + b - 1) / b * b; }

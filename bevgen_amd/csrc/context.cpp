@@ -15,13 +15,6 @@ void Arena::reserve(size_t bytes) {
     cap = bytes;
     off = 0;
 }
-void* Arena::alloc(size_t bytes) {
-    const size_t a = (off + 255) & ~size_t(255);
-    if (a + bytes > cap) fail(BEVGEN_ERR_INTERNAL, "workspace arena exhausted: need %zu more bytes (capacity %zu)", a + bytes - cap, cap);
-    off = a + bytes;
-    if (off > high) high = off;
-    return base + a;
-}
 void Arena::release() {
     if (base) (void)hipFree(base);
     base = nullptr;

@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "../../include/bevgen_hip.h"
+#include "arena.h"
 #include "common.h"
 #include "kernels.h"
 #include "profiler.h"
@@ -21,17 +22,6 @@ struct DevTensor {
     size_t bytes = 0;
     long numel() const { long n = 1; for (auto d : shape) n *= d; return n; }
     const float* f() const { return reinterpret_cast<const float*>(ptr); }
-};
-
-// Bump allocator over one device slab: workspace of a call is carved from it, nothing is allocated on the sampling path.
-struct Arena {
-    char* base = nullptr;
-    size_t cap = 0, off = 0, high = 0;
-    void reserve(size_t bytes);
-    void reset() { off = 0; }
-    void* alloc(size_t bytes);
-    template <class T> T* get(size_t count) { return reinterpret_cast<T*>(alloc(count * sizeof(T))); }
-    void release();
 };
 
 struct MuseLayer {

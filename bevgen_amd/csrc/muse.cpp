@@ -21,7 +21,9 @@ struct MuseWs {
 
     long rows = 0;
     float *img = nullptr, *c_embed = nullptr, *context = nullptr;
+    int64_t* cond_g = nullptr; float* c_embed_g = nullptr;   // S > 1: the first scene of every group as contiguous [G, ...] inputs of the condition side
     std::vector<float*> crossK, crossV;
+    float *logits = nullptr, *scores = nullptr;   // generate only
     float *x = nullptr, *xn = nullptr, *qraw = nullptr, *kvraw = nullptr, *Q = nullptr, *Ks = nullptr, *Vs = nullptr, *att = nullptr, *h = nullptr, *g = nullptr;
     float* attn_ws = nullptr; int attn_ks = 1;   // key-split self-attention of the low-latency path (pick_attn_ksplit): partial rows of the key ranges
     float* kpart = nullptr;   // split-K partial tiles of the narrow (N = D) projections when the batch is too small to fill the chip (low-latency path)
@@ -79,28 +81,6 @@ int pick_attn_ksplit(long blocks, int ntiles) {
     if (blocks * 2 > 256) return 1;
     const int ks = std::min(std::min(4, (int)(256 / blocks)), ntiles / 8);
     return std::max(ks, 1);
-}
-
-size_t muse_ws_bytes(const Ctx& c, int B) {
-    const size_t rows = (size_t)B * c.N;
-    const size_t crows = (size_t)B * c.K;
-    size_t f = 0;
-    f += rows * c.D * 2;                 // img, x
-    f += (size_t)B * c.cfg.num_cams * c.D + crows * c.D;
-    f += (size_t)c.cfg.num_layers * 2 * B * c.H * c.NkC_pad * 64 + (size_t)B * c.K * 2 + (size_t)B * c.cfg.num_cams * c.D;
-    f += rows * c.D * 3;                 // xn, qraw, att
-    f += std::max(rows, crows) * 2 * c.D; // kvraw
-    f += rows * c.D;                     // Q
-    f += (size_t)2 * B * c.H * c.NkS_pad * 64;
-    f += rows * 2 * c.F + rows * c.Fpad;
-    f += rows * (c.V + 1);               // logits, scores (generate)
-    if (std::max(pick_ksplit((long)rows, c.D, c.D), pick_ksplit((long)rows, c.D, c.Fpad)) > 1) f += (size_t)KSPLIT_MAX * rows * c.D;
-    {
-        const int ks = pick_attn_ksplit((long)cdiv(c.N, 256) * c.H * B, c.NkS_pad / 32);
-        if (ks > 1) f += (size_t)attn_split_ws_floats(B, c.H, c.N, ks);
-    }   // split-K partial tiles (small batches only)
-    f += rows * (size_t)(2 * (c.D / 32) + 2 * (c.Fpad / 32) + 4);   // folded-LayerNorm row statistics
-    return f * sizeof(float) + (64 + 4 * c.cfg.num_layers) * 256 + (rows <= kSkMaxRows ? gemm_sk_ws_bytes() + 256 : 0);
 }
 
 void gemm(const float* A, int lda, const float* W, int ldb, float* C, int ldc, int M, int N, int K, const float* R, int ldr, hipStream_t s) {
@@ -170,20 +150,10 @@ void set_sk(GemmArgs& g, MuseWs* w) {
     g.sk_epoch = ++w->sk_epoch;
 }
 
-// per-batch constants: embeddings + cross-attention K/V
-void muse_prepare(Ctx& c, MuseWs& w, const int64_t* cond, const float* I_inv, const float* E_inv, int B, hipStream_t s, int samples_per_layout = 1) {
+// The workspace of a Route M call (w.B, w.S and w.rows set): the one description of it, run twice by Arena::carve (the rule is in arena.h)
+void muse_layout(const Ctx& c, MuseWs& w, Arena& a, bool generate) {
     const auto& g = c.cfg;
-    const std::string p = "transformer.";
-    const int S = samples_per_layout < 1 ? 1 : samples_per_layout;
-    BG_REQUIRE(B % S == 0, "batch %d is not a multiple of samples_per_layout %d", B, S);
-    const int G = B / S;   // BEV layouts: the condition side (context embedding, cross-attention K / V of every layer) is built once per layout
-    w.S = S;
-    w.B = B;
-    w.rows = (long)B * c.N;
-    Arena& a = c.arena;
-    a.reserve(muse_ws_bytes(c, B));
-    a.reset();
-    const int D = c.D, H = c.H;
+    const int D = c.D, H = c.H, B = w.B, G = B / w.S;
     w.img = g.image_embed ? a.get<float>((size_t)w.rows * D) : nullptr;
     w.c_embed = g.image_embed ? a.get<float>((size_t)B * g.num_cams * D) : nullptr;
     w.context = a.get<float>((size_t)G * c.K * D);
@@ -204,9 +174,34 @@ void muse_prepare(Ctx& c, MuseWs& w, const int64_t* cond, const float* I_inv, co
     w.stats_d = a.get<float>((size_t)w.rows * 2 * (D / 32));
     w.stats_f = a.get<float>((size_t)w.rows * 2 * (c.Fpad / 32));
     w.rowstat = a.get<float>((size_t)w.rows * 2);
-    w.sk_ws = nullptr;
-    if (w.rows <= kSkMaxRows && g.precision == BEVGEN_PRECISION_F16X3) {
-        w.sk_ws = a.alloc(gemm_sk_ws_bytes());
+    w.sk_ws = w.rows <= kSkMaxRows && g.precision == BEVGEN_PRECISION_F16X3 ? a.alloc(gemm_sk_ws_bytes()) : nullptr;
+    w.cond_g = w.S > 1 ? a.get<int64_t>((size_t)G * c.K) : nullptr;
+    w.c_embed_g = w.S > 1 && g.image_embed ? a.get<float>((size_t)G * g.num_cams * D) : nullptr;
+    const size_t kvC = (size_t)G * H * c.NkC_pad * 64;
+    w.crossK.resize(g.num_layers);
+    w.crossV.resize(g.num_layers);
+    for (int i = 0; i < g.num_layers; ++i) {
+        w.crossK[i] = a.get<float>(kvC);
+        w.crossV[i] = a.get<float>(kvC);
+    }
+    w.logits = generate ? a.get<float>((size_t)w.rows * c.V) : nullptr;
+    w.scores = generate ? a.get<float>((size_t)w.rows) : nullptr;
+}
+
+// per-batch constants: embeddings + cross-attention K/V
+void muse_prepare(Ctx& c, MuseWs& w, const int64_t* cond, const float* I_inv, const float* E_inv, int B, hipStream_t s, int samples_per_layout = 1, bool generate = false) {
+    const auto& g = c.cfg;
+    const std::string p = "transformer.";
+    const int S = samples_per_layout < 1 ? 1 : samples_per_layout;
+    BG_REQUIRE(B % S == 0, "batch %d is not a multiple of samples_per_layout %d", B, S);
+    const int G = B / S;   // BEV layouts: the condition side (context embedding, cross-attention K / V of every layer) is built once per layout
+    w.S = S;
+    w.B = B;
+    w.rows = (long)B * c.N;
+    c.arena.carve([&](Arena& a) { muse_layout(c, w, a, generate); });
+    const int D = c.D, H = c.H;
+    const size_t kvS = (size_t)B * H * c.NkS_pad * 64;
+    if (w.sk_ws) {
         HIP_CHECK(hipMemsetAsync(w.sk_ws, 0, 1024 * sizeof(unsigned), s));   // the flag words: a flag equal to a launch's epoch means "published in this launch"
         w.sk_epoch = 0;
     }
@@ -218,13 +213,11 @@ void muse_prepare(Ctx& c, MuseWs& w, const int64_t* cond, const float* I_inv, co
     const int64_t* cond_g = cond;
     const float* c_embed_g = w.c_embed;
     if (S > 1) {   // the first scene of every group -> contiguous [G, ...] inputs of the condition side
-        int64_t* cg = a.get<int64_t>((size_t)G * c.K);
-        HIP_CHECK(hipMemcpy2DAsync(cg, (size_t)c.K * 8, cond, (size_t)S * c.K * 8, (size_t)c.K * 8, G, hipMemcpyDeviceToDevice, s));
-        cond_g = cg;
+        HIP_CHECK(hipMemcpy2DAsync(w.cond_g, (size_t)c.K * 8, cond, (size_t)S * c.K * 8, (size_t)c.K * 8, G, hipMemcpyDeviceToDevice, s));
+        cond_g = w.cond_g;
         if (w.c_embed) {
-            float* eg = a.get<float>((size_t)G * g.num_cams * D);
-            HIP_CHECK(hipMemcpy2DAsync(eg, (size_t)g.num_cams * D * 4, w.c_embed, (size_t)S * g.num_cams * D * 4, (size_t)g.num_cams * D * 4, G, hipMemcpyDeviceToDevice, s));
-            c_embed_g = eg;
+            HIP_CHECK(hipMemcpy2DAsync(w.c_embed_g, (size_t)g.num_cams * D * 4, w.c_embed, (size_t)S * g.num_cams * D * 4, (size_t)g.num_cams * D * 4, G, hipMemcpyDeviceToDevice, s));
+            c_embed_g = w.c_embed_g;
         }
     }
     launch_cond_embed(cond_g, c.pf(p + "cond_token_emb.weight"), c.pf(p + "cond_pos_emb.weight"), g.bev_embed ? c.pf(p + "bev_grid") : nullptr,
@@ -233,11 +226,7 @@ void muse_prepare(Ctx& c, MuseWs& w, const int64_t* cond, const float* I_inv, co
 
     // cross-attention keys/values: to_kv(context) (context is NOT layer-normed, muse_net:128-132), null kv prepended, k l2-normalised
     const size_t kvC = (size_t)G * H * c.NkC_pad * 64;
-    w.crossK.resize(g.num_layers);
-    w.crossV.resize(g.num_layers);
     for (int i = 0; i < g.num_layers; ++i) {
-        w.crossK[i] = a.get<float>(kvC);
-        w.crossV[i] = a.get<float>(kvC);
         HIP_CHECK(hipMemsetAsync(w.crossK[i], 0, kvC * sizeof(float), s));
         HIP_CHECK(hipMemsetAsync(w.crossV[i], 0, kvC * sizeof(float), s));
         const MuseLayer& l = c.muse[i];
@@ -442,12 +431,11 @@ void maskgit_generate(Ctx& c, const int64_t* cond, const float* I_inv, const flo
     BG_REQUIRE(score_mode != 0 || c.find("token_critic.to_pred.weight"), "maskgit_generate: the context holds no token critic (token_critic.to_pred.*): use score_mode 1 / 2");
     BG_REQUIRE(score_mode >= 0 && score_mode <= 2, "score_mode %d: 0 token critic, 1 softmax confidence, 2 softmax confidence with re-masking of earlier tokens", score_mode);
     MuseWs w;
-    muse_prepare(c, w, cond, I_inv, E_inv, B, s, samples_per_layout);
+    muse_prepare(c, w, cond, I_inv, E_inv, B, s, samples_per_layout, true);
     const int rows = (int)w.rows;            // B*C*T token rows
     const int seqs = B * c.cfg.num_cams;     // rows of the [B*C, T] id matrix
     const int T = c.T, V = c.V, D = c.D;
-    float* logits = c.arena.get<float>((size_t)rows * V);
-    float* scores = c.arena.get<float>((size_t)rows);
+    float *logits = w.logits, *scores = w.scores;
     const int64_t mask_id = c.cfg.vocab_size;
     int64_t* ids = out;  // generation happens in the caller's output buffer
     launch_fill_i64(ids, rows, mask_id, s);

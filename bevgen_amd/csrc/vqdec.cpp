@@ -100,6 +100,7 @@ struct DecWs {
     float* stats;       // [n*32*2]
     void* gn_ws;
     float *q, *k, *vT, *S;
+    float *o, *zq, *img, *dots, *zz;   // third rotating activation buffer; latents; decode: pixel staging / encode: codebook products and row norms
     GnPart part;        // epilogue partials of the most recent convolution output (buf: groupnorm_part_floats of the widest level, or null)
     RangeSites* range = nullptr;   // non-null: range-safe mode
 };
@@ -310,11 +311,23 @@ void vq_decode(Ctx& c, const int64_t* ids, const float* latents_nchw, int n_tota
     const int chunk_max = 48;
     const int attn_c = max_c;
     const int chunk = std::min(n_total, chunk_max);
-    const size_t act_b = (size_t)per_img * chunk * sizeof(float);
-    const size_t need = 4 * act_b + act_b / 64 + (size_t)chunk * 64 * sizeof(float) + groupnorm_ws_bytes(chunk, RH * RW) +
-                        (size_t)chunk * attn_hwp * (3 * attn_c + attn_hwp) * sizeof(float) + (size_t)chunk * lat_hw * g.vq_embed_dim * sizeof(float) +
-                        (size_t)chunk * RH * RW * 4 * sizeof(float) + 34 * 256;
-    c.arena.reserve(need);
+    // the workspace of a pass over n images (a layout function, arena.h): metered for the largest pass, carved per pass
+    auto layout = [&](Arena& a, DecWs& ws, int n) {
+        if (planes) ws.part.buf = a.get<float>((size_t)per_img * n / 64 + 64);   // GroupNorm partials of one tensor: (pixels / 32) x (channels / 4) x 2
+        ws.a = a.get<float>((size_t)per_img * n);
+        ws.b = a.get<float>((size_t)per_img * n);
+        ws.t = a.get<float>((size_t)per_img * n);
+        ws.stats = a.get<float>((size_t)n * 64);
+        ws.gn_ws = a.alloc(groupnorm_ws_bytes(n, RH * RW));
+        ws.q = a.get<float>((size_t)n * attn_hwp * attn_c);
+        ws.k = a.get<float>((size_t)n * attn_hwp * attn_c);
+        ws.vT = a.get<float>((size_t)n * attn_hwp * attn_c);
+        ws.S = a.get<float>((size_t)n * attn_hwp * attn_hwp);
+        ws.zq = a.get<float>((size_t)n * lat_hw * g.vq_embed_dim);
+        ws.img = a.get<float>((size_t)n * RH * RW * 4);
+        ws.o = a.get<float>((size_t)per_img * n);
+    };
+    c.arena.reserve(Arena::measure([&](Arena& a) { DecWs ws; layout(a, ws, chunk); }));
     RangeSites sites;
     c.vq_range_used = 0;
     if (planes && g.vq_range) {
@@ -336,18 +349,8 @@ void vq_decode(Ctx& c, const int64_t* ids, const float* latents_nchw, int n_tota
         c.arena.reset();
         DecWs ws;
         if (sites.cap) ws.range = &sites;
-        if (planes) ws.part.buf = c.arena.get<float>((size_t)per_img * n / 64 + 64);   // GroupNorm partials of one tensor: (pixels / 32) x (channels / 4) x 2
-        ws.a = c.arena.get<float>((size_t)per_img * n);
-        ws.b = c.arena.get<float>((size_t)per_img * n);
-        ws.t = c.arena.get<float>((size_t)per_img * n);
-        ws.stats = c.arena.get<float>((size_t)n * 64);
-        ws.gn_ws = c.arena.alloc(groupnorm_ws_bytes(n, RH * RW));
-        ws.q = c.arena.get<float>((size_t)n * attn_hwp * attn_c);
-        ws.k = c.arena.get<float>((size_t)n * attn_hwp * attn_c);
-        ws.vT = c.arena.get<float>((size_t)n * attn_hwp * attn_c);
-        ws.S = c.arena.get<float>((size_t)n * attn_hwp * attn_hwp);
-        float* zq = c.arena.get<float>((size_t)n * lat_hw * g.vq_embed_dim);
-        float* img = c.arena.get<float>((size_t)n * RH * RW * 4);
+        layout(c.arena, ws, n);
+        float *zq = ws.zq, *img = ws.img;
 
         const long lrows = (long)n * lat_hw;
         if (ids) launch_codebook_gather(ids + (long)i0 * lat_hw, c.codebook, zq, (int)lrows, g.vq_embed_dim, g.vq_n_embed, s);
@@ -358,7 +361,7 @@ void vq_decode(Ctx& c, const int64_t* ids, const float* latents_nchw, int n_tota
         else conv3(x, c.conv_in, ws.a, nullptr, 0, s, false, &ws.part);          // conv_in
         x = Act{ws.a, n, lat_h, lat_w, c.conv_in.cout};
         // three rotating activation buffers (input / scratch / output of a block) + ws.t for the normalised tensor
-        float* o = c.arena.get<float>((size_t)per_img * n);
+        float* o = ws.o;
         auto res_step = [&](const ResBlockW& r) {
             // buffers: x.p in {a,b,o}; pick scratch and y as the two others
             float* bufs[3] = {ws.a, ws.b, o};
@@ -509,28 +512,30 @@ void vq_encode(Ctx& c, const float* x_nchw, int n_total, int RH, int RW, int64_t
     }
     const int chunk = std::min(n_total, 48);
     const long attn_hwp = round_up(attn_hw, 32);
-    const size_t act_b = (size_t)per_img * chunk * sizeof(float);
-    const size_t need = 4 * act_b + (size_t)chunk * 64 * sizeof(float) + groupnorm_ws_bytes(chunk, RH * RW) +
-                        (size_t)chunk * attn_hwp * (3 * max_c + attn_hwp) * sizeof(float) + (size_t)chunk * lat_hw * (g.vq_n_embed + g.vq_embed_dim + 1) * sizeof(float) + 32 * 256;
-    c.arena.reserve(need);
+    // the workspace of a pass over n images (a layout function, arena.h): metered for the largest pass, carved per pass
+    auto layout = [&](Arena& a, DecWs& ws, int n) {
+        ws.a = a.get<float>((size_t)per_img * n);
+        ws.b = a.get<float>((size_t)per_img * n);
+        ws.t = a.get<float>((size_t)per_img * n);
+        ws.o = a.get<float>((size_t)per_img * n);
+        ws.stats = a.get<float>((size_t)n * 64);
+        ws.gn_ws = a.alloc(groupnorm_ws_bytes(n, RH * RW));
+        ws.q = a.get<float>((size_t)n * attn_hwp * max_c);
+        ws.k = a.get<float>((size_t)n * attn_hwp * max_c);
+        ws.vT = a.get<float>((size_t)n * attn_hwp * max_c);
+        ws.S = a.get<float>((size_t)n * attn_hwp * attn_hwp);
+        ws.dots = a.get<float>((size_t)n * lat_hw * g.vq_n_embed);
+        ws.zq = a.get<float>((size_t)n * lat_hw * g.vq_embed_dim);
+        ws.zz = a.get<float>((size_t)n * lat_hw);
+    };
+    c.arena.reserve(Arena::measure([&](Arena& a) { DecWs ws; layout(a, ws, chunk); }));
     for (int i0 = 0; i0 < n_total; i0 += chunk) {
         const int n = std::min(chunk, n_total - i0);
         c.arena.reset();
         DecWs ws;
-        ws.a = c.arena.get<float>((size_t)per_img * n);
-        ws.b = c.arena.get<float>((size_t)per_img * n);
-        ws.t = c.arena.get<float>((size_t)per_img * n);
-        float* o = c.arena.get<float>((size_t)per_img * n);
-        ws.stats = c.arena.get<float>((size_t)n * 64);
-        ws.gn_ws = c.arena.alloc(groupnorm_ws_bytes(n, RH * RW));
-        ws.q = c.arena.get<float>((size_t)n * attn_hwp * max_c);
-        ws.k = c.arena.get<float>((size_t)n * attn_hwp * max_c);
-        ws.vT = c.arena.get<float>((size_t)n * attn_hwp * max_c);
-        ws.S = c.arena.get<float>((size_t)n * attn_hwp * attn_hwp);
+        layout(c.arena, ws, n);
         const long lrows = (long)n * lat_hw;
-        float* dots = c.arena.get<float>((size_t)lrows * g.vq_n_embed);
-        float* zq = c.arena.get<float>((size_t)lrows * g.vq_embed_dim);
-        float* zz = c.arena.get<float>((size_t)lrows);
+        float *o = ws.o, *dots = ws.dots, *zq = ws.zq, *zz = ws.zz;
 
         launch_nchw_to_nhwc_pad(x_nchw + (long)i0 * g.vq_in_channels * RH * RW, ws.t, n, RH * RW, g.vq_in_channels, c.enc_cin_pad, s);
         Act x{ws.t, n, RH, RW, c.enc_cin_pad};
@@ -581,15 +586,23 @@ struct OpWeights {
     std::vector<const float*> keys;
     OpWeights(Ctx& c_, hipStream_t s_) : c(c_), s(s_) {}
     ~OpWeights() { for (const float* k : keys) c.split.erase(k); }
-    static size_t bytes(int cout, int cin, int k) { return 2 * ((size_t)cout * cin * k * k * sizeof(float) + 256); }
-    ConvW conv(const float* w_oihw, const float* b, int cout, int cin, int k) {
+    struct Buf { float* w; void* planes; };
+    // the layout half of conv(): the re-laid-out weight and, in split-precision mode, its planes
+    static Buf take(const Ctx& c, Arena& a, int cout, int cin, int k) {
+        const size_t n = (size_t)cout * cin * k * k;
+        Buf b;
+        b.w = a.get<float>(n);
+        b.planes = c.cfg.precision == BEVGEN_PRECISION_F16X3 ? a.alloc(n * 4) : nullptr;
+        return b;
+    }
+    ConvW conv(Buf buf, const float* w_oihw, const float* b, int cout, int cin, int k) {
         ConvW cw;
         cw.cout = cout; cw.cin = cin; cw.k = k; cw.b = b;
         const long n = (long)cout * cin * k * k;
-        cw.w = c.arena.get<float>((size_t)n);
+        cw.w = buf.w;
         launch_relayout_conv_weight(w_oihw, cw.w, cout, cin, k, k, s);
         if (c.cfg.precision == BEVGEN_PRECISION_F16X3) {
-            void* planes = c.arena.alloc((size_t)n * 4);
+            void* planes = buf.planes;
             const bool w16 = c.cfg.weight_dtype == BEVGEN_W_F16;
             if (w16) launch_round_to_f16(cw.w, nullptr, n, s);
             launch_split_weight(cw.w, planes, n, s);
@@ -605,10 +618,10 @@ struct OpWeights {
 void vq_op_conv3x3_down(Ctx& c, const float* x, const float* w, const float* bias, float* y, int n, int H, int W, int Cin, int Cout, hipStream_t s) {
     BG_REQUIRE(n >= 1 && H >= 2 && W >= 2 && H % 2 == 0 && W % 2 == 0 && Cin >= 32 && Cin % 32 == 0 && Cout >= 1,
                "op_conv3x3_down: needs even H, W and Cin %% 32 == 0 (H=%d W=%d Cin=%d)", H, W, Cin);
-    c.arena.reserve(OpWeights::bytes(Cout, Cin, 3) + 4096);
-    c.arena.reset();
+    OpWeights::Buf wb;
+    c.arena.carve([&](Arena& a) { wb = OpWeights::take(c, a, Cout, Cin, 3); });
     OpWeights ow(c, s);
-    const ConvW cw = ow.conv(w, bias, Cout, Cin, 3);
+    const ConvW cw = ow.conv(wb, w, bias, Cout, Cin, 3);
     conv3_down(Act{const_cast<float*>(x), n, H, W, Cin}, cw, y, s);
 }
 
@@ -619,20 +632,22 @@ void vq_op_attn_block(Ctx& c, const float* x, const float* norm_w, const float* 
     const long hw = (long)h * w, hwp = round_up(hw, 32);
     const size_t f = sizeof(float);
     const size_t qb = (size_t)n * hwp * C * f, sb = (size_t)n * hwp * hwp * f;
-    c.arena.reserve(4 * OpWeights::bytes(C, C, 1) + (size_t)n * hw * C * f + (size_t)n * 64 * f + groupnorm_ws_bytes(n, (int)hw) + 3 * qb + sb + 16 * 256);
-    c.arena.reset();
+    OpWeights::Buf wb[4];
+    DecWs ws{};
+    c.arena.carve([&](Arena& ar) {
+        for (OpWeights::Buf& b : wb) b = OpWeights::take(c, ar, C, C, 1);
+        ws.t = ar.get<float>((size_t)n * hw * C);
+        ws.stats = ar.get<float>((size_t)n * 64);
+        ws.gn_ws = ar.alloc(groupnorm_ws_bytes(n, (int)hw));
+        ws.q = ar.get<float>(qb / f);
+        ws.k = ar.get<float>(qb / f);
+        ws.vT = ar.get<float>(qb / f);
+        ws.S = ar.get<float>(sb / f);
+    });
     OpWeights ow(c, s);
     AttnBlockW a;
     a.nw = norm_w; a.nb = norm_b; a.c = C;
-    a.q = ow.conv(wq, bq, C, C, 1); a.k = ow.conv(wk, bk, C, C, 1); a.v = ow.conv(wv, bv, C, C, 1); a.proj = ow.conv(wp, bp, C, C, 1);
-    DecWs ws{};
-    ws.t = c.arena.get<float>((size_t)n * hw * C);
-    ws.stats = c.arena.get<float>((size_t)n * 64);
-    ws.gn_ws = c.arena.alloc(groupnorm_ws_bytes(n, (int)hw));
-    ws.q = c.arena.get<float>(qb / f);
-    ws.k = c.arena.get<float>(qb / f);
-    ws.vT = c.arena.get<float>(qb / f);
-    ws.S = c.arena.get<float>(sb / f);
+    a.q = ow.conv(wb[0], wq, bq, C, C, 1); a.k = ow.conv(wb[1], wk, bk, C, C, 1); a.v = ow.conv(wb[2], wv, bv, C, C, 1); a.proj = ow.conv(wb[3], wp, bp, C, C, 1);
     // the model's workspace holds whatever the previous kernels left there: NaN bit patterns here, so that a pad column that is read without having been written shows
     HIP_CHECK(hipMemsetAsync(ws.q, 0xFF, qb, s));
     HIP_CHECK(hipMemsetAsync(ws.k, 0xFF, qb, s));
@@ -649,26 +664,28 @@ void vq_op_out_tail(Ctx& c, const float* x, const float* norm_w, const float* no
     BG_REQUIRE(out_mode >= 0 && out_mode <= 2 && (out_mode == 0 || (mean && stdv)), "op_vq_out_tail: out_mode 0 / 1 / 2; 1 and 2 need mean and std");
     const bool planes = c.cfg.precision == BEVGEN_PRECISION_F16X3;
     const long hw = (long)H * W;
-    const size_t f = sizeof(float);
-    c.arena.reserve(OpWeights::bytes(cout, C, 3) + (size_t)n * hw * C * f + (size_t)n * 64 * f + groupnorm_ws_bytes(n, (int)hw) + (size_t)n * hw * 4 * f + 8 * 256);
-    c.arena.reset();
-    OpWeights ow(c, s);
-    const ConvW co = ow.conv(w, bias, cout, C, 3);
+    OpWeights::Buf wb;
     DecWs ws{};
-    ws.t = c.arena.get<float>((size_t)n * hw * C);
-    ws.stats = c.arena.get<float>((size_t)n * 64);
-    ws.gn_ws = c.arena.alloc(groupnorm_ws_bytes(n, (int)hw));
-    float* img = c.arena.get<float>((size_t)n * hw * 4);
-    out_tail(Act{const_cast<float*>(x), n, H, W, C}, norm_w, norm_b, co, mean, stdv, out_mode, three_kernels == 0, out, img, ws, planes, s);
+    c.arena.carve([&](Arena& a) {
+        wb = OpWeights::take(c, a, cout, C, 3);
+        ws.t = a.get<float>((size_t)n * hw * C);
+        ws.stats = a.get<float>((size_t)n * 64);
+        ws.gn_ws = a.alloc(groupnorm_ws_bytes(n, (int)hw));
+        ws.img = a.get<float>((size_t)n * hw * 4);
+    });
+    OpWeights ow(c, s);
+    const ConvW co = ow.conv(wb, w, bias, cout, C, 3);
+    out_tail(Act{const_cast<float*>(x), n, H, W, C}, norm_w, norm_b, co, mean, stdv, out_mode, three_kernels == 0, out, ws.img, ws, planes, s);
 }
 
 void vq_op_quantize(Ctx& c, const float* z, const float* codebook, int64_t* ids, float* zz_out, float* ee_out, long rows, int n_e, int D, hipStream_t s) {
     BG_REQUIRE(rows >= 1 && rows <= 0x7FFFFFFFL && n_e >= 1 && D >= 32 && D % 32 == 0, "op_vq_quantize: needs D %% 32 == 0 (rows=%ld n_e=%d D=%d)", rows, n_e, D);
-    c.arena.reserve(((size_t)rows * n_e + (size_t)rows + (size_t)n_e) * sizeof(float) + 8 * 256);
-    c.arena.reset();
-    float* dots = c.arena.get<float>((size_t)rows * n_e);
-    float* zz = c.arena.get<float>((size_t)rows);
-    float* ee = c.arena.get<float>((size_t)n_e);
+    float *dots, *zz, *ee;
+    c.arena.carve([&](Arena& a) {
+        dots = a.get<float>((size_t)rows * n_e);
+        zz = a.get<float>((size_t)rows);
+        ee = a.get<float>((size_t)n_e);
+    });
     launch_row_sqnorm(codebook, ee, n_e, D, s);   // (the model: once, at finalize)
     quantize(z, codebook, ee, zz, dots, ids, rows, n_e, D, s);
     if (zz_out) HIP_CHECK(hipMemcpyAsync(zz_out, zz, (size_t)rows * sizeof(float), hipMemcpyDeviceToDevice, s));
@@ -682,14 +699,18 @@ void vq_op_conv3x3_gn_stats(Ctx& c, const float* x, const float* w, const float*
     const int hw = H * W, q4 = Cin >> 2;
     BG_REQUIRE(n >= 1 && H >= 1 && W >= 1 && Cin >= 32 && Cin % 32 == 0 && (q4 & (q4 - 1)) == 0 && bias, "op_conv3x3_gn_stats: needs a bias and Cin / 4 a power of two >= 8 (Cin=%d)", Cin);
     BG_REQUIRE(groupnorm_partials_supported(hw, Cout), "groupnorm from partials: unsupported shape hw=%d C=%d", hw, Cout);
-    c.arena.reserve(OpWeights::bytes(Cout, Cin, 3) + (size_t)n * hw * Cin * sizeof(float) + 4 * 256);
-    c.arena.reset();
+    OpWeights::Buf wbuf;
+    float* planes;
+    int* e;
+    c.arena.carve([&](Arena& a) {
+        wbuf = OpWeights::take(c, a, Cout, Cin, 3);
+        planes = a.get<float>((size_t)n * hw * Cin);
+        e = range_route ? a.get<int>(1) : nullptr;
+    });
     OpWeights ow(c, s);
-    ConvW cw = ow.conv(w, bias, Cout, Cin, 3);
-    float* planes = c.arena.get<float>((size_t)n * hw * Cin);
+    ConvW cw = ow.conv(wbuf, w, bias, Cout, Cin, 3);
     Act xp{planes, n, H, W, Cin};
     if (range_route) {   // the upsample site of the range-safe mode without the upsample, exponent 0: planes, the convolution without its bias, then bias + statistics in one pass
-        int* e = c.arena.get<int>(1);
         HIP_CHECK(hipMemsetAsync(e, 0, sizeof(int), s));
         launch_range_split(x, planes, (long)n * hw, Cin, e, s);
         ConvW wb = cw;
