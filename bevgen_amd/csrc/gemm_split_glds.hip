@@ -4,8 +4,15 @@
 //
 //   C[M,N] = (Ah + Al 2^-11)(Bh + Bl 2^-11)^T  ~=  Ah Bh^T + 2^-11 (Ah Bl^T + Al Bh^T)          (see gemm_split.hip for the numerics)
 //
-// * Block tile (WM*64) x 128 x 32: WM*2 waves, each a 64x64 patch = (2x2) v_mfma_f32_32x32x16_f16 tiles with a main and a correction
-//   accumulator.  WM = 4 (256x128, 8 waves = two per SIMD, one block per CU) is the production shape.
+// * Block tile (WM*64) x 128 x 32: WM*2 waves, each a 64x64 patch = (4x4) v_mfma_f32_16x16x32_f16 tiles with a main and a correction
+//   accumulator of 4 registers each (128 accumulator registers).  WM = 4 (256x128, 8 waves = two per SIMD, one block per CU) is the production shape.
+// * MFMA shape (BEVGEN_GEMM_MFMA16, compile time, default 1; 0 builds the v_mfma_f32_32x32x16_f16 loop, (2x2) tiles of 16 registers, from the same source).  The kernel
+//   runs at the chip's power cap, where wall time follows the clock the chip can hold rather than the issue stream, and it holds a higher one on the 16x16x32 shape at equal
+//   cycles per FLOP (MI355X guide, DVFS give-back).  Measured on one device, arms alternating, random data (profiles/r10_ab_gemm_mfma16.txt): [24576, 1024] x 1024
+//   141 -> 133 us, x 2048 262 -> 245 us, [24576, 5504] x 1024 725 -> 691 us, x 32 (three rounds of tiles, hardly any k loop) 29 -> 30 us: the price of the layout
+//   conversion below; sixteen-scene step 1426.8 -> 1398.2 ms.  The epilogues are unchanged: they were written for the 32x32 accumulator layout and the merged patch is
+//   converted to it through the dead stage ring first (see "layout conversion" in gemm_tile).  Results differ from the 32x32x16 build's in fp32 association only (one
+//   32-deep product per k-tile instead of two 16-deep ones).
 // * Operands live in HBM in the interleaved plane layout [row][k/32][hi 32 | lo 32] (gemm_split.hip): one (row, k-block) is one 128-byte
 //   line, so every DMA request is a whole line (with separate hi / lo planes each k-tile touched only half of every line it fetched and
 //   the L2->L1 fill traffic was twice the useful bytes - the measured limiter).
@@ -17,7 +24,9 @@
 //        top of k-tile t :  ds_read fragments F1 (k-step 1 of tile t)            | MFMAs on F0 (k-step 0, fetched during tile t-1)
 //        middle          :  lgkmcnt(0); vmcnt(tile t+1 landed); s_barrier        -- every wave is done READING tile t, tile t+1 is complete
 //        bottom          :  ds_read F0 of tile t+1; DMA of tile t+3 -> stage of t | MFMAs on F1, DMA pieces interleaved between MFMA groups
-//   so every ds_read is issued a full 12-MFMA phase before its use and every DMA two k-tiles before its use.
+//   so every ds_read is issued a full 12-MFMA phase before its use and every DMA two k-tiles before its use.  (That is the 32x32x16 loop, two k-steps per k-tile.  The
+//   16x16x32 loop has one k-step per k-tile and splits the phases by ROWS of the patch: all B fragments of the k-tile plus the A fragments of one row half, double buffered -
+//   64 fragment registers as before, 16 ds_read_b128 and 48 MFMAs per wave and k-tile; the B fragments of tile t+1 replace those of tile t group by group in the bottom phase.)
 // * MODE_CONV3: implicit-GEMM 3x3 convolution over NHWC planes; taps that fall into the zero padding are fetched from a zero page.
 // * MODE_CONV3S: the same for the common case (stride 1, padding 1, no fused upsample: every 3x3 convolution of the VQGAN decoder but the four behind an upsample).  The address
 //   of a tap is then the output pixel's own address plus a WAVE-UNIFORM displacement, and whether the tap lies inside the image is one bit of a 9-bit mask the lane forms once:
@@ -55,7 +64,12 @@ struct RowDiv {
     }
 };
 constexpr int GBN = 128, GBK = 32;
-#ifdef BEVGEN_GEMM_TRACE   // tools/gemm_trace: phase stamps (100 MHz clock) of the first 2048 workgroups of the LAST throughput launch: entry, first tile landed, loop done, epilogue issued, stores acknowledged
+// 1: the k loop issues v_mfma_f32_16x16x32_f16 (one MFMA per 16x16 tile and k-tile), 0: v_mfma_f32_32x32x16_f16 (two per 32x32 tile and k-tile).  Compile time only (csrc/Makefile
+// passes it): two loops per instantiation would double the compile time of the largest kernels.  See the header comment; measurements in profiles/r10_ab_gemm_mfma16.txt.
+#ifndef BEVGEN_GEMM_MFMA16
+#define BEVGEN_GEMM_MFMA16 1
+#endif
+#ifdef BEVGEN_GEMM_TRACE  // tools/gemm_trace: phase stamps (100 MHz clock) of the first 2048 workgroups of the LAST throughput launch: entry, first tile landed, loop done, epilogue issued, stores acknowledged
 __device__ unsigned long long g_gemm_trace[5 * 2048 * 8];   // [epilogue kind][workgroup][stamp]
 __device__ unsigned long long g_gemm_tr_tmp[2];
 #define GT_STAMP(i) do { if (MODE == MODE_PLAIN && !KS) gt[i] = __builtin_amdgcn_s_memrealtime(); } while (0)
@@ -125,10 +139,10 @@ __device__ __forceinline__ void gemm_tile(const GemmArgs& g, const int tx, const
     constexpr int STAGE_H = AREGION + GBN * 2 * GBK;  // halves per stage
     constexpr int DMA = NAJ + NBJ;                    // DMA wave-instructions per k-tile
     extern __shared__ __attribute__((aligned(1024))) _Float16 smem_g[];
-    const int lane = tid & 63;
+    int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = wave / WN, wn = wave % WN;
-    const int r = lane & 31, h = lane >> 5;
+    int r = lane & 31, h = lane >> 5;   // (lane, r, h: formed again behind the k loop in the 16x16x32 build, see there)
     const int n0 = tx * GBN, m0 = ty * TBM + g.m_base;
     const int n0l = n0, m0l = m0;
 
@@ -236,6 +250,61 @@ __device__ __forceinline__ void gemm_tile(const GemmArgs& g, const int tx, const
 #pragma unroll
             for (int q = 0; q < 16; ++q) { accM[i][j][q] = 0.f; accC[i][j][q] = 0.f; }
 
+#if BEVGEN_GEMM_MFMA16
+    // ---- 16x16x32 loop state.  The wave's patch is (2 TI) x (2 TJ) tiles of 16 x 16, each with a main and a correction accumulator of 4 registers (operands swapped, B
+    // fragment first: lane -> output row lane & 15 of the tile, register e -> column 4 (lane >> 4) + e).  One MFMA covers the whole 32-deep k-tile: lane l reads row
+    // base + (l & 15), logical 16-byte chunk l >> 4 (hi) / 4 + (l >> 4) (lo, at the hi address ^ 32 halves), physical chunk = logical ^ ((row >> 1) & 7) as the DMA wrote
+    // it.  A 16-lane service group of the ds_read_b128 is 16 consecutive rows of one logical chunk: 8 values of (row >> 1) & 7 = 8 physical chunks x 2 row parities = all
+    // 64 banks once.  Tiles are 16 rows apart, which leaves (row >> 1) & 7 alone: one address per operand and plane, the tile is a constant offset.
+    constexpr int NI = 2 * TI, NJ = 2 * TJ;
+    constexpr int T16 = 16 * 2 * GBK;   // halves between two 16-row tiles
+    f32x4 qM[NI][NJ], qC[NI][NJ];
+#pragma unroll
+    for (int i = 0; i < NI; ++i)
+#pragma unroll
+        for (int j = 0; j < NJ; ++j)
+#pragma unroll
+            for (int e = 0; e < 4; ++e) { qM[i][j][e] = 0.f; qC[i][j][e] = 0.f; }
+    const int r16 = lane & 15, c16 = lane >> 4;
+    const int a_rd = (wm * WROWS + r16) * 2 * GBK + ((c16 ^ (((wm * WROWS + r16) >> 1) & 7)) << 3);
+    const int b_rd = AREGION + (wn * WCOLS + r16) * 2 * GBK + ((c16 ^ (((wn * WCOLS + r16) >> 1) & 7)) << 3);
+    // Fragments: ALL B tiles of the k-tile (bh, bl) and the A tiles of one row half (TI tiles), double buffered: 64 registers for the 64x64 patch, as the two k-step
+    // sets of the 32x32x16 loop.
+    struct AFrag { half8 h[TI], l[TI]; };
+    half8 bh[NJ], bl[NJ];
+    auto fetch_a = [&](AFrag& f, int stage, int half) {
+        // (the lo address is formed from the hi address of THIS stage, one XOR in place of the stage add of a second per-lane register that would live through the loop;
+        // stage and tile offsets are multiples of 1024 halves)
+        const int hi = stage * STAGE_H + a_rd, lo = hi ^ 32;
+#pragma unroll
+        for (int i = 0; i < TI; ++i) {
+            f.h[i] = *reinterpret_cast<const half8*>(smem_g + hi + (half * TI + i) * T16);
+            f.l[i] = *reinterpret_cast<const half8*>(smem_g + lo + (half * TI + i) * T16);
+        }
+    };
+    auto fetch_b = [&](int stage, int jg) {   // column tiles [jg TJ, (jg + 1) TJ)
+        const int hi = stage * STAGE_H + b_rd, lo = hi ^ 32;
+#pragma unroll
+        for (int j = 0; j < TJ; ++j) {
+            bh[jg * TJ + j] = *reinterpret_cast<const half8*>(smem_g + hi + (jg * TJ + j) * T16);
+            if (!W16) bl[jg * TJ + j] = *reinterpret_cast<const half8*>(smem_g + lo + (jg * TJ + j) * T16);
+        }
+    };
+    // The products of row half `half` x column group jg.  Per output element and k-tile the order is main += (Bh, Ah); corr += (Bl, Ah); corr += (Bh, Al) - callers issue
+    // part 0, 1, 2 of a (half, jg) in that order, in every phase of the pipeline and in every instantiation (the bit-identity of the row-split / CONV3S launches).
+    auto mma = [&](const AFrag& a, int half, int jg, int part) {
+        if (part == 1 && W16) return;
+#pragma unroll
+        for (int jj = 0; jj < TJ; ++jj)
+#pragma unroll
+            for (int i = 0; i < TI; ++i) {
+                const int it = half * TI + i, j = jg * TJ + jj;
+                if (part == 0) qM[it][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(bh[j], a.h[i], qM[it][j], 0, 0, 0);
+                else if (part == 1) qC[it][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(bl[j], a.h[i], qC[it][j], 0, 0, 0);
+                else qC[it][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(bh[j], a.l[i], qC[it][j], 0, 0, 0);
+            }
+    };
+#else
     // operand fetch addresses (halves) inside a stage: row*64 + swizzled chunk*8; the lo chunk (logical +4) sits at the hi address ^ 32 halves
     int a_rd[2][2], b_rd[2][2];   // [tile i/j][k-step]
 #pragma unroll
@@ -280,6 +349,7 @@ __device__ __forceinline__ void gemm_tile(const GemmArgs& g, const int tx, const
 #pragma unroll
             for (int j = 0; j < TJ; ++j) accC[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(f.bh[j], f.al[i], accC[i][j], 0, 0, 0);
     };
+#endif
 
     // ---- prologue: tiles 0..S-1 in flight, tile 0 landed, F0 of tile 0 on its way
 #pragma unroll
@@ -333,8 +403,16 @@ __device__ __forceinline__ void gemm_tile(const GemmArgs& g, const int tx, const
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
     GT_STAMP(1);
+#if BEVGEN_GEMM_MFMA16
+    // (the first fragments are fetched at the head of EACH of the two paths below, behind a marker that keeps the compiler from merging the two copies: fetched once in
+    // front of the branch, the 48 registers land in one place and are copied to where each path's loop carries them, and that moment - both sets and the 128 accumulator
+    // zeros live - is the register peak of the kernel; the 256-row convolution instantiations spilled their DMA state into the loop over it)
+    AFrag fa0, fa1;
+    auto first_fetch = [&]() { fetch_b(0, 0); fetch_b(0, 1); fetch_a(fa0, 0, 0); };
+#else
     Frag f0, f1;
     fetch(f0, 0, 0);
+#endif
 
     // One k-tile.  WHERE selects the DMA work of this iteration at compile time (the steady-state loops below are branch free; a runtime
     // `if (more)` around every DMA piece costs ~10 %: each one ends a scheduling region in the middle of the MFMA stream):
@@ -373,6 +451,27 @@ __device__ __forceinline__ void gemm_tile(const GemmArgs& g, const int tx, const
         const int stage_next = stage == S - 1 ? 0 : stage + 1;
         const int stage_prev = stage == 0 ? S - 1 : stage - 1;
 #define BG_FENCE() __builtin_amdgcn_sched_barrier(0)   /* pin the hand-placed order: the machine scheduler otherwise sinks the ds_reads below the MFMAs */
+#if BEVGEN_GEMM_MFMA16
+        // 16x16x32 cut of the same pipeline (one k-tile = one MFMA per tile and product, so the phases split the ROWS of the patch, not the k-steps):
+        //   top    : ds_read A row half 1 of tile t                                         | MFMAs: row half 0 x all columns (A half 0 and B fetched during tile t-1)
+        //   middle : lgkmcnt(0); vmcnt; s_barrier, as before
+        //   bottom : ds_read A half 0 of tile t+1; B of tile t+1 group by group, each behind | MFMAs: row half 1, column group 0 then 1
+        //            the last MFMA that reads the registers it replaces; DMA as before
+        // Column group 1 of B is the last read of a k-tile and the top phase uses it last (12 MFMAs later for the 64x64 patch).
+        fetch_a(fa1, stage, 1);
+        BG_FENCE();
+        mma(fa0, 0, 0, 0);
+        mma(fa0, 0, 0, 1);
+        BG_FENCE();
+        if (WHERE == 2) { issue_a_half(stage_prev, 0); BG_FENCE(); }
+        mma(fa0, 0, 0, 2);
+        mma(fa0, 0, 1, 0);
+        BG_FENCE();
+        if (WHERE == 2) { issue_a_half(stage_prev, 1); BG_FENCE(); }
+        mma(fa0, 0, 1, 1);
+        mma(fa0, 0, 1, 2);
+        if (WHERE == 2) { BG_FENCE(); issue_b(stage_prev); }
+#else
         fetch(f1, stage, 1);
         BG_FENCE();
         mma_main(f0);
@@ -383,6 +482,7 @@ __device__ __forceinline__ void gemm_tile(const GemmArgs& g, const int tx, const
         if (WHERE == 2) { issue_a_half(stage_prev, 1); BG_FENCE(); }
         mma_c2(f0);
         if (WHERE == 2) { BG_FENCE(); issue_b(stage_prev); }
+#endif
         // this wave is done reading tile kt; tile kt+1 must be complete (own pieces; tiles kt+2 .. kt+S-1 may stay in flight).  The scheduling fences keep
         // the MFMAs of F0 above the waits (they are not memory operations, nothing else would stop them sinking below) and F1's below.
         __builtin_amdgcn_sched_barrier(0);
@@ -393,6 +493,27 @@ __device__ __forceinline__ void gemm_tile(const GemmArgs& g, const int tx, const
         __builtin_amdgcn_s_barrier();
         asm volatile("" ::: "memory");
         __builtin_amdgcn_sched_barrier(0);
+#if BEVGEN_GEMM_MFMA16
+        mma(fa1, 1, 0, 0);               // A half 1 landed before the barrier: the matrix pipe restarts at once
+        __builtin_amdgcn_sched_barrier(0);
+        fetch_a(fa0, stage_next, 0);     // unconditional (after the last tile these read a stale stage and are never used): keeps the wait counters exact
+        BG_FENCE();
+        if (WHERE == 1) { issue_a_half(stage, 0); BG_FENCE(); }
+        if (RPF && WHERE == 0 && rpf_pending) { issue_rpf(stage); rpf_pending = false; rpf_flight = true; BG_FENCE(); }
+        mma(fa1, 1, 0, 1);
+        mma(fa1, 1, 0, 2);
+        BG_FENCE();
+        fetch_b(stage_next, 0);
+        BG_FENCE();
+        if (WHERE == 1) { issue_a_half(stage, 1); BG_FENCE(); }
+        mma(fa1, 1, 1, 0);
+        mma(fa1, 1, 1, 1);
+        mma(fa1, 1, 1, 2);
+        BG_FENCE();
+        fetch_b(stage_next, 1);
+        BG_FENCE();
+        if (WHERE == 1) { issue_b(stage); BG_FENCE(); }
+#else
         mma_main(f1);                    // F1 landed before the barrier: the matrix pipe restarts at once
         __builtin_amdgcn_sched_barrier(0);
         fetch(f0, stage_next, 0);        // unconditional (after the last tile it reads a stale stage and is never used): keeps the wait counters exact
@@ -405,6 +526,7 @@ __device__ __forceinline__ void gemm_tile(const GemmArgs& g, const int tx, const
         mma_c2(f1);
         BG_FENCE();
         if (WHERE == 1) { issue_b(stage); BG_FENCE(); }
+#endif
 #undef BG_FENCE
         stage = stage_next;
     };
@@ -412,8 +534,16 @@ __device__ __forceinline__ void gemm_tile(const GemmArgs& g, const int tx, const
     const bool late = NW == 8 && wave >= NW / 2;   // staggering only matters when two waves of ONE block share a SIMD
     int kt = 0;
     if (!late) {
+#if BEVGEN_GEMM_MFMA16
+        asm volatile("; early waves" ::: "memory");
+        first_fetch();
+#endif
         for (; kt < nk - S; ++kt) body(integral_constant<int, 1>{}, integral_constant<bool, true>{}, kt);   // tiles kt+S <= nk-1 exist
     } else {
+#if BEVGEN_GEMM_MFMA16
+        asm volatile("; late waves" ::: "memory");
+        first_fetch();
+#endif
         if (nk > 0) { body(integral_constant<int, 0>{}, integral_constant<bool, false>{}, 0); kt = 1; }
         for (; kt <= nk - S; ++kt) body(integral_constant<int, 2>{}, integral_constant<bool, true>{}, kt);  // tiles kt+S-1 <= nk-1 exist
     }
@@ -436,6 +566,16 @@ __device__ __forceinline__ void gemm_tile(const GemmArgs& g, const int tx, const
         const long lane_off = (long)wave * (TI * TJ * 16 * 64) + lane * 4;
         if (sk_role == 1) {
             float* mine = ws + (long)blockIdx.x * SLOT + lane_off;
+#if BEVGEN_GEMM_MFMA16
+            // (the exchange runs in the 16x16 layout - slot = [wave][tile it][tile jt][lane][4], the same size - and the owner converts after it)
+#pragma unroll
+            for (int u = 0; u < NI * NJ; ++u) {
+                f32x4 v;
+#pragma unroll
+                for (int e = 0; e < 4; ++e) v[e] = qM[u / NJ][u % NJ][e] + qC[u / NJ][u % NJ][e] * kGLoInv;
+                *reinterpret_cast<f32x4*>(mine + u * 256) = v;
+            }
+#else
 #pragma unroll
             for (int i = 0; i < TI; ++i)
 #pragma unroll
@@ -447,6 +587,7 @@ __device__ __forceinline__ void gemm_tile(const GemmArgs& g, const int tx, const
                         for (int e = 0; e < 4; ++e) v[e] = accM[i][j][qq * 4 + e] + accC[i][j][qq * 4 + e] * kGLoInv;
                         *reinterpret_cast<f32x4*>(mine + ((i * TJ + j) * 4 + qq) * 256) = v;
                     }
+#endif
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // (every wave: its stores are acknowledged)
             __syncthreads();
             if (tid == 0) __hip_atomic_store(flags + blockIdx.x, g.sk_epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -464,12 +605,19 @@ __device__ __forceinline__ void gemm_tile(const GemmArgs& g, const int tx, const
         __syncthreads();
         // own sums first (main + correction accumulators merged: the correction registers are free from here on), then the contributors' added ONTO them from the nearest
         // k range down to the first - a fixed order; four register quads (4 KiB per wave) in flight at a time: the accumulators leave no room for more
+#if BEVGEN_GEMM_MFMA16
+#pragma unroll
+        for (int u = 0; u < NI * NJ; ++u)
+#pragma unroll
+            for (int e = 0; e < 4; ++e) { qM[u / NJ][u % NJ][e] += qC[u / NJ][u % NJ][e] * kGLoInv; qC[u / NJ][u % NJ][e] = 0.f; }
+#else
 #pragma unroll
         for (int i = 0; i < TI; ++i)
 #pragma unroll
             for (int j = 0; j < TJ; ++j)
 #pragma unroll
                 for (int q = 0; q < 16; ++q) { accM[i][j][q] += accC[i][j][q] * kGLoInv; accC[i][j][q] = 0.f; }
+#endif
         for (int w = (int)blockIdx.x - 8; w >= sk_first; w -= 8) {
             const float* theirs = ws + (long)w * SLOT + lane_off;
             // half of a contributor's slot in flight at a time (8 KiB per wave: two L2 round trips per contributor; four quads at a time made it sixteen, the whole slot
@@ -484,13 +632,66 @@ __device__ __forceinline__ void gemm_tile(const GemmArgs& g, const int tx, const
 #pragma unroll
                 for (int u = 0; u < HB; ++u) {
                     asm volatile("" : "+v"(pv[u]));   // (defined behind the wait)
-                    const int uu = u0 + u;            // = (i TJ + j) 4 + qq
+                    const int uu = u0 + u;            // = (i TJ + j) 4 + qq  (16x16 loop: it NJ + jt)
 #pragma unroll
+#if BEVGEN_GEMM_MFMA16
+                    for (int e = 0; e < 4; ++e) qM[uu / NJ][uu % NJ][e] += pv[u][e];
+#else
                     for (int e = 0; e < 4; ++e) accM[uu / (TJ * 4)][(uu / 4) % TJ][(uu & 3) * 4 + e] += pv[u][e];
+#endif
                 }
             }
         }
     }
+    constexpr int VT_LD = WROWS == 64 ? 72 : 40;          // transposed value stage: [64 columns][1 + WROWS tokens], padded (4 VT_LD = 32 mod 64 banks)
+    constexpr int RS = TJ == 2 ? 68 : 36;                 // row stride (floats) of the row-major stage
+    constexpr int SLICE_W = TJ == 2 ? (64 * VT_LD > WROWS * RS ? 64 * VT_LD : WROWS * RS) : WROWS * RS;   // words per wave (a tile may hold both kinds of waves: one size)
+    constexpr bool STG = MODE == MODE_PLAIN && !KS && !SKK && !(WM == 2 && S == 2) && (TI == 2 ? TJ == 2 : true) && (long)NW * SLICE_W * 4 <= (long)S * STAGE_H * 2;
+    float* const pl = reinterpret_cast<float*>(smem_g) + wave * SLICE_W;
+#if BEVGEN_GEMM_MFMA16
+    // The lane index is formed AGAIN here, from the hardware's lane counter: everything per-lane below (and every offset derived from it, loop-invariant for the k loop
+    // above and hoisted in front of it otherwise) then starts behind the loop instead of staying live through it - the throughput instantiations have no register for that.
+    lane = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+    r = lane & 31; h = lane >> 5;
+    // ---- layout conversion: everything below (the folded LayerNorm, every fused epilogue, the split-K partial store) was written for the 32x32 accumulator layout and
+    // begins with accM + accC 2^-11.  The merged patch goes through the wave's own slice of the dead stage ring - written from the 16x16 layout, read back in the 32x32
+    // layout, rows of RS floats: sixteen consecutive rows of one 16-byte column group in both directions, conflict-free - and comes back as accM with accC = 0, so the
+    // code below is unchanged (x + 0 c = x).  The ring is dead: every wave's last operand read of the last k-tile lies before that tile's barrier (the look-ahead fetches
+    // behind it are never used), that barrier's wait left no operand DMA in flight, and the residual prefetch lands in the sink behind the ring.  The staged epilogues
+    // below rely on exactly that and touch only the wave's own slice, which is this slice; the other instantiations get a barrier of their own.  Where the ring is smaller
+    // than the waves' whole patches (two-stage 128-row block) a 32-row half goes through at a time.
+    // Cost: 128 KB per 256x128 block written at the ds_write_b128 rate (~79 B/clk) and read at 256 B/clk, ~2100 clk = ~1.1 us per round of tiles.
+    {
+        constexpr bool CV_FULL = (long)NW * SLICE_W * 4 <= (long)S * STAGE_H * 2;
+        constexpr int CV_W = CV_FULL ? SLICE_W : 32 * RS;   // words per wave
+        static_assert((long)NW * CV_W * 4 <= (long)S * STAGE_H * 2, "the ring holds a 32-row half of every wave's patch");
+        static_assert(!STG || CV_FULL, "the staged epilogues' slice is the conversion's slice");
+        if constexpr (!STG) __syncthreads();
+        const int wr = (lane & 15) * RS + 4 * (lane >> 4), rd = r * RS + 4 * h;
+        float* const cv = reinterpret_cast<float*>(smem_g) + wave * CV_W;
+#pragma unroll
+        for (int i = 0; i < TI; ++i) {
+            float* const ch = cv + (CV_FULL ? i * 32 * RS : 0);
+#pragma unroll
+            for (int t = 0; t < 2; ++t)
+#pragma unroll
+                for (int j = 0; j < NJ; ++j) {
+                    f32x4 v;
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) v[e] = fmaf(qC[2 * i + t][j][e], kGLoInv, qM[2 * i + t][j][e]);
+                    *reinterpret_cast<f32x4*>(ch + wr + t * 16 * RS + j * 16) = v;
+                }
+#pragma unroll
+            for (int j = 0; j < TJ; ++j)
+#pragma unroll
+                for (int qq = 0; qq < 4; ++qq) {
+                    const f32x4 v = *reinterpret_cast<const f32x4*>(ch + rd + j * 32 + 8 * qq);
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) { accM[i][j][qq * 4 + e] = v[e]; accC[i][j][qq * 4 + e] = 0.f; }
+                }
+        }
+    }
+#endif
     // ---- folded LayerNorm, consumer side: LN(x) W^T = rstd (x (W o gamma)^T - mean cs) applied to the tile sums in place, so that every epilogue below sees the projection
     // of the normalised rows (it is linear in the sums: alpha, bias, activation and residual follow unchanged)
     if (MODE == MODE_PLAIN && (g.ln_in_stats || g.ln_in_gsums)) {
@@ -522,11 +723,7 @@ __device__ __forceinline__ void gemm_tile(const GemmArgs& g, const int tx, const
     // LayerNorm statistics) stays on the accumulator side, element for element as in the direct forms: results are bit-identical, only the store instructions change.
     // (Also the small-problem shapes - 32-row patches of the eight-wave / 64-row blocks, 32 x 32 patches with the plain epilogue - wherever the ring holds the slices; not
     // the two-stage 128-row block, whose 64 KB ring is smaller than its four slices.)
-    constexpr int VT_LD = WROWS == 64 ? 72 : 40;          // transposed value stage: [64 columns][1 + WROWS tokens], padded (4 VT_LD = 32 mod 64 banks)
-    constexpr int RS = TJ == 2 ? 68 : 36;                 // row stride (floats) of the row-major stage
-    constexpr int SLICE_W = TJ == 2 ? (64 * VT_LD > WROWS * RS ? 64 * VT_LD : WROWS * RS) : WROWS * RS;   // words per wave (a tile may hold both kinds of waves: one size)
-    constexpr bool STG = MODE == MODE_PLAIN && !KS && !SKK && !(WM == 2 && S == 2) && (TI == 2 ? TJ == 2 : true) && (long)NW * SLICE_W * 4 <= (long)S * STAGE_H * 2;
-    float* const pl = reinterpret_cast<float*>(smem_g) + wave * SLICE_W;
+    // (VT_LD, RS, SLICE_W, STG and the wave's slice pl: defined in front of the layout conversion above)
     // the row-major view of a 64-column patch: 8 lanes x 8 columns per row, 8 rows per pass
     const int rm_row = lane >> 3, rm_c8 = lane & 7;
     auto stage_read8 = [&](int row, f32x4& a0, f32x4& a1) {
