@@ -13,7 +13,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("BEVGEN_LIB_PATH") or os.path.join(_HERE, "csrc", "libbevgen_hip.so")   # override: A/B runs of two builds on one GPU box
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "bevgen_hip.h")
 
-ABI_VERSION = 9
+ABI_VERSION = 10
 ROUTE_MASKGIT, ROUTE_AR = 0, 1
 PRECISION_FP32, PRECISION_BF16, PRECISION_F16X3 = 0, 1, 2
 KV_F32, KV_F16 = 0, 1
@@ -99,6 +99,7 @@ SIGNATURES = {
     "bevgen_op_vq_out_tail": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _p, _i, _i, _i, _i, _p]),
     "bevgen_op_vq_quantize": (_i, [_p, _p, _p, _p, _p, _p, _l, _i, _i, _p]),
     "bevgen_op_conv3x3_gn_stats": (_i, [_p, _p, _p, _p, _i, _p, _p, _p, _i, _i, _i, _i, _i, _p]),
+    "bevgen_op_conv_ranged": (_i, [_p, _p, _p, _p, _i, _p, _p, _i, _i, _i, _i, _i, _p]),
     "bevgen_decode_attention_splits": (_i, [_i, _i, _i]),
     "bevgen_profile_begin": (_i, [_p]),
     "bevgen_profile_end": (_i, [_p, C.POINTER(C.c_double)]),

@@ -689,6 +689,14 @@ int bevgen_op_conv3x3_gn_stats(bevgen_ctx* ctx, const float* x, const float* w, 
     });
 }
 
+int bevgen_op_conv_ranged(bevgen_ctx* ctx, const float* x, const float* w, const float* bias, int kind, float* y, int32_t* d_exp, int n, int H, int W, int Cin, int Cout,
+                          void* stream) {
+    return guarded(ctx, [&] {
+        BG_REQUIRE(x && w && bias && y && d_exp, "op_conv_ranged: null argument");
+        vq_op_conv_ranged(*ctx, x, w, bias, kind, y, d_exp, n, H, W, Cin, Cout, (hipStream_t)stream);
+    });
+}
+
 int bevgen_decode_attention_splits(int B, int H, int n) { return decode_attention_splits(B, H, n); }
 
 int bevgen_profile_begin(bevgen_ctx* ctx) {

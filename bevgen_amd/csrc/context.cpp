@@ -81,8 +81,8 @@ void Ctx::check_status(const char* when) {
         m += "  A sampler read a NaN / inf logit or critic score (the reference asserts finite logits every step: mingpt_sparse.py:383,388, cond_transformer_multi_view.py:202).";
     if (e & BG_ST_F16_RANGE)
         m += "  A value written as an f16 operand (hi / lo planes of precision='f16x3', fp16 KV cache, fp16 decode activations) was NaN or had |v| >= 65520: the f16 split has a "
-             "5-bit exponent where the reference's bf16 / fp32 arithmetic has 8.  Run this checkpoint with precision='fp32' (and kv_cache='f32'); the VQGAN decoder alone also "
-             "with precision='f16x3r', which rescales its un-normalised activations instead of refusing them.";
+             "5-bit exponent where the reference's bf16 / fp32 arithmetic has 8.  Run this checkpoint with precision='fp32' (and kv_cache='f32'); the VQGAN (decoder and encoder) alone "
+             "also with precision='f16x3r', which rescales its un-normalised activations instead of refusing them.";
     if (e & BG_ST_NONFINITE_PIXELS) m += "  The VQGAN decoder produced a NaN / inf pixel.";
     if (e & BG_ST_NONFINITE_LATENTS)
         m += "  The VQGAN quantizer met a latent row without a finite distance to any codebook entry (NaN / inf in the input image, or an overflow inside the encoder): "

@@ -424,6 +424,10 @@ void launch_range_scale(const float* x, float* y, long elems, const int* e, hipS
 // in place y [rows, C] = 2^e y + bias[c] (+ residual); gn_part non-null: also the GroupNorm partial sums of the result as the LDS-DMA convolution's epilogue leaves them
 // (GemmArgs::gn_part; needs groupnorm_partials_supported, a bias and no residual)
 void launch_range_unscale(float* y, const float* bias, const float* residual, long rows, int C, const int* e, float* gn_part, hipStream_t s);
+// the encoder's fused forms: launch_range_unscale (no residual, no partials) that also leaves the exponent of what it wrote in e_next[0] (`amax_next`: one zeroed word),
+// and launch_nchw_to_nhwc_pad that also leaves the exponent of the image in e[0].  Same bits as the unfused kernels; NaN / inf as launch_range_exponent.
+void launch_range_unscale_amax(float* y, const float* bias, long rows, int C, const int* e, unsigned* amax_next, int* e_next, hipStream_t s);
+void launch_nchw_to_nhwc_pad_amax(const float* x, float* y, int n, int hw, int C, int Cpad /* % 4 == 0 */, unsigned* amax, int* e, hipStream_t s);
 void launch_row_softmax(float* x, int rows, int cols, float scale, hipStream_t s, int ld = 0 /* row stride (0 = cols); columns [cols, ld) are zero-filled */);
 
 // misc

@@ -122,7 +122,7 @@ struct Ctx {
     std::vector<UpLevelW> up;  // index = level (0 = full resolution)
     const float *norm_out_w = nullptr, *norm_out_b = nullptr;
     float *denorm_mean = nullptr, *denorm_std = nullptr;
-    // range-safe mode (cfg.vq_range with the split precision): one (exponent, absmax word) slot per site and pass of the most recent decode call, device memory that is
+    // range-safe mode (cfg.vq_range with the split precision): one (exponent, absmax word) slot per site and pass of the most recent decode / encode call, device memory that is
     // only grown; the host reads the exponents in bevgen_vq_range_exponents and nowhere else
     Arena vq_range_slots;
     int vq_range_used = 0;
@@ -208,8 +208,8 @@ void ar_forward(Ctx& c, const int64_t* cond, const float* I_inv, const float* E_
 void vq_finalize(Ctx& c);
 void vq_decode(Ctx& c, const int64_t* ids, const float* latents_nchw, int n, int lat_h, int lat_w, int out_mode, void* out, hipStream_t s);
 void vq_encode(Ctx& c, const float* x_nchw, int n, int RH, int RW, int64_t* ids, hipStream_t s);
-int vq_range_exponents(Ctx& c, int32_t* h_out, int cap);   // range-safe mode: exponents of the most recent vq_decode in site order (synchronises); returns their number
-// operator entries (bevgen_op_conv3x3_down, _vq_attn_block, _vq_out_tail, _vq_quantize, _conv3x3_gn_stats; include/bevgen_hip.h): the model's helpers on caller tensors
+int vq_range_exponents(Ctx& c, int32_t* h_out, int cap);   // range-safe mode: exponents of the most recent vq_decode / vq_encode in site order (synchronises); returns their number
+// operator entries (bevgen_op_conv3x3_down, _vq_attn_block, _vq_out_tail, _vq_quantize, _conv3x3_gn_stats, _conv_ranged; include/bevgen_hip.h): the model's helpers on caller tensors
 void vq_op_conv3x3_down(Ctx& c, const float* x, const float* w, const float* bias, float* y, int n, int H, int W, int Cin, int Cout, hipStream_t s);
 void vq_op_attn_block(Ctx& c, const float* x, const float* norm_w, const float* norm_b, const float* wq, const float* bq, const float* wk, const float* bk, const float* wv,
                       const float* bv, const float* wp, const float* bp, float* y, int n, int h, int w, int C, hipStream_t s);
@@ -218,6 +218,7 @@ void vq_op_out_tail(Ctx& c, const float* x, const float* norm_w, const float* no
 void vq_op_quantize(Ctx& c, const float* z, const float* codebook, int64_t* ids, float* zz_out, float* ee_out, long rows, int n_e, int D, hipStream_t s);
 void vq_op_conv3x3_gn_stats(Ctx& c, const float* x, const float* w, const float* bias, int range_route, float* y, float* part, float* stats, int n, int H, int W, int Cin,
                             int Cout, hipStream_t s);
+void vq_op_conv_ranged(Ctx& c, const float* x, const float* w, const float* bias, int kind, float* y, int32_t* d_exp, int n, int H, int W, int Cin, int Cout, hipStream_t s);
 // vqenc_kernels.hip
 void launch_nchw_to_nhwc_pad(const float* x, float* y, int n, int hw, int C, int Cpad, hipStream_t s);
 void launch_relayout_conv_weight_pad(const float* w, float* o, int cout, int cin, int cin_pad, int kh, int kw, hipStream_t s);

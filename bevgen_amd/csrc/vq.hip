@@ -225,7 +225,78 @@ __global__ __launch_bounds__(256) void range_unscale_gn_kernel(float* __restrict
     }
 }
 
+// The encoder's fused forms (vq_encode, range-safe mode): a pass that writes a tensor which the NEXT site reads as its operand also leaves that tensor's absmax, so the
+// next site's range_absmax_kernel pass disappears.  Both write exactly the bits of their unfused kernels and treat NaN / inf as range_absmax_kernel does.
+__device__ __forceinline__ void range_amax_finish(float m, unsigned bad, unsigned* __restrict__ amax, unsigned* __restrict__ status) {
+    m = wave_max(m);
+    if ((threadIdx.x & 63) == 0 && m > 0.f) atomicMax(amax, __float_as_uint(m));
+    if (bad) status_raise(status, BG_ST_F16_RANGE);
+}
+
+__device__ __forceinline__ void range_amax4(float4 t, float& m, unsigned& bad) {
+    const float v[4] = {t.x, t.y, t.z, t.w};
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        if (nonfinite(v[k])) bad = 1;
+        else m = fmaxf(m, fabsf(v[k]));
+    }
+}
+
+// range_unscale_kernel (no residual) + the absmax of what it writes
+__global__ __launch_bounds__(256) void range_unscale_amax_kernel(float4* __restrict__ y, const float* __restrict__ bias, long n4, int q4, const int* __restrict__ e,
+                                                                 unsigned* __restrict__ amax, unsigned* __restrict__ status) {
+    const float up = range_pow2(*e);
+    float m = 0.f;
+    unsigned bad = 0;
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x) {
+        const int cq = (int)(i % q4);
+        const float4 b = bias ? reinterpret_cast<const float4*>(bias)[cq] : make_float4(0.f, 0.f, 0.f, 0.f);
+        const float4 t = range_unscale4(y[i], up, b, nullptr, 0);
+        y[i] = t;
+        range_amax4(t, m, bad);
+    }
+    range_amax_finish(m, bad, amax, status);
+}
+
+// x [n, C, hw] -> y [n, hw, Cpad] (channels >= C are zero: launch_nchw_to_nhwc_pad's output) + the absmax of x; one thread per channel quad of a pixel
+__global__ __launch_bounds__(256) void nchw_to_nhwc_pad_amax_kernel(const float* __restrict__ x, float4* __restrict__ y, long n4, int hw, int C, int q4,
+                                                                    unsigned* __restrict__ amax, unsigned* __restrict__ status) {
+    float m = 0.f;
+    unsigned bad = 0;
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x) {
+        const int c0 = (int)(i % q4) * 4;
+        const long np = i / q4;
+        const int p = (int)(np % hw);
+        const long n = np / hw;
+        float v[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) v[k] = c0 + k < C ? x[(n * C + c0 + k) * hw + p] : 0.f;
+        const float4 t = make_float4(v[0], v[1], v[2], v[3]);
+        y[i] = t;
+        range_amax4(t, m, bad);
+    }
+    range_amax_finish(m, bad, amax, status);
+}
+
 static dim3 range_grid(long n4) { return dim3((unsigned)std::max<long>(1, std::min<long>((n4 + 255) / 256, 8192))); }
+
+void launch_range_unscale_amax(float* y, const float* bias, long rows, int C, const int* e, unsigned* amax_next, int* e_next, hipStream_t s) {
+    BG_REQUIRE(C % 4 == 0 && rows > 0, "range_unscale: C=%d must be a multiple of 4", C);
+    const long n4 = rows * (C / 4);
+    hipLaunchKernelGGL(range_unscale_amax_kernel, range_grid(n4), dim3(256), 0, s, reinterpret_cast<float4*>(y), bias, n4, C / 4, e, amax_next, status_current());
+    LAUNCH_CHECK();
+    hipLaunchKernelGGL(range_exponent_kernel, dim3(1), dim3(1), 0, s, amax_next, e_next);
+    LAUNCH_CHECK();
+}
+
+void launch_nchw_to_nhwc_pad_amax(const float* x, float* y, int n, int hw, int C, int Cpad, unsigned* amax, int* e, hipStream_t s) {
+    BG_REQUIRE(Cpad % 4 == 0 && C >= 1 && C <= Cpad && n >= 1 && hw >= 1, "nchw_to_nhwc_pad: C=%d Cpad=%d (Cpad must be a multiple of 4)", C, Cpad);
+    const long n4 = (long)n * hw * (Cpad / 4);
+    hipLaunchKernelGGL(nchw_to_nhwc_pad_amax_kernel, range_grid(n4), dim3(256), 0, s, x, reinterpret_cast<float4*>(y), n4, hw, C, Cpad / 4, amax, status_current());
+    LAUNCH_CHECK();
+    hipLaunchKernelGGL(range_exponent_kernel, dim3(1), dim3(1), 0, s, amax, e);
+    LAUNCH_CHECK();
+}
 
 void launch_range_exponent(const float* x, long elems, unsigned* amax, int* e, hipStream_t s) {
     BG_REQUIRE(elems > 0 && elems % 4 == 0, "range_exponent: element count %ld must be a positive multiple of 4", elems);

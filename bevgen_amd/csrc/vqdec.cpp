@@ -90,10 +90,13 @@ void conv1(const float* x, long rows, const ConvW& w, float* y, const float* res
     launch_gemm(g, s);
 }
 
-// Range-safe mode (cfg.vq_range, split precision, decoder only): the sites where an UN-normalised activation becomes an f16 operand - conv_in (reads post_quant_conv's
-// output), every nin_shortcut and every upsample convolution (both read the residual stream) - take a per-tensor exponent from the next slot (kernels.h launch_range_*).
-// Everything else on the path reads a GroupNorm output or softmax-weighted values of one; the codebook and the weights are parameters, refused as before.
-struct RangeSites { int* exps = nullptr; unsigned* amax = nullptr; int used = 0, cap = 0; };
+// Range-safe mode (cfg.vq_range, split precision): the sites where an UN-normalised activation becomes an f16 operand take a per-tensor exponent from the next slot
+// (kernels.h launch_range_*).  Decoder: conv_in (reads post_quant_conv's output), every nin_shortcut and every upsample convolution (both read the residual stream).
+// Encoder: conv_in (reads the caller's image), every nin_shortcut and every downsample convolution (residual stream), quant_conv (reads conv_out's output).
+// Everything else on the path reads a GroupNorm output or softmax-weighted values of one, or runs on the exact-fp32 kernel (the batched attention products, the
+// quantizer's codebook products); the codebook and the weights are parameters, refused as before.
+// pre_of: the tensor whose exponent a fused pass has already left in the next slot (range_next_slot): the site that reads it takes the slot without a pass of its own.
+struct RangeSites { int* exps = nullptr; unsigned* amax = nullptr; int used = 0, cap = 0; const float* pre_of = nullptr; };
 
 struct DecWs {
     float *a, *b, *t;   // ping-pong activations + temp (each max_act floats)
@@ -107,23 +110,48 @@ struct DecWs {
 
 const int* range_exponent(DecWs& ws, const Act& x, hipStream_t s) {
     RangeSites& r = *ws.range;
-    BG_REQUIRE(r.used < r.cap, "vq_decode: more range-safe sites than counted (%d)", r.cap);
-    launch_range_exponent(x.p, x.elems(), r.amax + r.used, r.exps + r.used, s);
+    BG_REQUIRE(r.used < r.cap, "vq: more range-safe sites than counted (%d)", r.cap);
+    BG_REQUIRE(!r.pre_of || r.pre_of == x.p, "vq: the next range-safe slot was prepared for another tensor");
+    if (r.pre_of) r.pre_of = nullptr;
+    else launch_range_exponent(x.p, x.elems(), r.amax + r.used, r.exps + r.used, s);
     return r.exps + r.used++;
 }
 
+// the slot the NEXT site takes, for a pass that writes that site's operand `of` and leaves its exponent on the way (launch_*_amax)
+struct NextSlot { unsigned* amax; int* e; };
+NextSlot range_next_slot(DecWs& ws, const float* of) {
+    RangeSites& r = *ws.range;
+    BG_REQUIRE(r.used < r.cap && !r.pre_of, "vq: more range-safe sites than counted (%d)", r.cap);
+    r.pre_of = of;
+    return NextSlot{r.amax + r.used, r.exps + r.used};
+}
+
+// the encoder's two fused passes (0: their unfused pairs, for A/B runs)
+static bool enc_fuse() {
+    static const int fuse = getenv("BEVGEN_VQ_ENC_FUSE") ? atoi(getenv("BEVGEN_VQ_ENC_FUSE")) : 1;
+    return fuse != 0;
+}
+
 // range-safe form of a convolution that reads the un-normalised fp32 tensor x itself: x 2^-e into `tmp` (x's size), W x' without the bias, then y = 2^e y + b.
-// k = 1: 1x1, k = 3: 3x3 (up: fused nearest-2x upsample)
-void conv_ranged(const Act& x, const ConvW& w, int k, int up, float* tmp, float* y, DecWs& ws, hipStream_t s) {
+// k = 1: 1x1, k = 3: 3x3 (up: fused nearest-2x upsample; down: the encoder's Downsample, conv3_down).  y_feeds_site: y is the next site's operand - the last pass also
+// leaves that site's exponent (range_next_slot)
+void conv3_down(const Act& x, const ConvW& w, float* y, hipStream_t s);
+void conv_ranged(const Act& x, const ConvW& w, int k, int up, float* tmp, float* y, DecWs& ws, hipStream_t s, int down = 0, bool y_feeds_site = false) {
     const int* e = range_exponent(ws, x, s);
     note_write(&ws.part, tmp);
     launch_range_scale(x.p, tmp, x.elems(), e, s);
     ConvW wb = w;
     wb.b = nullptr;
-    const long rows = (long)x.n * x.h * x.w * (up ? 4 : 1);
+    const long rows = down ? (long)x.n * (x.h / 2) * (x.w / 2) : (long)x.n * x.h * x.w * (up ? 4 : 1);
     if (k == 1) conv1(tmp, rows, wb, y, nullptr, s, &ws.part);
+    else if (down) { note_write(&ws.part, y); conv3_down(Act{tmp, x.n, x.h, x.w, x.c}, wb, y, s); }
     else conv3(Act{tmp, x.n, x.h, x.w, x.c}, wb, y, nullptr, up, s, false, &ws.part);
-    launch_range_unscale(y, w.b, nullptr, rows, w.cout, e, nullptr, s);
+    if (y_feeds_site && enc_fuse()) {
+        const NextSlot nx = range_next_slot(ws, y);
+        launch_range_unscale_amax(y, w.b, rows, w.cout, e, nx.amax, nx.e, s);
+    } else {
+        launch_range_unscale(y, w.b, nullptr, rows, w.cout, e, nullptr, s);
+    }
 }
 
 // statistics of x: from the producing convolution's epilogue partials when they describe exactly this tensor, else the pass over the tensor
@@ -428,7 +456,7 @@ void vq_decode(Ctx& c, const int64_t* ids, const float* latents_nchw, int n_tota
     c.vq_range_used = sites.used;
 }
 
-// exponents of the most recent decode call (host array); synchronises
+// exponents of the most recent decode / encode call (host array); synchronises
 int vq_range_exponents(Ctx& c, int32_t* out, int cap) {
     HIP_CHECK(hipDeviceSynchronize());
     const int n = std::min(c.vq_range_used, cap);
@@ -529,17 +557,45 @@ void vq_encode(Ctx& c, const float* x_nchw, int n_total, int RH, int RW, int64_t
         ws.zz = a.get<float>((size_t)n * lat_hw);
     };
     c.arena.reserve(Arena::measure([&](Arena& a) { DecWs ws; layout(a, ws, chunk); }));
+    RangeSites sites;
+    c.vq_range_used = 0;
+    if (planes && g.vq_range) {
+        int per_pass = 2;   // conv_in, quant_conv
+        auto count = [&](const ResBlockW& r) { per_pass += r.has_nin ? 1 : 0; };
+        for (const DownLevelW& d : c.down) {
+            for (const ResBlockW& r : d.blocks) count(r);
+            per_pass += d.has_down ? 1 : 0;
+        }
+        count(c.enc_mid1); count(c.enc_mid2);
+        sites.cap = per_pass * cdiv(n_total, chunk);
+        c.vq_range_slots.reserve((size_t)sites.cap * 8);
+        sites.exps = reinterpret_cast<int*>(c.vq_range_slots.base);
+        sites.amax = reinterpret_cast<unsigned*>(sites.exps + sites.cap);
+        HIP_CHECK(hipMemsetAsync(sites.exps, 0, (size_t)sites.cap * 8, s));
+    }
     for (int i0 = 0; i0 < n_total; i0 += chunk) {
         const int n = std::min(chunk, n_total - i0);
         c.arena.reset();
         DecWs ws;
+        if (sites.cap) ws.range = &sites;
         layout(c.arena, ws, n);
         const long lrows = (long)n * lat_hw;
         float *o = ws.o, *dots = ws.dots, *zq = ws.zq, *zz = ws.zz;
 
-        launch_nchw_to_nhwc_pad(x_nchw + (long)i0 * g.vq_in_channels * RH * RW, ws.t, n, RH * RW, g.vq_in_channels, c.enc_cin_pad, s);
+        const float* x_in = x_nchw + (long)i0 * g.vq_in_channels * RH * RW;
         Act x{ws.t, n, RH, RW, c.enc_cin_pad};
-        conv3(x, c.enc_conv_in, ws.a, nullptr, 0, s);
+        if (ws.range) {   // the layout change also leaves the image's exponent: conv_in's site needs no pass of its own over the padded tensor
+            if (enc_fuse()) {
+                const NextSlot nx = range_next_slot(ws, ws.t);
+                launch_nchw_to_nhwc_pad_amax(x_in, ws.t, n, RH * RW, g.vq_in_channels, c.enc_cin_pad, nx.amax, nx.e, s);
+            } else {
+                launch_nchw_to_nhwc_pad(x_in, ws.t, n, RH * RW, g.vq_in_channels, c.enc_cin_pad, s);
+            }
+            conv_ranged(x, c.enc_conv_in, 3, 0, ws.b, ws.a, ws, s);
+        } else {
+            launch_nchw_to_nhwc_pad(x_in, ws.t, n, RH * RW, g.vq_in_channels, c.enc_cin_pad, s);
+            conv3(x, c.enc_conv_in, ws.a, nullptr, 0, s);
+        }
         x = Act{ws.a, n, RH, RW, c.enc_conv_in.cout};
         auto pick2 = [&](float*& scratch, float*& y) {
             float* bufs[3] = {ws.a, ws.b, o};
@@ -556,7 +612,10 @@ void vq_encode(Ctx& c, const float* x_nchw, int n_total, int RH, int RW, int64_t
             }
             if (d.has_down) {  // F.pad(x, (0,1,0,1)) + conv 3x3 stride 2 padding 0
                 float *sc, *y; pick2(sc, y);
-                conv3_down(x, d.down, y, s);
+                // (its output is the next level's residual stream: where that level opens with a nin_shortcut, that site's operand)
+                const bool feeds_nin = !c.down[lvl + 1].blocks.empty() && c.down[lvl + 1].blocks[0].has_nin;
+                if (ws.range) conv_ranged(x, d.down, 3, 0, sc, y, ws, s, 1, feeds_nin);
+                else conv3_down(x, d.down, y, s);
                 x = Act{y, x.n, x.h / 2, x.w / 2, d.down.cout};
             }
         }
@@ -567,9 +626,11 @@ void vq_encode(Ctx& c, const float* x_nchw, int n_total, int RH, int RW, int64_t
         Act t{ws.t, x.n, x.h, x.w, x.c};
         float *sc, *y; pick2(sc, y);
         conv3(t, c.enc_conv_out, y, nullptr, 0, s, planes);                     // [n, lat*lat, z_channels]
-        conv1(y, lrows, c.quant_conv, zq, nullptr, s);                  // quant_conv (1x1)
+        if (ws.range) conv_ranged(Act{y, x.n, x.h, x.w, g.vq_z_channels}, c.quant_conv, 1, 0, sc, zq, ws, s);
+        else conv1(y, lrows, c.quant_conv, zq, nullptr, s);             // quant_conv (1x1)
         quantize(zq, c.codebook, c.codebook_sqnorm, zz, dots, ids + (long)i0 * lat_hw, lrows, g.vq_n_embed, g.vq_embed_dim, s);
     }
+    c.vq_range_used = sites.used;
 }
 
 // =====================================================================================================
@@ -623,6 +684,34 @@ void vq_op_conv3x3_down(Ctx& c, const float* x, const float* w, const float* bia
     OpWeights ow(c, s);
     const ConvW cw = ow.conv(wb, w, bias, Cout, Cin, 3);
     conv3_down(Act{const_cast<float*>(x), n, H, W, Cin}, cw, y, s);
+}
+
+// one range-safe site as vq_decode / vq_encode run it (conv_ranged); kind 0: 1x1, 1: 3x3, 2: the Downsample.  kind 2 ends in the fused pass (y_feeds_site) as a
+// downsample in front of a nin_shortcut does; the exponent that pass leaves for y stays in the arena.
+void vq_op_conv_ranged(Ctx& c, const float* x, const float* w, const float* bias, int kind, float* y, int32_t* d_exp, int n, int H, int W, int Cin, int Cout, hipStream_t s) {
+    BG_REQUIRE(c.cfg.precision == BEVGEN_PRECISION_F16X3, "op_conv_ranged: the range-safe sites belong to the split-precision mode (precision = f16x3)");
+    BG_REQUIRE(kind >= 0 && kind <= 2, "op_conv_ranged: kind %d (0 = 1x1, 1 = 3x3, 2 = downsample)", kind);
+    BG_REQUIRE(n >= 1 && H >= 1 && W >= 1 && Cin >= 32 && Cin % 32 == 0 && Cout >= 4 && Cout % 4 == 0, "op_conv_ranged: needs Cin %% 32 == 0 and Cout %% 4 == 0 (Cin=%d Cout=%d)", Cin, Cout);
+    BG_REQUIRE(kind != 2 || (H % 2 == 0 && W % 2 == 0), "op_conv_ranged: the downsample needs even H, W (H=%d W=%d)", H, W);
+    BG_REQUIRE(x != y, "op_conv_ranged: the output must not alias the input");
+    const int k = kind == 0 ? 1 : 3;
+    OpWeights::Buf wb;
+    float* tmp;
+    RangeSites sites;
+    sites.cap = 2;
+    c.arena.carve([&](Arena& a) {
+        wb = OpWeights::take(c, a, Cout, Cin, k);
+        tmp = a.get<float>((size_t)n * H * W * Cin);
+        sites.exps = a.get<int>(2 * sites.cap);
+    });
+    sites.amax = reinterpret_cast<unsigned*>(sites.exps + sites.cap);
+    HIP_CHECK(hipMemsetAsync(sites.exps, 0, (size_t)sites.cap * 8, s));
+    OpWeights ow(c, s);
+    const ConvW cw = ow.conv(wb, w, bias, Cout, Cin, k);
+    DecWs ws{};
+    ws.range = &sites;
+    conv_ranged(Act{const_cast<float*>(x), n, H, W, Cin}, cw, k, 0, tmp, y, ws, s, kind == 2, kind == 2);
+    HIP_CHECK(hipMemcpyAsync(d_exp, sites.exps, sizeof(int32_t), hipMemcpyDeviceToDevice, s));
 }
 
 void vq_op_attn_block(Ctx& c, const float* x, const float* norm_w, const float* norm_b, const float* wq, const float* bq, const float* wk, const float* bk, const float* wv,

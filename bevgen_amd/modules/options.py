@@ -6,8 +6,8 @@ option is: a key next to the ``_target_`` (``+model.transformer.kv_cache=f16`` o
 
     key             env var                  values                 drop-in default
     precision       $BEVGEN_PRECISION        fp32 | f16x3 | f16x3r  f16x3   (3 f16 MFMAs per product on hi/lo splits, fp32 accumulate; token-exact on every fixture;
-                                                                            f16x3r = f16x3 whose VQGAN DECODER rescales an un-normalised activation outside the f16 range by
-                                                                            a per-tensor power of two instead of refusing the checkpoint - MaskGit, Route A and vq_encode
+                                                                            f16x3r = f16x3 whose VQGAN (decoder and encoder) rescales an un-normalised activation outside the
+                                                                            f16 range by a per-tensor power of two instead of refusing the checkpoint - MaskGit and Route A
                                                                             treat it exactly as f16x3)
     weights         $BEVGEN_WEIGHTS          f32 | f16              f32     (f16: GEMM / conv matrices rounded once at load, two MFMAs per product)
     kv_cache        $BEVGEN_KV_CACHE         f32 | f16              f32     (Route A; f16 = fp16 storage / fp32 accumulate: BASELINE config 4)

@@ -76,8 +76,8 @@ class Context:
         if precision not in ("fp32", "f16x3", "f16x3r"):
             raise ValueError(f"precision must be 'fp32', 'f16x3' or 'f16x3r', got {precision!r}")
         self.precision = precision
-        # 'f16x3r' ("range-safe") = f16x3 whose VQGAN decoder rescales its un-normalised activations by a per-tensor power of two instead of refusing a checkpoint whose
-        # residual stream leaves the f16 range (bevgen_cfg.vq_range); the transformer routes and vq_encode behave exactly as under 'f16x3'
+        # 'f16x3r' ("range-safe") = f16x3 whose VQGAN decoder and encoder rescale their un-normalised activations by a per-tensor power of two instead of refusing a
+        # checkpoint whose residual stream leaves the f16 range (bevgen_cfg.vq_range); the transformer routes behave exactly as under 'f16x3'
         c.precision = {"fp32": _lib.PRECISION_FP32, "f16x3": _lib.PRECISION_F16X3, "f16x3r": _lib.PRECISION_F16X3}[precision]
         c.vq_range = 1 if precision == "f16x3r" else 0
         c.max_batch = max_batch
@@ -391,7 +391,10 @@ class Context:
         return out
 
     def vq_encode(self, x, check=True):
-        """VQModel.encode -> token ids: x [n, in_channels, H, W] fp32 (NCHW; H, W multiples of 2^(levels-1)) -> ids [n, h*w] int64."""
+        """VQModel.encode -> token ids: x [n, in_channels, H, W] fp32 (NCHW; H, W multiples of 2^(levels-1)) -> ids [n, h*w] int64.
+        precision='f16x3': an image or a residual stream outside the f16 operand range raises BevgenError (ERR_NUMERIC); precision='f16x3r' rescales the image (conv_in),
+        the residual stream in front of every nin_shortcut and downsample convolution and conv_out's output (quant_conv) by a per-tensor power of two instead
+        (vq_range_exponents); where nothing leaves the range the ids are those of 'f16x3' bit for bit."""
         dd = self.vq_ddconfig
         x = _req(x, torch.float32, self.device, "x")
         n, ch, H, W = x.shape
@@ -415,8 +418,9 @@ class Context:
         return out
 
     def vq_range_exponents(self, cap: int = 4096):
-        """precision='f16x3r': the exponents the most recent vq_decode / vq_decode_latents chose, in site order (per pass of up to 48 images: conv_in, then every
-        nin_shortcut and upsample convolution as executed), as an int32 numpy array; empty in every other mode.  Synchronises."""
+        """precision='f16x3r': the exponents the most recent vq_decode / vq_decode_latents / vq_encode chose, in site order (per pass of up to 48 images; decode: conv_in,
+        then every nin_shortcut and upsample convolution as executed; encode: conv_in, then every nin_shortcut and downsample convolution as executed, then quant_conv),
+        as an int32 numpy array; empty in every other mode.  Synchronises."""
         buf = (C.c_int32 * cap)()
         n = C.c_int(0)
         self._check(self.lib.bevgen_vq_range_exponents(self._h, buf, cap, C.byref(n)))
@@ -646,6 +650,19 @@ class Context:
         ee = torch.empty((n_e,), dtype=torch.float32, device=self.device) if want_norms else None
         self._check(self.lib.bevgen_op_vq_quantize(self._h, _ptr(z), _ptr(codebook), _ptr(ids), _ptr(zz), _ptr(ee), rows, n_e, D, self._s()))
         return (ids, zz, ee) if want_norms else ids
+
+    def op_conv_ranged(self, x_nhwc, w_oihw, bias, kind, check=True):
+        """precision='f16x3' / 'f16x3r' contexts: one site of the range-safe mode as vq_decode / vq_encode run it -> (y, e): e (a one-element int32 tensor) is the exponent
+        of x (0 where max |x| < 32768, else the smallest e with max |x| 2^-e < 32768), y = 2^e conv(x 2^-e) + bias.  kind 0: 1x1 ([n, H, W, Cout]), 1: 3x3 stride 1
+        padding 1, 2: the encoder's Downsample ([n, H / 2, W / 2, Cout]; H, W even).  Cin % 32 == 0; NaN / inf in x raise BevgenError (ERR_NUMERIC)."""
+        x = _req(x_nhwc, torch.float32, self.device, "x")
+        n, H, W, Cin = x.shape
+        Cout = w_oihw.shape[0]
+        y = torch.empty((n, H // 2, W // 2, Cout) if kind == 2 else (n, H, W, Cout), dtype=torch.float32, device=self.device)
+        e = torch.zeros((1,), dtype=torch.int32, device=self.device)
+        self._check(self.lib.bevgen_op_conv_ranged(self._h, _ptr(x), _ptr(w_oihw), _ptr(bias), int(kind), _ptr(y), _ptr(e), n, H, W, Cin, Cout, self._s()))
+        self._done(check)
+        return y, e
 
     def op_conv3x3_gn_stats(self, x_nhwc, w_oihw, bias, range_route=False):
         """precision='f16x3': the LDS-DMA 3x3 convolution whose epilogue leaves the GroupNorm partial sums of its output -> (y [n, H, W, Cout], partials

@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define BEVGEN_ABI_VERSION 9   /* 9: operator entries of the VQGAN building blocks (bevgen_op_conv3x3_down, _vq_attn_block, _vq_out_tail, _vq_quantize, _conv3x3_gn_stats), BEVGEN_STATUS_NONFINITE_LATENTS.  8: bevgen_cfg.vq_range (taken out of reserved[]: the struct size is unchanged), bevgen_vq_range_exponents, bevgen_op_range_split.  7: operator entries of the token samplers (bevgen_op_remask, _maskgit_pick, _critic_scores, _ar_pick, _ar_score_rows, _mean_fixed_order).  6: device status word (bevgen_synchronize, bevgen_status, BEVGEN_ERR_NUMERIC, BEVGEN_STATUS_*).  5: bevgen_op_mlp_fused; a context without max_batch <= 4 packs the split decode layer lazily (see Conventions).  4: 4: BEVGEN_PROFILE_KINDS 5 -> 6 (bevgen_profile_end writes 18 doubles), bevgen_cfg.decode_chains, decode_path values 2 / 3 */
+#define BEVGEN_ABI_VERSION 10   /* 10: bevgen_cfg.vq_range covers bevgen_vq_encode (bevgen_vq_range_exponents reports the most recent decode OR encode call), bevgen_op_conv_ranged.  9: operator entries of the VQGAN building blocks (bevgen_op_conv3x3_down, _vq_attn_block, _vq_out_tail, _vq_quantize, _conv3x3_gn_stats), BEVGEN_STATUS_NONFINITE_LATENTS.  8: bevgen_cfg.vq_range (taken out of reserved[]: the struct size is unchanged), bevgen_vq_range_exponents, bevgen_op_range_split.  7: operator entries of the token samplers (bevgen_op_remask, _maskgit_pick, _critic_scores, _ar_pick, _ar_score_rows, _mean_fixed_order).  6: device status word (bevgen_synchronize, bevgen_status, BEVGEN_ERR_NUMERIC, BEVGEN_STATUS_*).  5: bevgen_op_mlp_fused; a context without max_batch <= 4 packs the split decode layer lazily (see Conventions).  4: 4: BEVGEN_PROFILE_KINDS 5 -> 6 (bevgen_profile_end writes 18 doubles), bevgen_cfg.decode_chains, decode_path values 2 / 3 */
 
 enum { BEVGEN_ROUTE_MASKGIT = 0, BEVGEN_ROUTE_AR = 1 };
 /* FP32  : every product and accumulation in exact fp32 on the matrix cores (v_mfma_f32_32x32x2_f32) - bit-exact greedy tokens vs the CPU reference.
@@ -61,10 +61,11 @@ enum {
  * A raised word is returned as BEVGEN_ERR_NUMERIC (bits 4, 8, 16, 32) or BEVGEN_ERR_INTERNAL (bits 1, 2) and then cleared.
  * Policy for precision = F16X3 / fp16 storage modes: an operand whose f16 image would be inf / NaN (|v| >= 65520) is an ERROR, not rescaled - the split keeps fp32-class
  * mantissas but f16's exponent range, where the reference's bf16 / fp32 arithmetic has 8 exponent bits; such a checkpoint must run with BEVGEN_PRECISION_FP32.
- * One opt-in exception, stage-1 DECODE only: with bevgen_cfg.vq_range = 1 the un-normalised activation tensors of the decoder that become f16 operands (in front of the
- * upsample convolutions, the nin_shortcut convolutions and conv_in) are rescaled by a per-tensor power of two chosen on the device (exact in every bit the split keeps), so
- * BEVGEN_STATUS_F16_RANGE is then raised by the decoder only for NaN / inf activations and for a codebook entry outside the range.  Weights outside the range are refused by
- * bevgen_finalize in either setting; the transformer routes and bevgen_vq_encode ignore vq_range. */
+ * One opt-in exception, stage 1 only: with bevgen_cfg.vq_range = 1 the un-normalised activation tensors of the decoder and the encoder that become f16 operands (decoder: in
+ * front of the upsample convolutions, the nin_shortcut convolutions and conv_in; encoder: the image in front of conv_in, the residual stream in front of the nin_shortcut
+ * and downsample convolutions, conv_out's output in front of quant_conv) are rescaled by a per-tensor power of two chosen on the device (exact in every bit the split
+ * keeps), so BEVGEN_STATUS_F16_RANGE is then raised by stage 1 only for NaN / inf activations and for a codebook entry outside the range.  Weights outside the range are
+ * refused by bevgen_finalize in either setting; the transformer routes ignore vq_range. */
 enum {
     BEVGEN_STATUS_MLP_BARRIER = 1,        /* fused MLP launch of the decode step: an XCD-local barrier timed out (the GPU was shared); the context falls back to two launches */
     BEVGEN_STATUS_MLP_PLACEMENT = 2,      /* ...: a workgroup was not placed on the XCD its index implies */
@@ -118,11 +119,11 @@ typedef struct bevgen_cfg {
                                                           layer kernels are enqueued on separate HIP streams (one fork / join per step inside the captured graph), so
                                                           that one chain's weight-streaming projections run under another chain's K/V stream instead of every short
                                                           dependent kernel paying its ramp alone.  0 = the library's choice for the batch, 1 = a single chain */
-    int32_t vq_range;                                  /* stage-1 decoder with BEVGEN_PRECISION_F16X3: 0 (default) = an un-normalised activation outside the f16 operand range
+    int32_t vq_range;                                  /* stage 1 (decoder and encoder) with BEVGEN_PRECISION_F16X3: 0 (default) = an un-normalised activation outside the f16 operand range
                                                           is refused (BEVGEN_STATUS_F16_RANGE); 1 = "range-safe": per call and per site, a device-side absmax of the tensor, an
                                                           exponent e (0 where absmax < 32768, else the smallest e with absmax 2^-e < 32768), the operand split as x 2^-e and the
                                                           convolution's result formed as 2^e (W x') + bias (+ residual).  No host synchronisation; e = 0 everywhere gives the bits
-                                                          of vq_range = 0.  The encoder is not covered yet; ignored with BEVGEN_PRECISION_FP32 */
+                                                          of vq_range = 0.  Ignored with BEVGEN_PRECISION_FP32 */
     int32_t reserved[9];
 } bevgen_cfg;
 
@@ -279,9 +280,10 @@ int bevgen_vq_encode(bevgen_ctx* ctx, const float* d_x, int n, int H, int W, int
 /* VQModel.decode(quant) (stage1/vqgan.py:118-121) for already looked-up latents: d_zq [n, embed_dim, lat_h, lat_w] (NCHW, like the reference). */
 int bevgen_vq_decode_latents(bevgen_ctx* ctx, const float* d_zq, int n, int lat_h, int lat_w, int out_mode, void* d_out, void* stream);
 
-/* vq_range = 1: the exponents the most recent bevgen_vq_decode / bevgen_vq_decode_latents call on this context chose, in site order (per pass of up to 48 images: conv_in,
- * then every nin_shortcut and upsample convolution in execution order), written to the HOST array h_out[cap]; *count = their number (may exceed cap; 0 with vq_range = 0
- * or before the first call).  Synchronises the device. */
+/* vq_range = 1: the exponents the most recent bevgen_vq_decode / bevgen_vq_decode_latents / bevgen_vq_encode call on this context chose, in site order (per pass of up to
+ * 48 images; decode: conv_in, then every nin_shortcut and upsample convolution in execution order; encode: conv_in, then every nin_shortcut and downsample convolution in
+ * execution order, then quant_conv), written to the HOST array h_out[cap]; *count = their number (may exceed cap; 0 with vq_range = 0 or before the first call).
+ * Synchronises the device. */
 int bevgen_vq_range_exponents(bevgen_ctx* ctx, int32_t* h_out, int cap, int* count);
 
 /* ---------------------------------------------------------------------------------------------------------------
@@ -385,6 +387,13 @@ int bevgen_op_vq_quantize(bevgen_ctx* ctx, const float* d_z, const float* d_code
  * Cout % 128 == 0, else BEVGEN_ERR_INVALID. */
 int bevgen_op_conv3x3_gn_stats(bevgen_ctx* ctx, const float* d_x_nhwc, const float* d_w_oihw, const float* d_bias, int range_route, float* d_y_nhwc, float* d_part, float* d_stats,
                                int n, int H, int W, int Cin, int Cout, void* stream);
+/* conv_ranged (precision = F16X3 contexts, else BEVGEN_ERR_INVALID): ONE site of the range-safe mode exactly as bevgen_vq_decode / bevgen_vq_encode run it, whatever the
+ * context's vq_range: device-side absmax of d_x and exponent e (the rule at bevgen_cfg.vq_range) -> d_exp[0], the convolution of x 2^-e without its bias, then
+ * y = 2^e y + bias.  kind 0: 1x1; 1: 3x3, stride 1, padding 1; 2: the encoder's Downsample (zero pad bottom / right, 3x3, stride 2; H and W even, d_y [n, H/2, W/2, Cout],
+ * and its last pass is the fused one that also takes the absmax of d_y).  Cin % 32 == 0, Cout % 4 == 0; d_bias is required; d_y must not alias d_x.  NaN / inf in d_x
+ * raise BEVGEN_STATUS_F16_RANGE. */
+int bevgen_op_conv_ranged(bevgen_ctx* ctx, const float* d_x_nhwc, const float* d_w_oihw, const float* d_bias, int kind, float* d_y_nhwc, int32_t* d_exp, int n, int H, int W,
+                          int Cin, int Cout, void* stream);
 
 /* Per-kernel timing support for bench.py's roofline leg: number of workgroup splits the decode-attention kernel uses. */
 int bevgen_decode_attention_splits(int B, int H, int n);
