@@ -15,7 +15,7 @@ HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "bevgen_hip.h")
 
 ABI_VERSION = 10
 ROUTE_MASKGIT, ROUTE_AR = 0, 1
-PRECISION_FP32, PRECISION_BF16, PRECISION_F16X3 = 0, 1, 2
+PRECISION_FP32, PRECISION_BF16, PRECISION_F16X3, PRECISION_F16X1 = 0, 1, 2, 3
 KV_F32, KV_F16 = 0, 1
 DECODE_FUSED, DECODE_PER_OP, DECODE_SPLIT, DECODE_AUTO = 0, 1, 2, 3
 VQ_OUT_RAW, VQ_OUT_DENORM, VQ_OUT_U8 = 0, 1, 2

@@ -17,6 +17,7 @@ static int guarded(bevgen_ctx* ctx, F&& f, bool check_first = true) {
         if (!ctx) return BEVGEN_ERR_INVALID;
         HIP_CHECK(hipSetDevice(ctx->device));
         split_registry_set(ctx->cfg.precision == BEVGEN_PRECISION_F16X3 ? &ctx->split : nullptr);
+        split_single_product_set(false);   // (only the Route M entry points below turn it on, for their own call)
         struct CurrentProf {   // this context's profiler and status word receive the launch records / flags of this call (restored on every exit path)
             Profiler* old;
             unsigned* old_st;
@@ -36,6 +37,13 @@ static int guarded(bevgen_ctx* ctx, F&& f, bool check_first = true) {
     }
 }
 
+// Route M entry points of a BEVGEN_PRECISION_F16X1 context: this thread's launches through the split table carry GemmArgs::a_hi_only until the call returns
+struct SingleProductScope {
+    bool old;
+    explicit SingleProductScope(const bevgen_ctx* c) : old(split_single_product_set(c->single_product)) {}
+    ~SingleProductScope() { split_single_product_set(old); }
+};
+
 static void need_final(bevgen_ctx* c) {
     if (!c->finalized) fail(BEVGEN_ERR_STATE, "bevgen_finalize must be called after loading tensors and before compute calls");
 }
@@ -50,9 +58,11 @@ int bevgen_create(const bevgen_cfg* cfg, int device, bevgen_ctx** out) {
         BG_REQUIRE(cfg->abi_version == BEVGEN_ABI_VERSION, "bevgen_create: ABI version %d, library is %d", cfg->abi_version, BEVGEN_ABI_VERSION);
         BG_REQUIRE(cfg->route == BEVGEN_ROUTE_MASKGIT || cfg->route == BEVGEN_ROUTE_AR, "bevgen_create: unknown route %d", cfg->route);
         BG_REQUIRE(cfg->kv_cache_dtype == BEVGEN_KV_F32 || cfg->kv_cache_dtype == BEVGEN_KV_F16, "bevgen_create: kv_cache_dtype must be BEVGEN_KV_F32 or BEVGEN_KV_F16");
-        BG_REQUIRE(cfg->precision == BEVGEN_PRECISION_FP32 || cfg->precision == BEVGEN_PRECISION_F16X3, "bevgen_create: precision must be BEVGEN_PRECISION_FP32 or BEVGEN_PRECISION_F16X3");
-        BG_REQUIRE(cfg->weight_dtype == BEVGEN_W_F32 || (cfg->weight_dtype == BEVGEN_W_F16 && cfg->precision == BEVGEN_PRECISION_F16X3),
-                   "bevgen_create: weight_dtype must be BEVGEN_W_F32, or BEVGEN_W_F16 together with BEVGEN_PRECISION_F16X3");
+        const bool f16x1 = cfg->precision == BEVGEN_PRECISION_F16X1;
+        BG_REQUIRE(cfg->precision == BEVGEN_PRECISION_FP32 || cfg->precision == BEVGEN_PRECISION_F16X3 || f16x1,
+                   "bevgen_create: precision must be BEVGEN_PRECISION_FP32, BEVGEN_PRECISION_F16X3 or BEVGEN_PRECISION_F16X1");
+        BG_REQUIRE(cfg->weight_dtype == BEVGEN_W_F32 || (cfg->weight_dtype == BEVGEN_W_F16 && (cfg->precision == BEVGEN_PRECISION_F16X3 || f16x1)),
+                   "bevgen_create: weight_dtype must be BEVGEN_W_F32, or BEVGEN_W_F16 together with BEVGEN_PRECISION_F16X3 / _F16X1");
         BG_REQUIRE(cfg->vq_range == 0 || cfg->vq_range == 1, "bevgen_create: vq_range must be 0 (refuse) or 1 (rescale), got %d", cfg->vq_range);
         int ndev = 0;
         HIP_CHECK(hipGetDeviceCount(&ndev));
@@ -64,6 +74,10 @@ int bevgen_create(const bevgen_cfg* cfg, int device, bevgen_ctx** out) {
         HIP_CHECK(hipSetDevice(device));
         std::unique_ptr<bevgen_ctx> c(new bevgen_ctx());
         c->cfg = *cfg;
+        if (f16x1) {   // an F16X3 context in everything but the Route M projections (bevgen_hip.h): every `precision == F16X3` test of the library holds for it
+            c->cfg.precision = BEVGEN_PRECISION_F16X3;
+            c->single_product = true;
+        }
         c->device = device;
         // the device status word: mapped host memory, so that the host reads it without a copy or a synchronisation (common.h BG_ST_*)
         HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&c->status_host), 64, hipHostMallocMapped));
@@ -131,6 +145,7 @@ int bevgen_muse_forward(bevgen_ctx* ctx, const int64_t* ids, const int64_t* cond
         need_final(ctx);
         BG_REQUIRE(ids && cond && I_inv && E_inv, "muse_forward: null input");
         BG_REQUIRE(B >= 1 && (ctx->cfg.max_batch <= 0 || B <= ctx->cfg.max_batch), "muse_forward: batch %d exceeds max_batch %d", B, ctx->cfg.max_batch);
+        const SingleProductScope sp(ctx);
         muse_forward(*ctx, ids, cond, I_inv, E_inv, B, logits, embed, (hipStream_t)stream);
     });
 }
@@ -152,6 +167,7 @@ int bevgen_maskgit_generate_ex(bevgen_ctx* ctx, const int64_t* cond, const float
         for (int i = 0; i < timesteps; ++i)
             BG_REQUIRE(sched[i] >= 1 && sched[i] <= ctx->cfg.cam_latent_h * ctx->cfg.cam_latent_w, "maskgit_generate: mask_schedule[%d]=%d out of range", i, sched[i]);
         BG_REQUIRE(samples_per_layout >= 1 && B % samples_per_layout == 0, "maskgit_generate: batch %d is not a multiple of samples_per_layout %d", B, samples_per_layout);
+        const SingleProductScope sp(ctx);
         maskgit_generate(*ctx, cond, I_inv, E_inv, B, timesteps, sched, temperature, topk_k, critic_noise_scale, gumbel_u, critic_u, init_ids, out, (hipStream_t)stream, noise_seed,
                          score_mode, samples_per_layout);
     });
@@ -275,8 +291,13 @@ int bevgen_op_gemm(bevgen_ctx* ctx, const float* a, const float* w, const float*
         g.M = M; g.N = N; g.K = K; g.lda = K; g.ldb = K; g.ldc = N; g.ldr = N;
         g.act = act_gelu ? ACT_GELU : ACT_NONE;
         if (skinny == 5 || skinny == 6) skinny = 3;   // 5 = mode 3 with the k range split over three slices (the low-latency path of small batches); needs M small enough for
-        const bool ksplit3 = skinny_in == 5;           // 128-row tiles.  6 = mode 3 in its stream-K form (gemm_split_glds_sk_kernel), whatever the shape
+        const bool ksplit3 = skinny_in == 5 || skinny_in == 8;   // 128-row tiles.  6 = mode 3 in its stream-K form (gemm_split_glds_sk_kernel), whatever the shape
         const bool stream_k = skinny_in == 6;
+        // 7 - 9 = the single-product forms (BEVGEN_PRECISION_F16X1): 7 = mode 4 computing f16(a) f16(w)^T, 8 = 7 with the k range in three slices, 9 = mode 2
+        // (gemm_split_kernel) single-product.  w's low plane is ignored whatever w holds
+        const bool single = skinny_in >= 7 && skinny_in <= 9;
+        if (skinny == 7 || skinny == 8) skinny = 4;
+        if (skinny == 9) skinny = 2;
         if (skinny == 4 || skinny == 3 || skinny == 2) {  // split-precision paths with on-the-fly operand splits (tests / roofline probes): 3 = LDS-DMA kernel, 4 = the same for
                                                           // an f16-representable w (two MFMAs per product: the weights='f16' mode's kernel)
             uint16_t *bp, *ap;
@@ -288,6 +309,8 @@ int bevgen_op_gemm(bevgen_ctx* ctx, const float* a, const float* w, const float*
             });
             launch_split_weight(w, bp, (long)N * K, (hipStream_t)stream);
             g.B_hi = bp; g.B_lo = bp + 32;
+            g.a_hi_only = single;
+            g.b_lo_zero = single;
             if (skinny >= 3) {
                 g.b_lo_zero = skinny == 4;
                 launch_split_weight(a, ap, (long)M * K, (hipStream_t)stream);

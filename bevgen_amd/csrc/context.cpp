@@ -22,12 +22,13 @@ void Arena::release() {
 }
 
 // ------------------------------------------------------------------------------------------------ ctx
-void Ctx::split_weight(const float* w, long n) {
+void Ctx::split_weight(const float* w, long n, bool route_m) {
     if (cfg.precision != BEVGEN_PRECISION_F16X3 || split.count(w)) return;
     void* planes = own((size_t)n * 4);
-    const bool w16 = cfg.weight_dtype == BEVGEN_W_F16;
+    // (the decision is per weight: BEVGEN_PRECISION_F16X1 rounds the Route M matrices whatever weight_dtype says, the VQGAN's and Route A's follow weight_dtype alone)
+    const bool w16 = cfg.weight_dtype == BEVGEN_W_F16 || (route_m && single_product);
     // weight_dtype = f16: the model becomes the one whose matrices are f16-representable (rounded once, in place, so that every other consumer of
-    // the fp32 copy sees the same values); the low plane is then zero and the GEMM issues two MFMAs per product instead of three
+    // the fp32 copy sees the same values); the low plane is then zero and the GEMM issues two MFMAs per product instead of three (single-product mode: one)
     if (w16) launch_round_to_f16(const_cast<float*>(w), nullptr, n, 0);
     launch_split_weight(w, planes, n, 0);
     split[w] = SplitPlanes{reinterpret_cast<const uint16_t*>(planes), reinterpret_cast<const uint16_t*>(planes) + 32, w16};
@@ -81,7 +82,8 @@ void Ctx::check_status(const char* when) {
         m += "  A sampler read a NaN / inf logit or critic score (the reference asserts finite logits every step: mingpt_sparse.py:383,388, cond_transformer_multi_view.py:202).";
     if (e & BG_ST_F16_RANGE)
         m += "  A value written as an f16 operand (hi / lo planes of precision='f16x3', fp16 KV cache, fp16 decode activations) was NaN or had |v| >= 65520: the f16 split has a "
-             "5-bit exponent where the reference's bf16 / fp32 arithmetic has 8.  Run this checkpoint with precision='fp32' (and kv_cache='f32'); the VQGAN (decoder and encoder) alone "
+             "5-bit exponent where the reference's bf16 / fp32 arithmetic has 8 (precision='f16x1', Route M's single-product mode, has the same operand range).  Run this checkpoint with "
+             "precision='fp32' (and kv_cache='f32'); the VQGAN (decoder and encoder) alone "
              "also with precision='f16x3r', which rescales its un-normalised activations instead of refusing them.";
     if (e & BG_ST_NONFINITE_PIXELS) m += "  The VQGAN decoder produced a NaN / inf pixel.";
     if (e & BG_ST_NONFINITE_LATENTS)
@@ -213,11 +215,11 @@ static void finalize_muse(Ctx& c) {
         l.ff_w4_padded = reinterpret_cast<float*>(c.own((size_t)D * c.Fpad * sizeof(float)));
         launch_pad_rows(c.pf(q + "4.weight"), F, l.ff_w4_padded, c.Fpad, D, F, 0);
         for (int j = 0; j < 2; ++j) {
-            c.split_weight(l.to_q[j], (long)inner * D);
-            c.split_weight(l.to_kv[j], 2L * inner * D);
-            c.split_weight(l.to_out[j], (long)D * inner);
+            c.split_weight(l.to_q[j], (long)inner * D, true);
+            c.split_weight(l.to_kv[j], 2L * inner * D, true);
+            c.split_weight(l.to_out[j], (long)D * inner, true);
         }
-        c.split_weight(l.ff_w1, 2L * F * D);
+        c.split_weight(l.ff_w1, 2L * F * D, true);
         if (g.precision == BEVGEN_PRECISION_F16X3) {
             l.null_self = c.own((size_t)4 * H * 64 * sizeof(_Float16));
             launch_muse_null_kv_prep(l.null_kv[0], l.k_scale[0], l.null_self, H, 0);
@@ -225,22 +227,22 @@ static void finalize_muse(Ctx& c) {
             l.to_qkv_self = reinterpret_cast<float*>(c.own((size_t)3 * inner * D * sizeof(float)));
             HIP_CHECK(hipMemcpy(l.to_qkv_self, l.to_q[0], (size_t)inner * D * sizeof(float), hipMemcpyDeviceToDevice));
             HIP_CHECK(hipMemcpy(l.to_qkv_self + (size_t)inner * D, l.to_kv[0], (size_t)2 * inner * D * sizeof(float), hipMemcpyDeviceToDevice));
-            c.split_weight(l.to_qkv_self, 3L * inner * D);
+            c.split_weight(l.to_qkv_self, 3L * inner * D, true);
         }
         if (g.precision == BEVGEN_PRECISION_F16X3 && c.Fpad % 64 == 0) {
             l.ff_w1_geglu = reinterpret_cast<float*>(c.own((size_t)2 * c.Fpad * D * sizeof(float)));
             launch_geglu_weight_order(l.ff_w1, l.ff_w1_geglu, F, c.Fpad, D, 0);
-            c.split_weight(l.ff_w1_geglu, 2L * c.Fpad * D);
+            c.split_weight(l.ff_w1_geglu, 2L * c.Fpad * D, true);
         }
-        c.split_weight(l.ff_w4_padded, (long)D * c.Fpad);
-        if (g.precision == BEVGEN_PRECISION_F16X3 && g.weight_dtype != BEVGEN_W_F16 && l.ff_w1_geglu) {
-            // consumer-side constants of the folded LayerNorms (muse.cpp muse_blocks; weight_dtype = f16 keeps the LayerNorm kernels: W o gamma is not f16-representable
-            // and that mode's contract is "the fp32-class evaluation of the ROUNDED matrices")
+        c.split_weight(l.ff_w4_padded, (long)D * c.Fpad, true);
+        if (g.precision == BEVGEN_PRECISION_F16X3 && g.weight_dtype != BEVGEN_W_F16 && !c.single_product && l.ff_w1_geglu) {
+            // consumer-side constants of the folded LayerNorms (muse.cpp muse_blocks; weight_dtype = f16 - and the single-product mode, which rounds the same matrices - keeps the
+            // LayerNorm kernels: W o gamma is not f16-representable and that mode's contract is "the fp32-class evaluation of the ROUNDED matrices")
             auto fold = [&](const float* W, const float* gamma, int N, int K, int Kg, float*& Wg, float*& cs) {
                 Wg = reinterpret_cast<float*>(c.own((size_t)N * K * sizeof(float)));
                 cs = reinterpret_cast<float*>(c.own((size_t)N * sizeof(float)));
                 launch_ln_fold_weight(W, gamma, Wg, cs, N, K, Kg, 0);
-                c.split_weight(Wg, (long)N * K);
+                c.split_weight(Wg, (long)N * K, true);
             };
             fold(l.ff_w4_padded, l.ff_g3, D, c.Fpad, F, l.fold_w4, l.fold_w4_cs);
             fold(l.to_qkv_self, l.norm_g[0], 3 * inner, D, D, l.fold_qkv, l.fold_qkv_cs);
@@ -250,7 +252,7 @@ static void finalize_muse(Ctx& c) {
             fold(l.ff_w1_geglu, l.ff_g0, 2 * c.Fpad, D, D, l.fold_w1, l.fold_w1_cs);
         }
     }
-    c.split_weight(c.pf(p + "to_logits.weight"), (long)g.vocab_size * D);
+    c.split_weight(c.pf(p + "to_logits.weight"), (long)g.vocab_size * D, true);
     // attention bias matrices with the null-key column
     c.NkS_pad = (int)round_up(c.N + 1, 32);
     c.NkC_pad = (int)round_up(c.K + 1, 32);

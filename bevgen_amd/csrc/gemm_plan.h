@@ -132,7 +132,8 @@ inline GldsLaunch glds_plan_range(const GemmArgs& g_in, const GldsSwitches& sw, 
     // every segment refills the three-stage ring, and the workgroup that holds a tile's last k range merges while its peers idle - together more than the empty part of
     // the last round they remove.  $BEVGEN_GEMM_SK=1 routes by glds_sk_pays, 2 takes the form whenever a workspace is given (the operator tests force it per call).
     // (xcd_ok launches a probe kernel on its first use per device: it is asked last, only when every other precondition holds)
-    if (g.sk_ws && (sw.sk || g.sk_force) && g.mode == MODE_PLAIN && g.ksplit <= 1 && g.m_base == 0 && !g.no_row_split && !g.bias_m && !g.ln_in_gsums && xcd_ok() &&
+    // (a single-product launch never takes it: the stream-K kernel has no single-product instantiation)
+    if (g.sk_ws && (sw.sk || g.sk_force) && !g.a_hi_only && g.mode == MODE_PLAIN && g.ksplit <= 1 && g.m_base == 0 && !g.no_row_split && !g.bias_m && !g.ln_in_gsums && xcd_ok() &&
         (sw.sk == 2 || g.sk_force || glds_sk_pays(sw, g.M, g.N))) {
         g.sk_tiles = cdiv(g.M, 256) * cdiv(g.N, kGldsBN);
         const long units = (long)g.sk_tiles * (g.K / kGldsBK);

@@ -189,6 +189,7 @@ __global__ __launch_bounds__(256, 2) void gemm_split_kernel(GemmArgs g) {
             for (int i = 0; i < 2; ++i)
 #pragma unroll
                 for (int j = 0; j < 2; ++j) accM[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[i], bh[j], accM[i][j], 0, 0, 0);
+            if (g.a_hi_only) continue;   // single-product mode (wave-uniform: a kernel argument): f16(A) f16(B)^T, the correction accumulators stay zero
 #pragma unroll
             for (int i = 0; i < 2; ++i)
 #pragma unroll
@@ -239,6 +240,8 @@ void launch_gemm_split(const GemmArgs& g_in, hipStream_t stream) {
         if (g.conv_win == 0) g.conv_win = g.conv_up ? g.conv_w / 2 : g.conv_w;
     }
     BG_REQUIRE(g.B_hi && g.B_lo, "gemm_split: the B operand has not been split");
+    BG_REQUIRE(!g.a_hi_only || (g.mode == MODE_PLAIN && g.b_lo_zero), "gemm_split: a single-product launch needs a plain GEMM and a weight rounded to f16 (mode=%d b_lo_zero=%d)", g.mode,
+               (int)g.b_lo_zero);
     g.status = status_current();
     BG_REQUIRE(g.K % SBK == 0 && g.lda % 4 == 0 && g.ldb % 8 == 0, "gemm_split: K %% 32, lda %% 4, ldb %% 8 required (K=%d lda=%d ldb=%d)", g.K, g.lda, g.ldb);
     BG_REQUIRE(g.batch == 1 || g.strideB == 0, "gemm_split: batched B operands are not split");

@@ -109,6 +109,8 @@ __device__ __forceinline__ void wait_tiles_x(int n) {
 
 // W16: the B operand (a weight matrix) is f16-representable, its low plane is zero: the product is  b_hi a_hi + 2^-11 b_hi a_lo  - TWO MFMAs per
 // k-step pair instead of three, and no low-plane fragment reads (weight_dtype = f16 contexts)
+// A16 (only with W16): single-product mode (GemmArgs::a_hi_only) - the product is  b_hi a_hi  alone: ONE MFMA per k-step pair, the A low-plane fragments are not read from LDS
+// either (the DMA still moves whole lines: the plane writers are unchanged).  The correction accumulators stay zero, so everything behind the k loop is the W16 code.
 // KS: the k range is cut into gridDim.z slices (small-M problems; a template flag so that the throughput instantiations carry none of it - the 256-row convolution
 // variant sits at the register limit and spilled 300 VGPRs with the slice arithmetic compiled in)
 // TI: 32-row MFMA tiles per wave along M.  2 = the 64x64 wave patch.  1 = a 32x64 patch, twice the waves on the same block tile: the shape of a block that has its CU
@@ -121,13 +123,14 @@ __device__ __forceinline__ void wait_tiles_x(int n) {
 // sk_role (stream-K launches, gemm_split_glds_sk_kernel below): 0 = the whole k range of the tile is here: the normal epilogue; 1 = a PART of the tile's k range whose last
 // part lies with a later workgroup: the raw tile sums go to this workgroup's slot of g.sk_ws and its flag is raised; 2 = the LAST part: the sums of the workgroups
 // sk_first .. blockIdx.x - 1 (ascending k) are added in that order, then the normal epilogue.
-template <int MODE, int WM, int S, bool W16, bool KS, int TI, int TJ, bool SKK = false>
+template <int MODE, int WM, int S, bool W16, bool KS, int TI, int TJ, bool SKK = false, bool A16 = false>
 __device__ __forceinline__ void gemm_tile(const GemmArgs& g, const int tx, const int ty, const int kt_first, const int nk, const int ksl, const int kz, const int sk_role,
                                           const int sk_first, const int tid
 #ifdef BEVGEN_GEMM_TRACE
                                           , unsigned long long* gt
 #endif
                                           ) {
+    static_assert(!A16 || (W16 && MODE == MODE_PLAIN && !SKK), "single-product instantiations: rounded weight, plain GEMM, not the stream-K kernel");
     constexpr int TBM = WM * 64;                 // block rows
     constexpr int NW = WM * 8 / (TI * TJ);       // waves
     constexpr int WROWS = TI * 32;               // rows of a wave's patch
@@ -279,7 +282,7 @@ __device__ __forceinline__ void gemm_tile(const GemmArgs& g, const int tx, const
 #pragma unroll
         for (int i = 0; i < TI; ++i) {
             f.h[i] = *reinterpret_cast<const half8*>(smem_g + hi + (half * TI + i) * T16);
-            f.l[i] = *reinterpret_cast<const half8*>(smem_g + lo + (half * TI + i) * T16);
+            if (!A16) f.l[i] = *reinterpret_cast<const half8*>(smem_g + lo + (half * TI + i) * T16);
         }
     };
     auto fetch_b = [&](int stage, int jg) {   // column tiles [jg TJ, (jg + 1) TJ)
@@ -293,7 +296,7 @@ __device__ __forceinline__ void gemm_tile(const GemmArgs& g, const int tx, const
     // The products of row half `half` x column group jg.  Per output element and k-tile the order is main += (Bh, Ah); corr += (Bl, Ah); corr += (Bh, Al) - callers issue
     // part 0, 1, 2 of a (half, jg) in that order, in every phase of the pipeline and in every instantiation (the bit-identity of the row-split / CONV3S launches).
     auto mma = [&](const AFrag& a, int half, int jg, int part) {
-        if (part == 1 && W16) return;
+        if ((part == 1 && W16) || (part == 2 && A16)) return;
 #pragma unroll
         for (int jj = 0; jj < TJ; ++jj)
 #pragma unroll
@@ -322,7 +325,7 @@ __device__ __forceinline__ void gemm_tile(const GemmArgs& g, const int tx, const
         for (int i = 0; i < 2; ++i) {
             if (i < TI) {
                 f.ah[i] = *reinterpret_cast<const half8*>(st + a_rd[i][ks]);
-                f.al[i] = *reinterpret_cast<const half8*>(st + (a_rd[i][ks] ^ 32));
+                if (!A16) f.al[i] = *reinterpret_cast<const half8*>(st + (a_rd[i][ks] ^ 32));
             }
             if (i < TJ) {
                 f.bh[i] = *reinterpret_cast<const half8*>(st + b_rd[i][ks]);
@@ -344,6 +347,7 @@ __device__ __forceinline__ void gemm_tile(const GemmArgs& g, const int tx, const
             for (int j = 0; j < TJ; ++j) accC[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(f.bl[j], f.ah[i], accC[i][j], 0, 0, 0);
     };
     auto mma_c2 = [&](const Frag& f) {
+        if (A16) return;
 #pragma unroll
         for (int i = 0; i < TI; ++i)
 #pragma unroll
@@ -1314,7 +1318,7 @@ __device__ __forceinline__ void gemm_tile(const GemmArgs& g, const int tx, const
 }
 
 
-template <int MODE, int WM, int S, bool W16 = false, bool KS = false, int TI = 2, int TJ = 2>
+template <int MODE, int WM, int S, bool W16 = false, bool KS = false, int TI = 2, int TJ = 2, bool A16 = false>
 __global__ __launch_bounds__(WM * 512 / (TI * TJ), (WM == 2 && S == 2) ? 2 : 1) void gemm_split_glds_kernel(GemmArgs g) {
     int tx, ty;
     if (g.tile_band > 0) xcd_tile_banded(gridDim.x, gridDim.y, g.tile_band, tx, ty);
@@ -1326,7 +1330,7 @@ __global__ __launch_bounds__(WM * 512 / (TI * TJ), (WM == 2 && S == 2) ? 2 : 1) 
 #ifdef BEVGEN_GEMM_TRACE
     unsigned long long gt[5] = {};
     gt[0] = __builtin_amdgcn_s_memrealtime();
-    gemm_tile<MODE, WM, S, W16, KS, TI, TJ>(g, tx, ty, kt_first, nk, ksl, kz, 0, 0, (int)threadIdx.x, gt);
+    gemm_tile<MODE, WM, S, W16, KS, TI, TJ, false, A16>(g, tx, ty, kt_first, nk, ksl, kz, 0, 0, (int)threadIdx.x, gt);
     if (MODE == MODE_PLAIN && !KS) {
         gt[3] = __builtin_amdgcn_s_memrealtime();
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -1345,7 +1349,7 @@ __global__ __launch_bounds__(WM * 512 / (TI * TJ), (WM == 2 && S == 2) ? 2 : 1) 
         }
     }
 #else
-    gemm_tile<MODE, WM, S, W16, KS, TI, TJ>(g, tx, ty, kt_first, nk, ksl, kz, 0, 0, (int)threadIdx.x);
+    gemm_tile<MODE, WM, S, W16, KS, TI, TJ, false, A16>(g, tx, ty, kt_first, nk, ksl, kz, 0, 0, (int)threadIdx.x);
 #endif
 }
 
@@ -1448,6 +1452,16 @@ constexpr GldsKernel glds_kernel() {
 #define BG_GLDS_KERNEL(...) glds_kernel<__VA_ARGS__>(),
 static const GldsKernel kGldsKernels[kGldsVariantCount] = {BG_GLDS_VARIANTS(BG_GLDS_KERNEL)};
 #undef BG_GLDS_KERNEL
+// ... and the single-product table (GemmArgs::a_hi_only), expanded from the same list so that one index serves both: entry i runs kGldsVariants[i] with A16 where that tuple
+// is a W16 plain GEMM, and is null elsewhere - a convolution (the VQGAN never runs single-product) and the stream-K form (gemm_plan.h does not route there) have none
+template <int MODE, int WM, int S, bool W16, bool KS, int TI, int TJ, bool SK>
+constexpr GldsKernel glds_kernel_a16() {
+    if constexpr (W16 && !SK && MODE == MODE_PLAIN) return gemm_split_glds_kernel<MODE, WM, S, true, KS, TI, TJ, true>;
+    else return nullptr;
+}
+#define BG_GLDS_KERNEL(...) glds_kernel_a16<__VA_ARGS__>(),
+static const GldsKernel kGldsKernelsA16[kGldsVariantCount] = {BG_GLDS_VARIANTS(BG_GLDS_KERNEL)};
+#undef BG_GLDS_KERNEL
 
 void launch_gemm_split_glds(const GemmArgs& g_in, hipStream_t stream) {
     static std::atomic<int> cu_count[kMaxDevices];
@@ -1460,10 +1474,13 @@ void launch_gemm_split_glds(const GemmArgs& g_in, hipStream_t stream) {
         HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
         cu_count[dslot].store(cus, std::memory_order_release);
     }
+    BG_REQUIRE(!g_in.a_hi_only || (g_in.b_lo_zero && g_in.mode == MODE_PLAIN),
+               "gemm_split_glds: a single-product launch needs a plain GEMM and a weight whose low plane is known to be zero (mode=%d b_lo_zero=%d)", g_in.mode, (int)g_in.b_lo_zero);
     GldsPlan plan = plan_gemm_split_glds(g_in, glds_switches(), cus, &xcd_placement_verified);
-    if (!attr_set[dslot].load(std::memory_order_acquire)) {   // the > 64 KB dynamic-LDS opt-in of every variant, once per device
+    if (!attr_set[dslot].load(std::memory_order_acquire)) {   // the > 64 KB dynamic-LDS opt-in of every variant of both tables, once per device
         for (int i = 0; i < kGldsVariantCount; ++i)
-            HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kGldsKernels[i]), hipFuncAttributeMaxDynamicSharedMemorySize, (int)glds_lds_max(kGldsVariants[i])));
+            for (const GldsKernel kern : {kGldsKernels[i], kGldsKernelsA16[i]})
+                if (kern) HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)glds_lds_max(kGldsVariants[i])));
         attr_set[dslot].store(true, std::memory_order_release);
     }
     unsigned* const status = status_current();
@@ -1471,10 +1488,13 @@ void launch_gemm_split_glds(const GemmArgs& g_in, hipStream_t stream) {
         GldsLaunch& l = plan.l[i];
         const int k = glds_variant_index(l.v);
         BG_REQUIRE(k >= 0, "gemm_split_glds: no instantiation <%d,%d,%d,w16=%d,ks=%d,%d,%d>%s", l.v.mode, l.v.wm, l.v.s, (int)l.v.w16, (int)l.v.ks, l.v.ti, l.v.tj, l.v.sk ? " (stream-K)" : "");
+        const GldsKernel kern = l.g.a_hi_only ? kGldsKernelsA16[k] : kGldsKernels[k];
+        BG_REQUIRE(kern != nullptr, "gemm_split_glds: no single-product instantiation <%d,%d,%d,w16=%d,ks=%d,%d,%d>%s", l.v.mode, l.v.wm, l.v.s, (int)l.v.w16, (int)l.v.ks, l.v.ti, l.v.tj,
+                   l.v.sk ? " (stream-K)" : "");
         l.g.status = status;
         ProfScope prof(l.prof_kind, l.work, stream);
         void* args[] = {&l.g};
-        HIP_CHECK(hipLaunchKernel(reinterpret_cast<const void*>(kGldsKernels[k]), l.grid, dim3(l.threads), args, l.lds, stream));
+        HIP_CHECK(hipLaunchKernel(reinterpret_cast<const void*>(kern), l.grid, dim3(l.threads), args, l.lds, stream));
         LAUNCH_CHECK();
         if (l.reduce_after) launch_splitk_reduce(l.g, l.g.kpart, l.g.ksplit, stream);
     }

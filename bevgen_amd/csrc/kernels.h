@@ -34,6 +34,9 @@ struct GemmArgs {
     const uint16_t* B_hi = nullptr;
     const uint16_t* B_lo = nullptr;
     bool b_lo_zero = false;   // B's low plane is all zeros (f16-rounded weight): the LDS-DMA kernel skips the b_lo a_hi product
+    // single-product mode (BEVGEN_PRECISION_F16X1, Route M only): the product is f16(A) f16(B)^T with fp32 accumulation - A's low plane is neither read from LDS nor
+    // multiplied.  The LDS-DMA kernel needs b_lo_zero with it (its single-product instantiations are the W16 ones); gemm_split_kernel drops both correction products
+    bool a_hi_only = false;
     // LDS-DMA path (gemm_split_glds.hip): A also arrives as interleaved (hi, lo) f16 planes ([M][lda/32][2][32] / NHWC pixels x channels),
     // written by the producing kernel; A_lo = A_hi + 32
     const uint16_t* A_hi = nullptr;
@@ -117,6 +120,9 @@ void launch_gemm_split(const GemmArgs& g, hipStream_t stream);
 void launch_split_weight(const float* w, void* planes /* 2n halves, interleaved (gemm_split.hip) */, long n, hipStream_t s);
 // Table of pre-split weights of the context whose call is executing (null = exact fp32 everywhere): launch_gemm consults it by B pointer.
 void split_registry_set(const void* table /* const std::unordered_map<const float*, SplitPlanes>* */);
+// Single-product mode of the calling thread's current call (GemmArgs::a_hi_only on every launch that launch_gemm resolves through the table); returns the previous value.
+// Per thread like the table; set only by the Route M entry points of a BEVGEN_PRECISION_F16X1 context (api.cpp), cleared at every C-ABI entry.
+bool split_single_product_set(bool on);
 
 // Skinny GEMM for decode steps (M <= 64 rows, weight-streaming bound): C[M,N] = A[M,K] B[N,K]^T + bias, act, residual
 int gemm_skinny_ksplit(int M, int N, int K);

@@ -138,7 +138,8 @@ struct Ctx {
 
     // ---- split-precision mode (BEVGEN_PRECISION_F16X3): (hi, lo) f16 planes of every GEMM / conv weight, keyed by its fp32 device pointer
     std::unordered_map<const float*, SplitPlanes> split;
-    void split_weight(const float* w, long n);
+    bool single_product = false;   // created with BEVGEN_PRECISION_F16X1 (cfg.precision then reads F16X3): the Route M projections run one MFMA per product (api.cpp, bevgen_hip.h)
+    void split_weight(const float* w, long n, bool route_m = false);   // route_m: a Route M projection matrix (rounded to f16 in a single-product context as well)
 
     Profiler prof;   // per-launch HIP-event timing (bevgen_profile_begin / _end) of THIS context
 

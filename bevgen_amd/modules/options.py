@@ -5,10 +5,14 @@ every reference constructor on the path ends in ``**kwargs`` (gpt:270, ar_lm:55,
 option is: a key next to the ``_target_`` (``+model.transformer.kv_cache=f16`` on the command line), or process-wide by an environment variable.
 
     key             env var                  values                 drop-in default
-    precision       $BEVGEN_PRECISION        fp32 | f16x3 | f16x3r  f16x3   (3 f16 MFMAs per product on hi/lo splits, fp32 accumulate; token-exact on every fixture;
+    precision       $BEVGEN_PRECISION        fp32 | f16x3 | f16x3r | f16x1  f16x3   (3 f16 MFMAs per product on hi/lo splits, fp32 accumulate; token-exact on every fixture;
                                                                             f16x3r = f16x3 whose VQGAN (decoder and encoder) rescales an un-normalised activation outside the
                                                                             f16 range by a per-tensor power of two instead of refusing the checkpoint - MaskGit and Route A
-                                                                            treat it exactly as f16x3)
+                                                                            treat it exactly as f16x3;
+                                                                            f16x1 = f16x3 whose MaskGit projections compute f16(A) f16(W)^T, ONE MFMA per product, on
+                                                                            matrices rounded to f16 at load whatever `weights` says: activations keep 11 significant bits
+                                                                            per call (the reference's bf16 autocast: 8), tokens are no longer those of the fp32 model -
+                                                                            the VQGAN and Route A treat it exactly as f16x3)
     weights         $BEVGEN_WEIGHTS          f32 | f16              f32     (f16: GEMM / conv matrices rounded once at load, two MFMAs per product)
     kv_cache        $BEVGEN_KV_CACHE         f32 | f16              f32     (Route A; f16 = fp16 storage / fp32 accumulate: BASELINE config 4)
     decode_weights  $BEVGEN_DECODE_WEIGHTS   f32 | f16              f32     (Route A decode step streams 2-byte q/k/v, MLP and head weights)
@@ -23,7 +27,7 @@ import os
 from typing import Dict, Mapping, MutableMapping, Optional
 
 CHOICES = {
-    "precision": ("fp32", "f16x3", "f16x3r"),
+    "precision": ("fp32", "f16x3", "f16x3r", "f16x1"),
     "weights": ("f32", "f16"),
     "kv_cache": ("f32", "f16"),
     "decode_weights": ("f32", "f16"),

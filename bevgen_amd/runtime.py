@@ -73,12 +73,14 @@ class Context:
                              ("decode_weights", decode_weights, ("f32", "f16"))):
             if val not in ok:
                 raise ValueError(f"{key} must be one of {ok}, got {val!r}")
-        if precision not in ("fp32", "f16x3", "f16x3r"):
-            raise ValueError(f"precision must be 'fp32', 'f16x3' or 'f16x3r', got {precision!r}")
+        if precision not in ("fp32", "f16x3", "f16x3r", "f16x1"):
+            raise ValueError(f"precision must be 'fp32', 'f16x3', 'f16x3r' or 'f16x1', got {precision!r}")
         self.precision = precision
         # 'f16x3r' ("range-safe") = f16x3 whose VQGAN decoder and encoder rescale their un-normalised activations by a per-tensor power of two instead of refusing a
         # checkpoint whose residual stream leaves the f16 range (bevgen_cfg.vq_range); the transformer routes behave exactly as under 'f16x3'
-        c.precision = {"fp32": _lib.PRECISION_FP32, "f16x3": _lib.PRECISION_F16X3, "f16x3r": _lib.PRECISION_F16X3}[precision]
+        # 'f16x1' ("single product") = f16x3 whose Route M projections compute f16(A) f16(W)^T, one MFMA per product, on matrices rounded to f16 at finalize whatever
+        # `weights` says (BEVGEN_PRECISION_F16X1 in bevgen_hip.h); the VQGAN and Route A behave exactly as under 'f16x3'
+        c.precision = {"fp32": _lib.PRECISION_FP32, "f16x3": _lib.PRECISION_F16X3, "f16x3r": _lib.PRECISION_F16X3, "f16x1": _lib.PRECISION_F16X1}[precision]
         c.vq_range = 1 if precision == "f16x3r" else 0
         c.max_batch = max_batch
         # Route A KV-cache storage: 'f32' (bit-exact tokens) or 'f16' (fp16 storage / fp32 accumulate, BASELINE config 4: half the decode traffic)

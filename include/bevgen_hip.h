@@ -35,8 +35,17 @@ extern "C" {
 enum { BEVGEN_ROUTE_MASKGIT = 0, BEVGEN_ROUTE_AR = 1 };
 /* FP32  : every product and accumulation in exact fp32 on the matrix cores (v_mfma_f32_32x32x2_f32) - bit-exact greedy tokens vs the CPU reference.
  * F16X3 : large GEMMs / convolutions as 3 f16 MFMAs per k-step on (hi, lo*2^-11) splits of the fp32 operands: ~2^-22 relative error per product,
- *         fp32 accumulation, up to 5x the fp32 MFMA rate.  Everything else (attention, norms, samplers, decode-step GEMMs) stays fp32. */
-enum { BEVGEN_PRECISION_FP32 = 0, BEVGEN_PRECISION_BF16 = 1 /* reserved */, BEVGEN_PRECISION_F16X3 = 2 };
+ *         fp32 accumulation, up to 5x the fp32 MFMA rate.  Everything else (attention, norms, samplers, decode-step GEMMs) stays fp32.
+ * F16X1 : "single product", an opt-in trade of accuracy for matrix instructions on Route M.  The context is an F16X3 context in everything (VQGAN, Route A, attention,
+ *         range policy: |v| >= 65520 raises BEVGEN_STATUS_F16_RANGE) except that every Route M projection that multiplies pre-split operands - to_q, to_kv, the merged
+ *         self-attention q|k|v, to_out, both feed-forward matrices, to_logits, their split-K forms, and whatever Route M sends through the on-the-fly-split kernel -
+ *         computes f16(A) f16(W)^T with fp32 accumulation: ONE MFMA per product.  bevgen_finalize rounds those matrices to f16 in place whatever weight_dtype says and
+ *         builds no LayerNorm fold constants (as under BEVGEN_W_F16); the VQGAN's convolutions keep following weight_dtype.  Epilogues (bias, GELU, residual, the q /
+ *         q|k|v / k|v preparation, GEGLU) and the plane writers are unchanged; the attention kernel keeps its three products (its loop is bound by the softmax phase, not
+ *         by the matrix phase).  The mode reaches a launch only from bevgen_muse_forward, bevgen_maskgit_generate and bevgen_maskgit_generate_ex.  Activations are
+ *         rounded to 11 significant bits on every call, where the reference's bf16 autocast keeps 8.  (A value of this enum and not a word of bevgen_cfg.reserved[]: a
+ *         library that does not know the mode refuses the context instead of running it with three products.) */
+enum { BEVGEN_PRECISION_FP32 = 0, BEVGEN_PRECISION_BF16 = 1 /* reserved */, BEVGEN_PRECISION_F16X3 = 2, BEVGEN_PRECISION_F16X1 = 3 };
 enum { BEVGEN_KV_F32 = 0, BEVGEN_KV_F16 = 1 };
 enum { BEVGEN_DECODE_FUSED = 0, BEVGEN_DECODE_PER_OP = 1, BEVGEN_DECODE_SPLIT = 2, BEVGEN_DECODE_AUTO = 3 };
 enum { BEVGEN_W_F32 = 0, BEVGEN_W_F16 = 1 };
@@ -290,7 +299,9 @@ int bevgen_vq_range_exponents(bevgen_ctx* ctx, int32_t* h_out, int cap, int* cou
  * Operator-level entry points (parity tests and roofline measurements call the kernels through these)             */
 int bevgen_op_gemm(bevgen_ctx* ctx, const float* d_a, const float* d_w, const float* d_bias, const float* d_residual, float* d_c,
                    int M, int N, int K, int act_gelu, int skinny, void* stream);            /* C = A W^T (+bias)(gelu)(+res); skinny: 0 tiled fp32, 1 M <= 64, 2-4 split-precision
-                                                                                               kernels (tests / probes), 5 = 3 with the k range split over three slices, 6 = 3 in its stream-K form */
+                                                                                               kernels (tests / probes), 5 = 3 with the k range split over three slices, 6 = 3 in its stream-K form;
+                                                                                               single-product (BEVGEN_PRECISION_F16X1) forms, w's low plane ignored: 7 = 4 computing
+                                                                                               f16(A) f16(W)^T, 8 = 7 with the k range in three slices, 9 = 2 single-product */
 /* Decode-step projection (decode_fused.hip): C = act(LayerNorm?(A) W^T + bias) for M <= 64 rows; d_ln_w NULL = no LayerNorm; ksplit > 1 (no LayerNorm, no bias / act):
  * d_c receives the split-K partial sums [ksplit, M, N] that the consumer adds; ksplit 0 = the library's choice for (N, K), returned through *ksplit_out if non-NULL;
  * ksplit -1 (LayerNorm with beta and bias): one K slice, the LayerNorm folded into the product the way the decode step launches ln2 + MLP-up. */
