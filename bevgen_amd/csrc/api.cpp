@@ -17,7 +17,6 @@ static int guarded(bevgen_ctx* ctx, F&& f, bool check_first = true) {
         if (!ctx) return BEVGEN_ERR_INVALID;
         HIP_CHECK(hipSetDevice(ctx->device));
         split_registry_set(ctx->cfg.precision == BEVGEN_PRECISION_F16X3 ? &ctx->split : nullptr);
-        split_single_product_set(false);   // (only the Route M entry points below turn it on, for their own call)
         struct CurrentProf {   // this context's profiler and status word receive the launch records / flags of this call (restored on every exit path)
             Profiler* old;
             unsigned* old_st;
@@ -36,13 +35,6 @@ static int guarded(bevgen_ctx* ctx, F&& f, bool check_first = true) {
         return BEVGEN_ERR_INTERNAL;
     }
 }
-
-// Route M entry points of a BEVGEN_PRECISION_F16X1 context: this thread's launches through the split table carry GemmArgs::a_hi_only until the call returns
-struct SingleProductScope {
-    bool old;
-    explicit SingleProductScope(const bevgen_ctx* c) : old(split_single_product_set(c->single_product)) {}
-    ~SingleProductScope() { split_single_product_set(old); }
-};
 
 static void need_final(bevgen_ctx* c) {
     if (!c->finalized) fail(BEVGEN_ERR_STATE, "bevgen_finalize must be called after loading tensors and before compute calls");
@@ -145,8 +137,7 @@ int bevgen_muse_forward(bevgen_ctx* ctx, const int64_t* ids, const int64_t* cond
         need_final(ctx);
         BG_REQUIRE(ids && cond && I_inv && E_inv, "muse_forward: null input");
         BG_REQUIRE(B >= 1 && (ctx->cfg.max_batch <= 0 || B <= ctx->cfg.max_batch), "muse_forward: batch %d exceeds max_batch %d", B, ctx->cfg.max_batch);
-        const SingleProductScope sp(ctx);
-        muse_forward(*ctx, ids, cond, I_inv, E_inv, B, logits, embed, (hipStream_t)stream);
+        muse_forward(*ctx, MuseBatch{cond, I_inv, E_inv, B}, ids, logits, embed, (hipStream_t)stream);
     });
 }
 
@@ -167,9 +158,8 @@ int bevgen_maskgit_generate_ex(bevgen_ctx* ctx, const int64_t* cond, const float
         for (int i = 0; i < timesteps; ++i)
             BG_REQUIRE(sched[i] >= 1 && sched[i] <= ctx->cfg.cam_latent_h * ctx->cfg.cam_latent_w, "maskgit_generate: mask_schedule[%d]=%d out of range", i, sched[i]);
         BG_REQUIRE(samples_per_layout >= 1 && B % samples_per_layout == 0, "maskgit_generate: batch %d is not a multiple of samples_per_layout %d", B, samples_per_layout);
-        const SingleProductScope sp(ctx);
-        maskgit_generate(*ctx, cond, I_inv, E_inv, B, timesteps, sched, temperature, topk_k, critic_noise_scale, gumbel_u, critic_u, init_ids, out, (hipStream_t)stream, noise_seed,
-                         score_mode, samples_per_layout);
+        const MaskgitSampling sp{timesteps, sched, temperature, topk_k, critic_noise_scale, gumbel_u, critic_u, init_ids, noise_seed, score_mode};
+        maskgit_generate(*ctx, MuseBatch{cond, I_inv, E_inv, B, samples_per_layout}, sp, out, (hipStream_t)stream);
     });
 }
 

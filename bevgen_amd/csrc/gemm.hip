@@ -184,8 +184,6 @@ __global__ __launch_bounds__(256, 2) void gemm_f32_kernel(GemmArgs g) {
 // per calling thread (like the profiler hook): set by every entry point for the context it runs, so two contexts driven from two host threads do not see each other's table
 static thread_local const std::unordered_map<const float*, SplitPlanes>* g_split_table = nullptr;
 void split_registry_set(const void* table) { g_split_table = reinterpret_cast<const std::unordered_map<const float*, SplitPlanes>*>(table); }
-static thread_local bool g_single_product = false;
-bool split_single_product_set(bool on) { const bool old = g_single_product; g_single_product = on; return old; }
 
 void launch_gemm(const GemmArgs& g_in, hipStream_t stream) {
     const GemmArgs g = conv_defaults(g_in);
@@ -196,8 +194,7 @@ void launch_gemm(const GemmArgs& g_in, hipStream_t stream) {
             GemmArgs s = g;
             s.B_hi = it->second.hi;
             s.B_lo = it->second.lo;
-            s.b_lo_zero = it->second.lo_zero;
-            s.a_hi_only = g_single_product;   // (a Route M call of a single-product context: the launchers refuse the flag on a convolution or an unrounded weight)
+            s.b_lo_zero = it->second.lo_zero;   // (a_hi_only stays as the caller set it: the launchers refuse the flag on a convolution or an unrounded weight)
             if (s.A_hi) return launch_gemm_split_glds(s, stream);
             return launch_gemm_split(s, stream);
         }

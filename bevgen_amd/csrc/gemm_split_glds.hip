@@ -1416,11 +1416,11 @@ namespace bevgen {
 static_assert(kGldsBN == GBN && kGldsBK == GBK, "gemm_plan.h plans for the block tile of this file's kernels");
 
 // The launcher's A/B switches: read once per process (the tests that pin one run in subprocesses).  Meaning and measurements: with each rule in gemm_plan.h; table in DESIGN.md.
-static const GldsSwitches& glds_switches() {
+const GldsSwitches& glds_switches() {
     static const GldsSwitches sw = [] {
         const auto env = [](const char* name, int dflt) { const char* v = getenv(name); return v ? atoi(v) : dflt; };
         GldsSwitches s;
-        s.sk = env("BEVGEN_GEMM_SK", 0);                  // stream-K form: 0 never (unless forced per call), 1 where gemm_sk_pays, 2 whenever a workspace is given
+        s.sk = env("BEVGEN_GEMM_SK", 0);                  // stream-K form: 0 never (unless forced per call), 1 where glds_sk_pays, 2 whenever a workspace is given
         s.rpf = env("BEVGEN_GEMM_RPF", 1);                // residual prefetch in the k loop's tail (0: off, for A/B runs; profiles/r06_ab_gemm_rpf.txt)
         s.rme = env("BEVGEN_GEMM_RME", 1);                // row-major store form of the plain epilogue (0: accumulator-layout stores, A/B runs)
         s.band = env("BEVGEN_GEMM_BAND", 0);              // > 0: band height of the XCD-aware tile order (default 4)
@@ -1435,11 +1435,6 @@ static const GldsSwitches& glds_switches() {
         return s;
     }();
     return sw;
-}
-
-bool gemm_sk_pays(long rows, int N, int K) {
-    (void)K;
-    return glds_sk_pays(glds_switches(), rows, N);
 }
 
 // gemm_plan.h's variant list as kernels: entry i runs kGldsVariants[i]

@@ -101,7 +101,7 @@ struct GemmArgs {
     void* sk_ws = nullptr;
     unsigned sk_epoch = 0;
     int sk_tiles = 0;                 // filled in by the launcher
-    bool sk_force = false;            // take the stream-K form whatever gemm_sk_pays says (operator tests)
+    bool sk_force = false;            // take the stream-K form whatever glds_sk_pays says (operator tests)
     int ln_rows = 0;                  // row stride of the producer's statistics array (the whole problem's rows: a row-split launch keeps indexing by absolute row)
 };
 // (sum, sum of squares) per (32 columns, row) [groups][rows][2] -> (mean, rstd) per row [rows][2]; `count` real columns (the zero padding of a padded row adds nothing to either sum)
@@ -112,7 +112,8 @@ void launch_gemm(const GemmArgs& g, hipStream_t stream);
 void launch_gemm_split_glds(const GemmArgs& g, hipStream_t stream);
 bool xcd_placement_verified();                            // decode_fused.hip: workgroup i of a launch runs on XCD i % 8 on the current device (probed once)
 size_t gemm_sk_ws_bytes();                                // workspace of a stream-K launch (GemmArgs::sk_ws)
-bool gemm_sk_pays(long rows, int N, int K);               // the launcher's rule: does the 256-row tiling leave enough of its last round empty for the stream-K form to win
+struct GldsSwitches;
+const GldsSwitches& glds_switches();                      // the LDS-DMA launcher's A/B switches (gemm_plan.h), read once per process (gemm_split_glds.hip)
 
 // Split-precision (3x f16 MFMA, fp32-class accuracy) variant and its weight preparation
 struct SplitPlanes { const uint16_t* hi; const uint16_t* lo; bool lo_zero = false; /* the matrix was rounded to f16: its low plane is all zeros */ };
@@ -120,9 +121,7 @@ void launch_gemm_split(const GemmArgs& g, hipStream_t stream);
 void launch_split_weight(const float* w, void* planes /* 2n halves, interleaved (gemm_split.hip) */, long n, hipStream_t s);
 // Table of pre-split weights of the context whose call is executing (null = exact fp32 everywhere): launch_gemm consults it by B pointer.
 void split_registry_set(const void* table /* const std::unordered_map<const float*, SplitPlanes>* */);
-// Single-product mode of the calling thread's current call (GemmArgs::a_hi_only on every launch that launch_gemm resolves through the table); returns the previous value.
-// Per thread like the table; set only by the Route M entry points of a BEVGEN_PRECISION_F16X1 context (api.cpp), cleared at every C-ABI entry.
-bool split_single_product_set(bool on);
+// (GemmArgs::a_hi_only passes through the lookup as the caller set it: muse.cpp sets it on every GemmArgs of a BEVGEN_PRECISION_F16X1 context, no other model code does)
 
 // Skinny GEMM for decode steps (M <= 64 rows, weight-streaming bound): C[M,N] = A[M,K] B[N,K]^T + bias, act, residual
 int gemm_skinny_ksplit(int M, int N, int K);

@@ -138,7 +138,7 @@ struct Ctx {
 
     // ---- split-precision mode (BEVGEN_PRECISION_F16X3): (hi, lo) f16 planes of every GEMM / conv weight, keyed by its fp32 device pointer
     std::unordered_map<const float*, SplitPlanes> split;
-    bool single_product = false;   // created with BEVGEN_PRECISION_F16X1 (cfg.precision then reads F16X3): the Route M projections run one MFMA per product (api.cpp, bevgen_hip.h)
+    bool single_product = false;   // created with BEVGEN_PRECISION_F16X1 (cfg.precision then reads F16X3): the Route M projections run one MFMA per product (muse.cpp sets GemmArgs::a_hi_only; bevgen_hip.h)
     void split_weight(const float* w, long n, bool route_m = false);   // route_m: a Route M projection matrix (rounded to f16 in a single-product context as well)
 
     Profiler prof;   // per-launch HIP-event timing (bevgen_profile_begin / _end) of THIS context
@@ -190,10 +190,16 @@ void ctx_load_tensor(Ctx& c, const char* name, const void* h, int dtype, int ndi
 void ctx_finalize(Ctx& c);
 void ctx_pack_split_qkv(Ctx& c, hipStream_t s);   // decode_path = auto: QKV operand image of the split decode layer, packed on first need
 // muse.cpp
-void muse_forward(Ctx& c, const int64_t* ids, const int64_t* cond, const float* I_inv, const float* E_inv, int B, float* logits, float* embed, hipStream_t s);
-void maskgit_generate(Ctx& c, const int64_t* cond, const float* I_inv, const float* E_inv, int B, int timesteps, const int32_t* sched, float temperature,
-                      int topk_k, float critic_noise_scale, const float* gumbel_u, const float* critic_u, const int64_t* init_ids, int64_t* out, hipStream_t s,
-                      unsigned long long noise_seed = 0, int score_mode = 0 /* 0 token critic, 1 / 2 softmax confidence (muse_net:611-622) */, int samples_per_layout = 1);
+struct MuseBatch {   // the scenes of a Route M call: condition ids and inverse camera matrices of B scenes, consecutive groups of samples_per_layout sharing their condition
+    const int64_t* cond; const float *I_inv, *E_inv; int B; int samples_per_layout = 1;
+};
+struct MaskgitSampling {   // bevgen_maskgit_generate_ex's sampling arguments (bevgen_hip.h)
+    int timesteps; const int32_t* sched; float temperature; int topk_k; float critic_noise_scale;
+    const float *gumbel_u, *critic_u; const int64_t* init_ids;
+    unsigned long long noise_seed = 0; int score_mode = 0;   // 0 token critic, 1 / 2 softmax confidence (muse_net:611-622)
+};
+void muse_forward(Ctx& c, const MuseBatch& in, const int64_t* ids, float* logits, float* embed, hipStream_t s);
+void maskgit_generate(Ctx& c, const MuseBatch& in, const MaskgitSampling& sp, int64_t* out, hipStream_t s);
 // ar.cpp
 void sparse_self_attention_op(Ctx& c, const float* q, const float* k, const float* v, const int64_t* layout, const float* mask, const float* add, int B, int H,
                               int L, int block, float* out, hipStream_t s);

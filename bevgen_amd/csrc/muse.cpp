@@ -9,7 +9,11 @@
 //   * the attention-bias matrices                                     (built once in bevgen_finalize)
 // and what is dropped: the classifier-free-guidance "null" forwards (bit-identical to the conditional ones in eval mode,
 // muse_net:352) and the critic forward after the last iteration (its scores are never read).
+//
+// A forward (muse_blocks) is the token embedding, the layers in ONE of two precisions - muse_blocks_f32, the exact-fp32 path, or muse_blocks_split, the f16x3 path on
+// (hi, lo) f16 planes - and the final LayerNorm.  Every LDS-DMA projection of the split path ends in project(), which executes the decision of muse_plan.h.
 #include "model.h"
+#include "muse_plan.h"
 
 namespace bevgen {
 
@@ -18,6 +22,7 @@ namespace {
 struct MuseWs {
     int B = 0;
     int S = 1;   // samples per BEV layout: consecutive groups of S scenes share their condition, whose cross-attention K / V exist once per layout
+    bool generate = false;   // the call also needs logits and scores
 
     long rows = 0;
     float *img = nullptr, *c_embed = nullptr, *context = nullptr;
@@ -25,73 +30,63 @@ struct MuseWs {
     std::vector<float*> crossK, crossV;
     float *logits = nullptr, *scores = nullptr;   // generate only
     float *x = nullptr, *xn = nullptr, *qraw = nullptr, *kvraw = nullptr, *Q = nullptr, *Ks = nullptr, *Vs = nullptr, *att = nullptr, *h = nullptr, *g = nullptr;
+    size_t kvS = 0, kvC = 0;   // elements of one self- / cross-attention K (or V) buffer: B (or B / S) x H x Nk_pad x 64
     float* attn_ws = nullptr; int attn_ks = 1;   // key-split self-attention of the low-latency path (pick_attn_ksplit): partial rows of the key ranges
     float* kpart = nullptr;   // split-K partial tiles of the narrow (N = D) projections when the batch is too small to fill the chip (low-latency path)
     float *stats_d = nullptr, *stats_f = nullptr;   // folded LayerNorms: per-(32 columns, row) (sum, sum of squares) of the residual rows [D / 32][rows][2] / of the GEGLU rows [Fpad / 32][rows][2]
     float* rowstat = nullptr;                       // ... merged to (mean, rstd) per row [rows][2] by launch_ln_stats_finalize
     void* sk_ws = nullptr;                          // stream-K workspace of the projections (small batches; flags zeroed in muse_prepare), null = never stream-K
-    unsigned sk_epoch = 0;                          // bumped per projection launch
+    unsigned sk_epoch = 0;                          // bumped per projection launch that carries the workspace
+    // the tensors a forward and the sampling loop need by name, looked up once per call (muse_prepare)
+    const float *token_emb = nullptr, *pos_emb = nullptr, *norm_g = nullptr, *to_logits = nullptr, *critic_w = nullptr, *critic_b = nullptr;
 };
 
-// LayerNorm folded across the GEMMs around it (GemmArgs::ln_*; needs the fold constants of bevgen_finalize: split-precision mode with fp32 weights).
-//   0  the LayerNorm kernels of rounds 1-5 everywhere
-//   1  (default) the feed-forward's INNER LayerNorm (over F = 2730 columns, the widest pass: 3.3 % of the sixteen-scene step) disappears: the GEGLU epilogue writes raw
-//      planes + per-32-column row sums INSTEAD of its fp32 result (no extra bytes), a one-thread-per-row kernel merges the sums (8 bytes read per 32 elements), the
-//      down-projection multiplies by W4 o gamma and applies rstd (acc - mean cs)
-//   2  all four LayerNorms of a layer (the residual-stream projections then write planes + sums BESIDES their fp32 row)
-// Measured, same box, scenes/s at 16 / 2 / 1 scenes per call (profiles/r06_ab_ln_fold.txt): level 0 10.29 / 7.88 / 6.04, level 1 **10.53 / 7.98 / 6.06**, level 2 10.10 / 7.85 /
-// 5.95 - the extra plane stores of the residual-stream epilogues cost more than the LayerNorm passes they replace (round 3 found the same with another design), at
-// every batch size; level 2 stays as a tested switch.  $BEVGEN_LN_FOLD pins the level (A/B runs, tests).
-int ln_fold_level(const Ctx& c, long rows) {
-    const char* e = getenv("BEVGEN_LN_FOLD");   // (read per forward, not cached: the tests switch it inside one process)
-    const int env = e ? atoi(e) : 1;
-    (void)rows;
-    if (c.muse.empty() || !c.muse[0].fold_w4) return 0;
-    return std::max(0, std::min(env, 2));
-}
-
-// Low-latency path (one or two scenes per call, scripts/interactive_editing.py:273-277): a [rows, D] x [D, D] projection is only cdiv(rows, 128) * D / 128 tiles -
-// 96 workgroups at one six-view scene, on 256 CUs.  Its k range is cut into slices until the grid covers the chip; the slices' partial tiles are added in a fixed
-// order (tokens stay identical run to run, and identical to the unsplit path up to fp32 summation order - checked against the B = 16 path in the tests).
-// How many slices (measured at one six-view scene, rows = 1536, tools/gemm_small_probe.py + profiles/r03_gemm_small_*.txt): with the eight-wave small-problem block of
-// gemm_split_glds.hip a [1536, 1024] x [1024, K] projection costs 7.6 us of fixed time (dispatch, pipeline fill from cold operands, store tail) + 0.43 us per k-tile
-// on 96 CUs.  A second slice halves the loop but adds a 6.4 us reduce launch and gives up the fused epilogues (q preparation): a wash at K = 1024 (21.4 vs 20.9 us),
-// a clear gain for a long k loop (K = 5504: 82 -> 51 us).  So: two slices from K = 2048 up, none below - and none where the 128-row grid covers at most half of the CUs:
-// there the launcher's 64-row blocks double the grid without a reduce launch (one-scene down-projection, K = 2752: 37.9 + 7.1 -> 40 us; step 169.9 -> 167.9 ms).  (Round-3 history: with the four-wave
-// block - 12 us + 0.62 us per k-tile - two slices everywhere were the optimum, step 257 -> 241 ms.)
-constexpr int KSPLIT_MAX = 6;
-constexpr long kSkMaxRows = 8192;   // batches up to this many token rows carry a stream-K workspace (gemm_sk_pays decides per projection)
-int ksplit_env() { static const int v = getenv("BEVGEN_KSPLIT") ? atoi(getenv("BEVGEN_KSPLIT")) : 0; return v; }
-int pick_ksplit(long rows, int N, int K) {
-    if ((long)cdiv(rows, 256) * cdiv(N, 128) >= 256) return 1;          // the 256-row tiling already fills the chip
-    const long tiles = (long)cdiv(rows, 128) * cdiv(N, 128);
-    if (tiles >= 160) return 1;
-    int s = (K >= 2048 && tiles > 128) ? 2 : 1;   // (<= 128 tiles: the launcher's 64-row blocks already double the grid, without a reduce: 45 -> 40 us at K = 2752)
-    if (ksplit_env() > 0) s = std::min(KSPLIT_MAX, ksplit_env());
-    while (s > 1 && K / 32 < 2 * s) --s;
+// The switches of muse_plan.h from the environment: ln_fold and ln_merge per call of this function (the tests switch them inside one process), the other four once per process
+MuseSwitches muse_switches() {
+    static const MuseSwitches once = [] {
+        const auto env = [](const char* name, int dflt) { const char* v = getenv(name); return v ? atoi(v) : dflt; };
+        MuseSwitches s;
+        s.qkv_merge = env("BEVGEN_QKV_MERGE", 1);
+        s.qkv_wm4 = env("BEVGEN_QKV_WM4", 1);
+        s.ksplit = env("BEVGEN_KSPLIT", 0);
+        s.attn_ksplit = env("BEVGEN_ATTN_KSPLIT", 0);
+        return s;
+    }();
+    MuseSwitches s = once;
+    const char *fold = getenv("BEVGEN_LN_FOLD"), *merge = getenv("BEVGEN_LN_MERGE");
+    s.ln_fold = fold ? atoi(fold) : 1;
+    s.ln_merge = merge ? (merge[0] == 't' ? 1 : 0) : -1;
     return s;
 }
 
-// Key ranges of the self-attention (same low-latency path): one scene is cdiv(1536, 256) * 16 heads = 96 workgroups on 256 CUs, each walking all 49 key tiles;
-// with the keys cut in two, 192 workgroups walk half of them and a combine kernel merges the pairs.  Only when the ranges stay long (>= 8 tiles each) and the
-// grid leaves at least half of the CUs idle.  $BEVGEN_ATTN_KSPLIT pins it (A/B runs, tests).
-int pick_attn_ksplit(long blocks, int ntiles) {
-    static const int env = getenv("BEVGEN_ATTN_KSPLIT") ? atoi(getenv("BEVGEN_ATTN_KSPLIT")) : 0;
-    if (env > 0) return std::max(1, std::min(std::min(env, 8), ntiles));
-    if (blocks * 2 > 256) return 1;
-    const int ks = std::min(std::min(4, (int)(256 / blocks)), ntiles / 8);
-    return std::max(ks, 1);
-}
+// a buffer that holds the (hi, lo) f16 planes of n elements back to back (same bytes as the fp32 buffer of n elements it replaces): Q, K, V^T of both attentions
+struct Planes { _Float16 *hi, *lo; };
+Planes planes_of(float* buf, size_t n) { _Float16* hi = reinterpret_cast<_Float16*>(buf); return {hi, hi + n}; }
 
-void gemm(const float* A, int lda, const float* W, int ldb, float* C, int ldc, int M, int N, int K, const float* R, int ldr, hipStream_t s) {
+struct In { const float* p = nullptr; int ld = 0; };   // a row-major fp32 matrix and its row stride
+struct Out { float* p = nullptr; int ld = 0; };
+
+// C[M, N] = A[M, K] W[N, K]^T (+ R): what every GEMM of Route M starts from (A: gemm() / on_planes()).  A single-product context (BEVGEN_PRECISION_F16X1) says so here,
+// on every launch - the fp32-A ones (cross to_kv, to_logits) included
+GemmArgs gemm_args(const Ctx& c, In W, Out C, int M, int N, int K, In R = {}) {
     GemmArgs g;
-    g.A = A; g.B = W; g.C = C; g.R = R;
+    g.B = W.p; g.C = C.p; g.R = R.p;
     g.M = M; g.N = N; g.K = K;
-    g.lda = lda; g.ldb = ldb; g.ldc = ldc; g.ldr = ldr;
+    g.ldb = W.ld; g.ldc = C.ld; g.ldr = R.ld;
+    g.a_hi_only = c.single_product;
+    return g;
+}
+void gemm(In A, GemmArgs g, hipStream_t s) {
+    g.A = A.p; g.lda = A.ld;
     launch_gemm(g, s);
 }
-
 // same with A given as interleaved (hi, lo) f16 planes [M][lda/32][2][32] (split-precision mode: the producer kernel wrote them)
+GemmArgs on_planes(const void* planes, int lda, GemmArgs g) {
+    g.A_hi = reinterpret_cast<const uint16_t*>(planes); g.A_lo = g.A_hi + 32;
+    g.lda = lda;
+    return g;
+}
+
 // folded-LayerNorm roles of a projection (GemmArgs::ln_*): `in` = it consumes raw planes + the statistics of `in_groups` 32-column groups over `in_count` real columns
 // (B must then be the W o gamma matrix, cs its row sums); `out_planes` = it produces raw planes + statistics of its own output rows
 struct LnFold {
@@ -99,60 +94,221 @@ struct LnFold {
     const float* in_gsums = nullptr; int in_groups = 0, in_count = 0; // ... or (small batches) the producer's group sums, merged by the consuming workgroups themselves
     void* out_planes = nullptr; float* out_stats = nullptr; int out_ld = 0;
 };
-void set_sk(GemmArgs& g, MuseWs* w);
-void set_fold(GemmArgs& g, const LnFold* f, int rows) {
+void set_fold(GemmArgs& g, const LnFold* f) {
     if (!f) return;
     g.ln_in_stats = f->in_stats; g.ln_in_cs = f->in_cs;
     g.ln_in_gsums = f->in_gsums; g.ln_in_groups = f->in_groups; g.ln_in_count = f->in_count;
     g.ln_out_planes = f->out_planes; g.ln_out_stats = f->out_stats; g.ln_out_ld = f->out_ld;
-    g.ln_rows = rows;
+    g.ln_rows = g.M;
 }
 
-void gemm_planes(const void* Aplanes, int lda, const float* W, int ldb, float* C, int ldc, int M, int N, int K, const float* R, int ldr, hipStream_t s, float* kpart = nullptr,
-                 const LnFold* fold = nullptr, MuseWs* sk = nullptr) {
-    GemmArgs g;
-    g.A_hi = reinterpret_cast<const uint16_t*>(Aplanes); g.A_lo = g.A_hi + 32;
-    g.B = W; g.C = C; g.R = R;
-    g.M = M; g.N = N; g.K = K;
-    g.lda = lda; g.ldb = ldb; g.ldc = ldc; g.ldr = ldr;
-    const bool use_sk = sk && gemm_sk_pays(M, N, K);   // (stream-K where it pays: it keeps the fused epilogue and needs no reduce launch)
-    if (kpart && N <= 1024 && !fold && !use_sk) { g.ksplit = pick_ksplit(M, N, K); g.kpart = kpart; }   // the workspace holds KSPLIT_MAX slices of [rows, D] (a folded projection
-    set_fold(g, fold, M);                                                                                // keeps its epilogue: the split-K reduce kernel has none of it)
-    if (use_sk) set_sk(g, sk);
-    launch_gemm(g, s);
+// One forward of the split path: what its three sub-layer functions share
+struct Fwd {
+    const Ctx& c;
+    MuseWs& w;
+    hipStream_t s;
+    int rows, B, N;
+    MuseSwitches sw;
+    int fold;          // muse_fold_level
+    bool tile_merge;   // muse_tile_merge: the consuming workgroups merge a LayerNorm's group sums themselves
+    // fold == 2: the residual-stream projections (to_out of both attention modules, the feed-forward's down-projection) write, besides the fp32 row, the raw planes of the
+    // row into w.xn and its statistics into w.stats_d: the next projection multiplies them by W o gamma.  `x_planes_ready`: w.xn / w.stats_d hold the current w.x
+    bool x_planes_ready = false;
+    LnFold prod_x;     // producer role of a residual-stream projection
+};
+
+// consumer role behind a folded LayerNorm over `count` real columns in `groups` 32-column groups (launches the merge kernel unless the consumer's tiles merge)
+LnFold consumer(const Fwd& f, const float* gsums, int groups, int count, const float* cs) {
+    LnFold r;
+    r.in_cs = cs;
+    if (f.tile_merge) { r.in_gsums = gsums; r.in_groups = groups; r.in_count = count; }
+    else { launch_ln_stats_finalize(gsums, f.w.rowstat, f.rows, groups, count, 1e-5f, f.s); r.in_stats = f.w.rowstat; }
+    return r;
 }
 
-// to_q projection with the query preparation (l2norm, q_scale, hi/lo split, head-major layout) fused into the GEMM epilogue
-void gemm_planes_q(const void* Aplanes, int lda, const float* W, const float* q_scale, void* Qh, void* Ql, int B, int H, int Nq, int D, hipStream_t s, float* kpart = nullptr,
-                   float* qraw = nullptr, const LnFold* fold = nullptr, MuseWs* sk = nullptr) {
-    const bool use_sk = sk && gemm_sk_pays((long)B * Nq, H * 64, D);
-    if (!fold && !use_sk && kpart && qraw && H * 64 <= 1024 && pick_ksplit((long)B * Nq, H * 64, D) > 1) {
-        // small batch: the projection split over K into qraw, then the query preparation as its own (tiny) kernel
-        gemm_planes(Aplanes, lda, W, D, qraw, H * 64, B * Nq, H * 64, D, nullptr, 0, s, kpart);
-        launch_muse_q_prep_split(qraw, q_scale, Qh, Ql, B, H, Nq, 8.0f * kLog2e, s);
+// THE launch of an LDS-DMA projection of the split path: `g` with its operands and fused epilogue as the table's last column wants them, the rest by muse_proj_plan
+void project(Fwd& f, MuseProj kind, GemmArgs g, const LnFold* fold = nullptr, bool merged = false) {
+    MuseWs& w = f.w;
+    MuseProjIn in;
+    in.kind = kind; in.M = g.M; in.N = g.N; in.K = g.K;
+    in.fold_role = fold != nullptr; in.merged = merged;
+    in.has_kpart = w.kpart != nullptr; in.has_sk_ws = w.sk_ws != nullptr;   // (qraw, the un-fused q projection's output, is part of every workspace)
+    const MuseProjPlan p = muse_proj_plan(in, f.sw, glds_switches());
+    if (p.q_unfused) {   // small batch: the projection split over K into qraw, then the query preparation as its own (tiny) kernel
+        GemmArgs r = on_planes(g.A_hi, g.lda, gemm_args(f.c, {g.B, g.ldb}, {w.qraw, g.N}, g.M, g.N, g.K));
+        r.ksplit = p.ksplit; r.kpart = w.kpart;
+        launch_gemm(r, f.s);
+        launch_muse_q_prep_split(w.qraw, g.epi_scale, g.epi_hi, g.epi_lo, g.M / g.epi_rows, g.epi_heads, g.epi_rows, g.epi_post, f.s);
         return;
     }
-    GemmArgs g;
-    g.A_hi = reinterpret_cast<const uint16_t*>(Aplanes); g.A_lo = g.A_hi + 32;
-    g.B = W;
-    g.M = B * Nq; g.N = H * 64; g.K = D;
-    g.lda = lda; g.ldb = D; g.ldc = H * 64;
-    g.epi = EPI_MUSE_Q; g.epi_scale = q_scale; g.epi_hi = Qh; g.epi_lo = Ql; g.epi_rows = Nq; g.epi_heads = H;
+    if (p.kpart) { g.ksplit = p.ksplit; g.kpart = w.kpart; }
+    set_fold(g, fold);
+    if (p.sk) { g.sk_ws = w.sk_ws; g.sk_epoch = ++w.sk_epoch; }
+    g.force_wm = p.force_wm;
+    launch_gemm(g, f.s);
+}
+
+// to_q over the LayerNorm planes in w.xn with the query preparation (l2norm, q_scale, hi/lo split, head-major layout) fused into the GEMM epilogue
+GemmArgs q_args(const Fwd& f, const float* W, const float* q_scale) {
+    const int D = f.c.D, H = f.c.H;
+    const Planes Q = planes_of(f.w.Q, (size_t)f.rows * D);
+    GemmArgs g = on_planes(f.w.xn, D, gemm_args(f.c, {W, D}, {nullptr, H * 64}, f.B * f.N, H * 64, D));
+    g.epi = EPI_MUSE_Q; g.epi_scale = q_scale; g.epi_hi = Q.hi; g.epi_lo = Q.lo; g.epi_rows = f.N; g.epi_heads = H;
     g.epi_post = 8.0f * kLog2e;   // sim = 8 q.k (muse_net:150) in the base-2 domain of the split attention kernel
-    set_fold(g, fold, B * Nq);
-    if (use_sk) set_sk(g, sk);
-    launch_gemm(g, s);
+    return g;
 }
 
-void set_sk(GemmArgs& g, MuseWs* w) {
-    if (!w || !w->sk_ws) return;
-    g.sk_ws = w->sk_ws;
-    g.sk_epoch = ++w->sk_epoch;
+// the split attention kernel over the prepared Q planes; output as the planes of the [rows, D] matrix the to_out projection reads
+AttnSplitArgs attn_args(const Fwd& f, Planes K, Planes VT, int Nk_pad) {
+    const Planes Q = planes_of(f.w.Q, (size_t)f.rows * f.c.D);
+    AttnSplitArgs sa{};
+    sa.Qh = Q.hi; sa.Ql = Q.lo; sa.Kh = K.hi; sa.Kl = K.lo; sa.VTh = VT.hi; sa.VTl = VT.lo;
+    sa.O = f.w.att; sa.B = f.B; sa.H = f.c.H; sa.Nq = f.N; sa.Nk_pad = Nk_pad;
+    sa.bias_head_stride = 0; sa.scale = 8.0f * kLog2e;
+    sa.o_bstride = (long)f.N * f.c.D; sa.o_qstride = f.c.D; sa.o_hstride = 64;
+    sa.Op = reinterpret_cast<_Float16*>(f.w.att);
+    return sa;
 }
 
-// The workspace of a Route M call (w.B, w.S and w.rows set): the one description of it, run twice by Arena::carve (the rule is in arena.h)
-void muse_layout(const Ctx& c, MuseWs& w, Arena& a, bool generate) {
+// x += to_out(attention(LayerNorm(x))) over the tokens themselves.  Every GEMM input is produced directly as (hi, lo) f16 planes (same bytes as the fp32 buffer they replace)
+void self_attention_split(Fwd& f, const MuseLayer& l) {
+    const Ctx& c = f.c;
+    MuseWs& w = f.w;
+    const int D = c.D, rows = f.rows;
+    const bool f0 = f.fold == 2 && f.x_planes_ready;   // (layer 0 reads the embedding: no projection produced it - its first LayerNorm stays a kernel)
+    LnFold cons_x;   // consumer role behind a LayerNorm over the D residual columns
+    if (!f0) launch_layernorm_planes(w.x, D, l.norm_g[0], nullptr, w.xn, D, rows, D, 1e-5f, f.s);
+    else cons_x = consumer(f, w.stats_d, D / 32, D, nullptr);
+    const bool merged = l.to_qkv_self && muse_qkv_merged(f.sw, rows);
+    if (!merged) {
+        cons_x.in_cs = l.fold_q_self_cs;
+        project(f, PROJ_Q, q_args(f, f0 ? l.fold_q_self : l.to_q[0], l.q_scale[0]), f0 ? &cons_x : nullptr);
+    }
+    // to_kv (merged: q | k | v) with the key / value preparation in its epilogue: k planes [B, H, NkS_pad, 64], v planes transposed [B, H, 64, NkS_pad]
+    const Planes K = planes_of(w.Ks, w.kvS), VT = planes_of(w.Vs, w.kvS);
+    const float* W = merged ? (f0 ? l.fold_qkv : l.to_qkv_self) : (f0 ? l.fold_kv_self : l.to_kv[0]);
+    const int Nkv = (merged ? 3 : 2) * D;
+    GemmArgs gk = on_planes(w.xn, D, gemm_args(c, {W, D}, {nullptr, Nkv}, rows, Nkv, D));
+    gk.epi = merged ? EPI_MUSE_QKV : EPI_MUSE_KV;
+    gk.epi_scale = l.k_scale[0]; gk.epi_hi = K.hi; gk.epi_lo = K.lo; gk.epi_hi2 = VT.hi; gk.epi_lo2 = VT.lo;
+    gk.epi_aux = l.null_self; gk.epi_rows = f.N; gk.epi_heads = c.H; gk.epi_ld = c.NkS_pad;
+    if (merged) {
+        const Planes Q = planes_of(w.Q, (size_t)rows * D);
+        gk.epi_qh = Q.hi; gk.epi_ql = Q.lo; gk.epi_qscale = l.q_scale[0];
+        gk.epi_post = 8.0f * kLog2e;   // sim = 8 q.k (muse_net:150) in the base-2 domain of the split attention kernel
+    }
+    cons_x.in_cs = merged ? l.fold_qkv_cs : l.fold_kv_self_cs;
+    project(f, PROJ_KV, gk, f0 ? &cons_x : nullptr, merged);
+    AttnSplitArgs sa = attn_args(f, K, VT, c.NkS_pad);
+    sa.bias = c.bias_self; sa.bias_pk = c.bias_self_pk; sa.ldbias = c.ldS;
+    sa.ksplit = w.attn_ks; sa.kws = w.attn_ws;
+    launch_attention_split(sa, f.s);
+    project(f, PROJ_OUT, on_planes(w.att, D, gemm_args(c, {l.to_out[0], D}, {w.x, D}, rows, D, D, {w.x, D})), f.fold == 2 ? &f.prod_x : nullptr);   // x = to_out(att) + x
+}
+
+// x += to_out(attention(LayerNorm(x))) over layer i's keys / values of the condition (muse_prepare)
+void cross_attention_split(Fwd& f, const MuseLayer& l, int i) {
+    const Ctx& c = f.c;
+    MuseWs& w = f.w;
+    const int D = c.D, rows = f.rows;
+    LnFold cons_x;
+    if (f.fold != 2) launch_layernorm_planes(w.x, D, l.norm_g[1], nullptr, w.xn, D, rows, D, 1e-5f, f.s);
+    else cons_x = consumer(f, w.stats_d, D / 32, D, l.fold_q_cross_cs);
+    project(f, PROJ_Q, q_args(f, f.fold == 2 ? l.fold_q_cross : l.to_q[1], l.q_scale[1]), f.fold == 2 ? &cons_x : nullptr);
+    AttnSplitArgs sa = attn_args(f, planes_of(w.crossK[i], w.kvC), planes_of(w.crossV[i], w.kvC), c.NkC_pad);   // (the cross-attention's 9 key tiles stay one range)
+    sa.bias = c.bias_cross; sa.bias_pk = c.bias_cross_pk; sa.ldbias = c.ldC;
+    sa.kv_group = w.S;   // the samples of a layout read the layout's cross-attention K / V
+    launch_attention_split(sa, f.s);
+    project(f, PROJ_OUT, on_planes(w.att, D, gemm_args(c, {l.to_out[1], D}, {w.x, D}, rows, D, D, {w.x, D})), f.fold == 2 ? &f.prod_x : nullptr);
+}
+
+// x += W4 LayerNorm(GEGLU(W1 LayerNorm(x))) (muse_net:78-88); `last`: no layer follows
+void feed_forward_split(Fwd& f, const MuseLayer& l, bool last) {
+    const Ctx& c = f.c;
+    MuseWs& w = f.w;
+    const int D = c.D, rows = f.rows, fold = f.fold;
+    if (fold != 2) launch_layernorm_planes(w.x, D, l.ff_g0, nullptr, w.xn, D, rows, D, 1e-5f, f.s);
+    if (l.ff_w1_geglu) {
+        // GEGLU in the up-projection's epilogue: h = gate * gelu(x) as [rows, Fpad] (pad columns exactly 0), then the LayerNorm half on its own - or (fold >= 1)
+        // folded away: the epilogue writes the raw planes of h and its row statistics, the down-projection multiplies by W4 o gamma
+        GemmArgs ge = on_planes(w.xn, D, gemm_args(c, {fold == 2 ? l.fold_w1 : l.ff_w1_geglu, D}, {w.h, c.Fpad}, rows, 2 * c.Fpad, D));
+        ge.epi = EPI_GEGLU;
+        LnFold fg;
+        if (fold == 2) fg = consumer(f, w.stats_d, D / 32, D, l.fold_w1_cs);
+        if (fold >= 1) { fg.out_planes = w.g; fg.out_stats = w.stats_f; fg.out_ld = c.Fpad; }
+        project(f, PROJ_GEGLU, ge, fold >= 1 ? &fg : nullptr);
+        if (fold == 0) launch_layernorm_planes(w.h, c.Fpad, l.ff_g3, nullptr, w.g, c.Fpad, rows, c.F, 1e-5f, f.s);
+    } else {
+        project(f, PROJ_UP, on_planes(w.xn, D, gemm_args(c, {l.ff_w1, D}, {w.h, 2 * c.F}, rows, 2 * c.F, D)));
+        launch_geglu_layernorm_planes(w.h, 2 * c.F, l.ff_g3, w.g, c.Fpad, rows, c.F, 1e-5f, f.s);
+    }
+    LnFold fd;   // the down-projection: consumer of the inner LayerNorm (fold >= 1), producer for the next layer's first LayerNorm (fold == 2, not behind the last layer)
+    if (fold >= 1 && l.ff_w1_geglu) fd = consumer(f, w.stats_f, c.Fpad / 32, c.F, l.fold_w4_cs);
+    const bool prod_next = fold == 2 && !last;
+    if (prod_next) { fd.out_planes = w.xn; fd.out_stats = w.stats_d; fd.out_ld = D; }
+    const bool cons = fd.in_stats || fd.in_gsums, any = cons || fd.out_planes;
+    project(f, PROJ_OUT, on_planes(w.g, c.Fpad, gemm_args(c, {cons ? l.fold_w4 : l.ff_w4_padded, c.Fpad}, {w.x, D}, rows, D, c.Fpad, {w.x, D})), any ? &fd : nullptr);
+    f.x_planes_ready = prod_next;
+}
+
+// the layers in split precision (f16x3; f16x1 and weights = f16 are this path with other weight planes)
+void muse_blocks_split(const Ctx& c, MuseWs& w, hipStream_t s) {
+    Fwd f{c, w, s, (int)w.rows, w.B, c.N, muse_switches()};
+    f.fold = muse_fold_level(f.sw, !c.muse.empty() && c.muse[0].fold_w4);
+    f.tile_merge = muse_tile_merge(f.sw, f.rows);
+    f.prod_x.out_planes = w.xn; f.prod_x.out_stats = w.stats_d; f.prod_x.out_ld = c.D;
+    const int layers = c.cfg.num_layers;
+    for (int i = 0; i < layers; ++i) {
+        const MuseLayer& l = c.muse[i];
+        self_attention_split(f, l);
+        cross_attention_split(f, l, i);
+        feed_forward_split(f, l, i + 1 == layers);
+    }
+}
+
+// the layers in exact fp32: sixteen launches per layer
+void muse_blocks_f32(const Ctx& c, MuseWs& w, hipStream_t s) {
+    const int D = c.D, H = c.H, B = w.B, N = c.N, F = c.F, Fpad = c.Fpad, rows = (int)w.rows;
+    AttnArgs self{};
+    self.Q = w.Q; self.K = w.Ks; self.V = w.Vs; self.bias = c.bias_self; self.R = nullptr; self.O = w.att;
+    self.B = B; self.H = H; self.Nq = N; self.Nk_pad = c.NkS_pad;
+    self.q_bstride = (long)H * N * 64; self.q_hstride = (long)N * 64;
+    self.kv_bstride = (long)H * c.NkS_pad * 64; self.kv_hstride = (long)c.NkS_pad * 64;
+    self.ldbias = c.ldS; self.bias_head_stride = 0; self.scale = 8.0f;
+    self.o_bstride = (long)N * D; self.o_qstride = D; self.o_hstride = 64;
+    AttnArgs cross = self;
+    cross.bias = c.bias_cross; cross.Nk_pad = c.NkC_pad; cross.ldbias = c.ldC;
+    cross.kv_bstride = (long)H * c.NkC_pad * 64; cross.kv_hstride = (long)c.NkC_pad * 64;
+    cross.kv_group = w.S;   // the samples of a layout read the layout's cross-attention K / V
+    for (int i = 0; i < c.cfg.num_layers; ++i) {
+        const MuseLayer& l = c.muse[i];
+        // ---- self attention
+        launch_layernorm(w.x, D, l.norm_g[0], nullptr, w.xn, D, rows, D, 1e-5f, s);
+        gemm({w.xn, D}, gemm_args(c, {l.to_q[0], D}, {w.qraw, D}, rows, D, D), s);
+        gemm({w.xn, D}, gemm_args(c, {l.to_kv[0], D}, {w.kvraw, 2 * D}, rows, 2 * D, D), s);
+        launch_muse_q_prep(w.qraw, l.q_scale[0], w.Q, B, H, N, s);
+        launch_muse_kv_prep(w.kvraw, l.null_kv[0], l.k_scale[0], w.Ks, w.Vs, B, H, N, c.NkS_pad, s);
+        launch_attention(self, s);
+        gemm({w.att, D}, gemm_args(c, {l.to_out[0], D}, {w.x, D}, rows, D, D, {w.x, D}), s);   // x = to_out(att) + x
+        // ---- cross attention
+        launch_layernorm(w.x, D, l.norm_g[1], nullptr, w.xn, D, rows, D, 1e-5f, s);
+        gemm({w.xn, D}, gemm_args(c, {l.to_q[1], D}, {w.qraw, D}, rows, D, D), s);
+        launch_muse_q_prep(w.qraw, l.q_scale[1], w.Q, B, H, N, s);
+        cross.K = w.crossK[i]; cross.V = w.crossV[i];
+        launch_attention(cross, s);
+        gemm({w.att, D}, gemm_args(c, {l.to_out[1], D}, {w.x, D}, rows, D, D, {w.x, D}), s);
+        // ---- feed forward
+        launch_layernorm(w.x, D, l.ff_g0, nullptr, w.xn, D, rows, D, 1e-5f, s);
+        gemm({w.xn, D}, gemm_args(c, {l.ff_w1, D}, {w.h, 2 * F}, rows, 2 * F, D), s);
+        launch_geglu_layernorm(w.h, 2 * F, l.ff_g3, w.g, Fpad, rows, F, 1e-5f, s);
+        gemm({w.g, Fpad}, gemm_args(c, {l.ff_w4_padded, Fpad}, {w.x, D}, rows, D, Fpad, {w.x, D}), s);
+    }
+}
+
+// The workspace of a Route M call (w.B, w.S, w.rows and w.generate set): the one description of it, run twice by Arena::carve (the rule is in arena.h)
+void muse_layout(const Ctx& c, MuseWs& w, Arena& a) {
     const auto& g = c.cfg;
+    const MuseSwitches sw = muse_switches();
     const int D = c.D, H = c.H, B = w.B, G = B / w.S;
     w.img = g.image_embed ? a.get<float>((size_t)w.rows * D) : nullptr;
     w.c_embed = g.image_embed ? a.get<float>((size_t)B * g.num_cams * D) : nullptr;
@@ -163,57 +319,60 @@ void muse_layout(const Ctx& c, MuseWs& w, Arena& a, bool generate) {
     w.att = a.get<float>((size_t)w.rows * D);
     w.kvraw = a.get<float>((size_t)std::max<long>(w.rows, (long)B * c.K) * 2 * D);
     w.Q = a.get<float>((size_t)w.rows * D);
-    const size_t kvS = (size_t)B * H * c.NkS_pad * 64;
-    w.Ks = a.get<float>(kvS);
-    w.Vs = a.get<float>(kvS);
+    w.kvS = (size_t)B * H * c.NkS_pad * 64;
+    w.Ks = a.get<float>(w.kvS);
+    w.Vs = a.get<float>(w.kvS);
     w.h = a.get<float>((size_t)w.rows * 2 * c.F);
     w.g = a.get<float>((size_t)w.rows * c.Fpad);
-    w.kpart = std::max(pick_ksplit(w.rows, D, D), pick_ksplit(w.rows, D, c.Fpad)) > 1 ? a.get<float>((size_t)KSPLIT_MAX * w.rows * D) : nullptr;
-    w.attn_ks = pick_attn_ksplit((long)cdiv(c.N, 256) * H * B, c.NkS_pad / 32);
+    w.kpart = muse_needs_kpart(w.rows, D, c.Fpad, sw) ? a.get<float>((size_t)kMuseKsplitMax * w.rows * D) : nullptr;
+    w.attn_ks = pick_attn_ksplit((long)cdiv(c.N, 256) * H * B, c.NkS_pad / 32, sw.attn_ksplit);
     w.attn_ws = w.attn_ks > 1 ? a.get<float>((size_t)attn_split_ws_floats(B, H, c.N, w.attn_ks)) : nullptr;
     w.stats_d = a.get<float>((size_t)w.rows * 2 * (D / 32));
     w.stats_f = a.get<float>((size_t)w.rows * 2 * (c.Fpad / 32));
     w.rowstat = a.get<float>((size_t)w.rows * 2);
-    w.sk_ws = w.rows <= kSkMaxRows && g.precision == BEVGEN_PRECISION_F16X3 ? a.alloc(gemm_sk_ws_bytes()) : nullptr;
+    w.sk_ws = w.rows <= kMuseSkMaxRows && g.precision == BEVGEN_PRECISION_F16X3 ? a.alloc(gemm_sk_ws_bytes()) : nullptr;
     w.cond_g = w.S > 1 ? a.get<int64_t>((size_t)G * c.K) : nullptr;
     w.c_embed_g = w.S > 1 && g.image_embed ? a.get<float>((size_t)G * g.num_cams * D) : nullptr;
-    const size_t kvC = (size_t)G * H * c.NkC_pad * 64;
+    w.kvC = (size_t)G * H * c.NkC_pad * 64;
     w.crossK.resize(g.num_layers);
     w.crossV.resize(g.num_layers);
     for (int i = 0; i < g.num_layers; ++i) {
-        w.crossK[i] = a.get<float>(kvC);
-        w.crossV[i] = a.get<float>(kvC);
+        w.crossK[i] = a.get<float>(w.kvC);
+        w.crossV[i] = a.get<float>(w.kvC);
     }
-    w.logits = generate ? a.get<float>((size_t)w.rows * c.V) : nullptr;
-    w.scores = generate ? a.get<float>((size_t)w.rows) : nullptr;
+    w.logits = w.generate ? a.get<float>((size_t)w.rows * c.V) : nullptr;
+    w.scores = w.generate ? a.get<float>((size_t)w.rows) : nullptr;
 }
 
-// per-batch constants: embeddings + cross-attention K/V
-void muse_prepare(Ctx& c, MuseWs& w, const int64_t* cond, const float* I_inv, const float* E_inv, int B, hipStream_t s, int samples_per_layout = 1, bool generate = false) {
+// per-batch constants: the workspace, the tensors used by name, embeddings + cross-attention K/V
+void muse_prepare(Ctx& c, MuseWs& w, const MuseBatch& in, bool generate, hipStream_t s) {
     const auto& g = c.cfg;
     const std::string p = "transformer.";
-    const int S = samples_per_layout < 1 ? 1 : samples_per_layout;
+    const int B = in.B, S = in.samples_per_layout < 1 ? 1 : in.samples_per_layout;
     BG_REQUIRE(B % S == 0, "batch %d is not a multiple of samples_per_layout %d", B, S);
     const int G = B / S;   // BEV layouts: the condition side (context embedding, cross-attention K / V of every layer) is built once per layout
     w.S = S;
     w.B = B;
+    w.generate = generate;
     w.rows = (long)B * c.N;
-    c.arena.carve([&](Arena& a) { muse_layout(c, w, a, generate); });
+    c.arena.carve([&](Arena& a) { muse_layout(c, w, a); });
+    w.token_emb = c.pf(p + "token_emb.weight"); w.pos_emb = c.pf(p + "pos_emb.weight");
+    w.norm_g = c.pf(p + "transformer_blocks.norm.gamma"); w.to_logits = c.pf(p + "to_logits.weight");
+    if (c.find("token_critic.to_pred.weight")) { w.critic_w = c.pf("token_critic.to_pred.weight"); w.critic_b = c.pf("token_critic.to_pred.bias"); }
     const int D = c.D, H = c.H;
-    const size_t kvS = (size_t)B * H * c.NkS_pad * 64;
     if (w.sk_ws) {
         HIP_CHECK(hipMemsetAsync(w.sk_ws, 0, 1024 * sizeof(unsigned), s));   // the flag words: a flag equal to a launch's epoch means "published in this launch"
         w.sk_epoch = 0;
     }
-    HIP_CHECK(hipMemsetAsync(w.Ks, 0, kvS * sizeof(float), s));  // rows beyond the real keys stay zero
-    HIP_CHECK(hipMemsetAsync(w.Vs, 0, kvS * sizeof(float), s));
+    HIP_CHECK(hipMemsetAsync(w.Ks, 0, w.kvS * sizeof(float), s));  // rows beyond the real keys stay zero
+    HIP_CHECK(hipMemsetAsync(w.Vs, 0, w.kvS * sizeof(float), s));
 
     if (g.image_embed)
-        launch_camera_embed(I_inv, E_inv, c.image_plane, c.pf(p + "img_embed.weight"), c.pf(p + "cam_embed.weight"), w.img, w.c_embed, B, g.num_cams, c.T, D, s);
-    const int64_t* cond_g = cond;
+        launch_camera_embed(in.I_inv, in.E_inv, c.image_plane, c.pf(p + "img_embed.weight"), c.pf(p + "cam_embed.weight"), w.img, w.c_embed, B, g.num_cams, c.T, D, s);
+    const int64_t* cond_g = in.cond;
     const float* c_embed_g = w.c_embed;
     if (S > 1) {   // the first scene of every group -> contiguous [G, ...] inputs of the condition side
-        HIP_CHECK(hipMemcpy2DAsync(w.cond_g, (size_t)c.K * 8, cond, (size_t)S * c.K * 8, (size_t)c.K * 8, G, hipMemcpyDeviceToDevice, s));
+        HIP_CHECK(hipMemcpy2DAsync(w.cond_g, (size_t)c.K * 8, in.cond, (size_t)S * c.K * 8, (size_t)c.K * 8, G, hipMemcpyDeviceToDevice, s));
         cond_g = w.cond_g;
         if (w.c_embed) {
             HIP_CHECK(hipMemcpy2DAsync(w.c_embed_g, (size_t)g.num_cams * D * 4, w.c_embed, (size_t)S * g.num_cams * D * 4, (size_t)g.num_cams * D * 4, G, hipMemcpyDeviceToDevice, s));
@@ -225,215 +384,52 @@ void muse_prepare(Ctx& c, MuseWs& w, const int64_t* cond, const float* I_inv, co
                       g.bev_embed ? c.pf(p + "bev_cam_pos_emb") : nullptr, c_embed_g, w.context, G, g.num_cams, c.K, D, g.cond_vocab_size, s);
 
     // cross-attention keys/values: to_kv(context) (context is NOT layer-normed, muse_net:128-132), null kv prepended, k l2-normalised
-    const size_t kvC = (size_t)G * H * c.NkC_pad * 64;
     for (int i = 0; i < g.num_layers; ++i) {
-        HIP_CHECK(hipMemsetAsync(w.crossK[i], 0, kvC * sizeof(float), s));
-        HIP_CHECK(hipMemsetAsync(w.crossV[i], 0, kvC * sizeof(float), s));
+        HIP_CHECK(hipMemsetAsync(w.crossK[i], 0, w.kvC * sizeof(float), s));
+        HIP_CHECK(hipMemsetAsync(w.crossV[i], 0, w.kvC * sizeof(float), s));
         const MuseLayer& l = c.muse[i];
-        gemm(w.context, D, l.to_kv[1], D, w.kvraw, 2 * D, G * c.K, 2 * D, D, nullptr, 0, s);
-        if (c.cfg.precision == BEVGEN_PRECISION_F16X3) {  // each fp32-sized buffer holds the (hi, lo) f16 planes back to back
-            _Float16* kh = reinterpret_cast<_Float16*>(w.crossK[i]);
-            _Float16* vh = reinterpret_cast<_Float16*>(w.crossV[i]);
-            launch_muse_kv_prep_split(w.kvraw, l.null_kv[1], l.k_scale[1], kh, kh + kvC, vh, vh + kvC, G, H, c.K, c.NkC_pad, s);
+        gemm({w.context, D}, gemm_args(c, {l.to_kv[1], D}, {w.kvraw, 2 * D}, G * c.K, 2 * D, D), s);
+        if (c.cfg.precision == BEVGEN_PRECISION_F16X3) {
+            const Planes K = planes_of(w.crossK[i], w.kvC), VT = planes_of(w.crossV[i], w.kvC);
+            launch_muse_kv_prep_split(w.kvraw, l.null_kv[1], l.k_scale[1], K.hi, K.lo, VT.hi, VT.lo, G, H, c.K, c.NkC_pad, s);
         } else {
             launch_muse_kv_prep(w.kvraw, l.null_kv[1], l.k_scale[1], w.crossK[i], w.crossV[i], G, H, c.K, c.NkC_pad, s);
         }
     }
 }
 
-// one transformer pass over the current ids: leaves LayerNorm(x) (= `embed`, muse_net:202) in w.xn
-void muse_blocks(Ctx& c, MuseWs& w, const int64_t* ids, hipStream_t s) {
-    const auto& g = c.cfg;
-    // (Round 3 built a first LayerNorm fold - producers wrote (row x gamma) planes + per-group (mean, M2), a merge kernel per LayerNorm - token-exact and SLOWER, 10.12 ->
-    // 9.86 scenes/s, profiles/r03_ab_ln_fold.txt; removed in round 4.  Round 6's form (ln_fold_level above) has no merge launch - the consumer adds the group sums itself, in the
-    // shadow of its first DMA - no gamma in the producer (it sits in W o gamma), and the inner LayerNorm's producer writes planes INSTEAD of its fp32 result.)
-    const std::string p = "transformer.";
-    const int D = c.D, H = c.H, B = w.B, N = c.N;
-    const int rows = (int)w.rows;
-    launch_token_embed(ids, c.pf(p + "token_emb.weight"), w.img, c.pf(p + "pos_emb.weight"), w.x, B, N, D, g.vocab_size + 1, s);
-    const bool split = g.precision == BEVGEN_PRECISION_F16X3;
-    const int fold = split ? ln_fold_level(c, rows) : 0;
-    // fold == 2: the residual-stream projections (to_out of both attention modules, the feed-forward's down-projection) write, besides the fp32 row, the raw planes of the
-    // row into w.xn and its statistics into w.stats_d: the next projection multiplies them by W o gamma.  `x_planes_ready`: w.xn / w.stats_d hold the current w.x
-    bool x_planes_ready = false;
-    // who merges a LayerNorm's group sums: up to two scenes every workgroup of the consuming projection runs ONE tile and merges its rows itself (no launch between producer
-    // and consumer: at one scene a 9 us kernel + its ramp per LayerNorm); above that one finalize kernel per LayerNorm feeds all tiles ($BEVGEN_LN_MERGE = kernel | tile)
-    const char* merge_env = getenv("BEVGEN_LN_MERGE");   // (read per forward: the tests switch it inside one process)
-    const bool tile_merge = merge_env ? merge_env[0] == 't' : rows <= 3072;
-    auto consumer = [&](const float* gsums, int groups, int count, const float* cs) {
-        LnFold f;
-        f.in_cs = cs;
-        if (tile_merge) { f.in_gsums = gsums; f.in_groups = groups; f.in_count = count; }
-        else { launch_ln_stats_finalize(gsums, w.rowstat, rows, groups, count, 1e-5f, s); f.in_stats = w.rowstat; }
-        return f;
-    };
-    LnFold prod_x;   // producer role of a residual-stream projection
-    prod_x.out_planes = w.xn; prod_x.out_stats = w.stats_d; prod_x.out_ld = D;
-    for (int i = 0; i < g.num_layers; ++i) {
-        const MuseLayer& l = c.muse[i];
-        // ---- self attention
-        // split-precision mode: every GEMM input is produced directly as (hi, lo) f16 planes (same bytes as the fp32 buffer they replace)
-        if (split) {
-            const bool f0 = fold == 2 && x_planes_ready;   // (layer 0 reads the embedding: no projection produced it - its first LayerNorm stays a kernel)
-            LnFold cons_x;   // consumer role behind a LayerNorm over the D residual columns
-            if (!f0) launch_layernorm_planes(w.x, D, l.norm_g[0], nullptr, w.xn, D, rows, D, 1e-5f, s);
-            else cons_x = consumer(w.stats_d, D / 32, D, nullptr);
-            // to_q and to_kv read the same LayerNorm planes (muse_net:126-132): ONE projection over the concatenated weight, query / key / value preparation in its
-            // epilogue ($BEVGEN_QKV_MERGE=0: the two launches of rounds 2-4, for A/B runs)
-            // Measured, round 5 (profiles/r05_ab_qkv_merge*.txt): one scene 161.9 -> 160.4 ms, sixteen scenes 10.31 -> 10.21 scenes/s - merged only on the low-latency path then.
-            // Round 6, after the staged row-major epilogues and with the row-split rest choosing its own block shape (profiles/r06_ab_qkv_merge.txt, same box, ms per step
-            // separate -> merged): three scenes 387.0 -> 373.5 (+3.6 %), four 443.7 -> 437.2, six 614.0 -> 607.1, eight 771.0 -> 768.7, twelve 1122.0 -> 1108.7 (+1.2 %),
-            // sixteen 1424.0 -> 1422.2: merged at every batch size.  $BEVGEN_QKV_MERGE = 0 never, 3 only up to 3072 token rows (the round-5 rule; A/B runs)
-            static const int qkv_merge = getenv("BEVGEN_QKV_MERGE") ? atoi(getenv("BEVGEN_QKV_MERGE")) : 1;
-            const bool merged = l.to_qkv_self && qkv_merge != 0 && (qkv_merge != 3 || rows <= 3072);
-            if (!merged) {
-                cons_x.in_cs = l.fold_q_self_cs;
-                gemm_planes_q(w.xn, D, f0 ? l.fold_q_self : l.to_q[0], l.q_scale[0], w.Q, reinterpret_cast<_Float16*>(w.Q) + (size_t)rows * D, B, H, N, D, s, w.kpart, w.qraw,
-                              f0 ? &cons_x : nullptr, &w);
-            }
-            {   // to_kv with the key / value preparation in its epilogue: k planes [B, H, NkS_pad, 64], v planes transposed [B, H, 64, NkS_pad]
-                const size_t kvS_ = (size_t)B * H * c.NkS_pad * 64;
-                _Float16 *Kp = reinterpret_cast<_Float16*>(w.Ks), *Vp = reinterpret_cast<_Float16*>(w.Vs);
-                GemmArgs gk;
-                gk.A_hi = reinterpret_cast<const uint16_t*>(w.xn); gk.A_lo = gk.A_hi + 32;
-                gk.B = merged ? (f0 ? l.fold_qkv : l.to_qkv_self) : (f0 ? l.fold_kv_self : l.to_kv[0]);
-                gk.M = rows; gk.N = (merged ? 3 : 2) * D; gk.K = D; gk.lda = D; gk.ldb = D; gk.ldc = gk.N;
-                gk.epi = merged ? EPI_MUSE_QKV : EPI_MUSE_KV;
-                gk.epi_scale = l.k_scale[0]; gk.epi_hi = Kp; gk.epi_lo = Kp + kvS_; gk.epi_hi2 = Vp; gk.epi_lo2 = Vp + kvS_;
-                gk.epi_aux = l.null_self; gk.epi_rows = N; gk.epi_heads = H; gk.epi_ld = c.NkS_pad;
-                if (merged) {
-                    gk.epi_qh = w.Q; gk.epi_ql = reinterpret_cast<_Float16*>(w.Q) + (size_t)rows * D; gk.epi_qscale = l.q_scale[0];
-                    gk.epi_post = 8.0f * kLog2e;   // sim = 8 q.k (muse_net:150) in the base-2 domain of the split attention kernel
-                }
-                if (f0) { cons_x.in_cs = merged ? l.fold_qkv_cs : l.fold_kv_self_cs; set_fold(gk, &cons_x, rows); }
-                // one scene: 144 blocks of 256 x 128 (one per CU, the staged row-major epilogue) against 288 of 128 x 128 sharing CUs in pairs on a two-stage ring
-                static const int qkv_wm4 = getenv("BEVGEN_QKV_WM4") ? atoi(getenv("BEVGEN_QKV_WM4")) : 1;   // (one scene 158.9 -> 153.8 ms, profiles/r06_ab_b1_qkv_wm4.txt; 0: A/B runs)
-                if (qkv_wm4 && merged) gk.force_wm = 4;
-                if (gemm_sk_pays(rows, gk.N, gk.K)) set_sk(gk, &w);
-                launch_gemm(gk, s);
-            }
-        } else {
-            launch_layernorm(w.x, D, l.norm_g[0], nullptr, w.xn, D, rows, D, 1e-5f, s);
-            gemm(w.xn, D, l.to_q[0], D, w.qraw, D, rows, D, D, nullptr, 0, s);
-            gemm(w.xn, D, l.to_kv[0], D, w.kvraw, 2 * D, rows, 2 * D, D, nullptr, 0, s);
-        }
-        const size_t qN = (size_t)rows * D, kvS = (size_t)B * H * c.NkS_pad * 64, kvC = (size_t)(B / w.S) * H * c.NkC_pad * 64;
-        _Float16 *Qh = reinterpret_cast<_Float16*>(w.Q), *Ksh = reinterpret_cast<_Float16*>(w.Ks), *VTsh = reinterpret_cast<_Float16*>(w.Vs);
-        AttnSplitArgs sa{};
-        if (split) {
-            sa.Qh = Qh; sa.Ql = Qh + qN; sa.Kh = Ksh; sa.Kl = Ksh + kvS; sa.VTh = VTsh; sa.VTl = VTsh + kvS;
-            sa.bias = c.bias_self; sa.bias_pk = c.bias_self_pk; sa.O = w.att; sa.B = B; sa.H = H; sa.Nq = N; sa.Nk_pad = c.NkS_pad;
-            sa.ldbias = c.ldS; sa.bias_head_stride = 0; sa.scale = 8.0f * kLog2e;
-            sa.o_bstride = (long)N * D; sa.o_qstride = D; sa.o_hstride = 64;
-            sa.Op = reinterpret_cast<_Float16*>(w.att);
-            sa.ksplit = w.attn_ks; sa.kws = w.attn_ws;
-            launch_attention_split(sa, s);
-            sa.ksplit = 1; sa.kws = nullptr;   // (the cross-attention's 9 key tiles stay one range)
-        } else {
-            launch_muse_q_prep(w.qraw, l.q_scale[0], w.Q, B, H, N, s);
-            launch_muse_kv_prep(w.kvraw, l.null_kv[0], l.k_scale[0], w.Ks, w.Vs, B, H, N, c.NkS_pad, s);
-        }
-        AttnArgs a{};
-        a.Q = w.Q; a.K = w.Ks; a.V = w.Vs; a.bias = c.bias_self; a.R = nullptr; a.O = w.att;
-        a.B = B; a.H = H; a.Nq = N; a.Nk_pad = c.NkS_pad;
-        a.q_bstride = (long)H * N * 64; a.q_hstride = (long)N * 64;
-        a.kv_bstride = (long)H * c.NkS_pad * 64; a.kv_hstride = (long)c.NkS_pad * 64;
-        a.ldbias = c.ldS; a.bias_head_stride = 0; a.scale = 8.0f;
-        a.o_bstride = (long)N * D; a.o_qstride = D; a.o_hstride = 64;
-        if (!split) launch_attention(a, s);
-        if (split) gemm_planes(w.att, D, l.to_out[0], D, w.x, D, rows, D, D, w.x, D, s, w.kpart, fold == 2 ? &prod_x : nullptr, &w);   // x = to_out(att) + x
-        else gemm(w.att, D, l.to_out[0], D, w.x, D, rows, D, D, w.x, D, s);
-        // ---- cross attention
-        if (split) {
-            LnFold cons_x;
-            if (fold != 2) launch_layernorm_planes(w.x, D, l.norm_g[1], nullptr, w.xn, D, rows, D, 1e-5f, s);
-            else cons_x = consumer(w.stats_d, D / 32, D, l.fold_q_cross_cs);
-            gemm_planes_q(w.xn, D, fold == 2 ? l.fold_q_cross : l.to_q[1], l.q_scale[1], w.Q, reinterpret_cast<_Float16*>(w.Q) + (size_t)rows * D, B, H, N, D, s, w.kpart, w.qraw,
-                          fold == 2 ? &cons_x : nullptr, &w);
-        } else {
-            launch_layernorm(w.x, D, l.norm_g[1], nullptr, w.xn, D, rows, D, 1e-5f, s);
-            gemm(w.xn, D, l.to_q[1], D, w.qraw, D, rows, D, D, nullptr, 0, s);
-        }
-        if (split) {
-            _Float16 *ckh = reinterpret_cast<_Float16*>(w.crossK[i]), *cvh = reinterpret_cast<_Float16*>(w.crossV[i]);
-            sa.Kh = ckh; sa.Kl = ckh + kvC; sa.VTh = cvh; sa.VTl = cvh + kvC;
-            sa.bias = c.bias_cross; sa.bias_pk = c.bias_cross_pk; sa.Nk_pad = c.NkC_pad; sa.ldbias = c.ldC;
-            sa.kv_group = w.S;   // the samples of a layout read the layout's cross-attention K / V
-            launch_attention_split(sa, s);
-        } else {
-            launch_muse_q_prep(w.qraw, l.q_scale[1], w.Q, B, H, N, s);
-            a.K = w.crossK[i]; a.V = w.crossV[i]; a.bias = c.bias_cross; a.Nk_pad = c.NkC_pad;
-            a.kv_bstride = (long)H * c.NkC_pad * 64; a.kv_hstride = (long)c.NkC_pad * 64;
-            a.ldbias = c.ldC;
-            a.kv_group = w.S;
-            launch_attention(a, s);
-        }
-        // ---- feed forward
-        if (split) {
-            gemm_planes(w.att, D, l.to_out[1], D, w.x, D, rows, D, D, w.x, D, s, w.kpart, fold == 2 ? &prod_x : nullptr, &w);
-            if (fold != 2) launch_layernorm_planes(w.x, D, l.ff_g0, nullptr, w.xn, D, rows, D, 1e-5f, s);
-            if (l.ff_w1_geglu) {
-                // GEGLU in the up-projection's epilogue: h = gate * gelu(x) as [rows, Fpad] (pad columns exactly 0), then the LayerNorm half on its own - or (fold >= 1)
-                // folded away: the epilogue writes the raw planes of h and its row statistics, the down-projection multiplies by W4 o gamma
-                GemmArgs ge;
-                ge.A_hi = reinterpret_cast<const uint16_t*>(w.xn); ge.A_lo = ge.A_hi + 32;
-                ge.B = fold == 2 ? l.fold_w1 : l.ff_w1_geglu; ge.C = w.h;
-                ge.M = rows; ge.N = 2 * c.Fpad; ge.K = D;
-                ge.lda = D; ge.ldb = D; ge.ldc = c.Fpad;
-                ge.epi = EPI_GEGLU;
-                LnFold fg;
-                if (fold == 2) fg = consumer(w.stats_d, D / 32, D, l.fold_w1_cs);
-                if (fold >= 1) { fg.out_planes = w.g; fg.out_stats = w.stats_f; fg.out_ld = c.Fpad; }
-                if (fold >= 1) set_fold(ge, &fg, rows);
-                if (gemm_sk_pays(rows, ge.N, ge.K)) set_sk(ge, &w);
-                launch_gemm(ge, s);
-                if (fold == 0) launch_layernorm_planes(w.h, c.Fpad, l.ff_g3, nullptr, w.g, c.Fpad, rows, c.F, 1e-5f, s);
-            } else {
-                gemm_planes(w.xn, D, l.ff_w1, D, w.h, 2 * c.F, rows, 2 * c.F, D, nullptr, 0, s);
-                launch_geglu_layernorm_planes(w.h, 2 * c.F, l.ff_g3, w.g, c.Fpad, rows, c.F, 1e-5f, s);
-            }
-            LnFold fd;   // the down-projection: consumer of the inner LayerNorm (fold >= 1), producer for the next layer's first LayerNorm (fold == 2, not behind the last layer)
-            if (fold >= 1 && l.ff_w1_geglu) fd = consumer(w.stats_f, c.Fpad / 32, c.F, l.fold_w4_cs);
-            const bool prod_next = fold == 2 && i + 1 < g.num_layers;
-            if (prod_next) { fd.out_planes = w.xn; fd.out_stats = w.stats_d; fd.out_ld = D; }
-            const bool cons = fd.in_stats || fd.in_gsums, any = cons || fd.out_planes;
-            gemm_planes(w.g, c.Fpad, cons ? l.fold_w4 : l.ff_w4_padded, c.Fpad, w.x, D, rows, D, c.Fpad, w.x, D, s, w.kpart, any ? &fd : nullptr, &w);
-            x_planes_ready = prod_next;
-        } else {
-            gemm(w.att, D, l.to_out[1], D, w.x, D, rows, D, D, w.x, D, s);
-            launch_layernorm(w.x, D, l.ff_g0, nullptr, w.xn, D, rows, D, 1e-5f, s);
-            gemm(w.xn, D, l.ff_w1, D, w.h, 2 * c.F, rows, 2 * c.F, D, nullptr, 0, s);
-            launch_geglu_layernorm(w.h, 2 * c.F, l.ff_g3, w.g, c.Fpad, rows, c.F, 1e-5f, s);
-            gemm(w.g, c.Fpad, l.ff_w4_padded, c.Fpad, w.x, D, rows, D, c.Fpad, w.x, D, s);
-        }
-    }
-    launch_layernorm(w.x, D, c.pf(p + "transformer_blocks.norm.gamma"), nullptr, w.xn, D, rows, D, 1e-5f, s);
+// one transformer pass over the current ids: leaves LayerNorm(x) (= `embed`, muse_net:202) in w.xn.  The two precisions share the token embedding and the final LayerNorm
+void muse_blocks(const Ctx& c, MuseWs& w, const int64_t* ids, hipStream_t s) {
+    const int D = c.D, rows = (int)w.rows;
+    launch_token_embed(ids, w.token_emb, w.img, w.pos_emb, w.x, w.B, c.N, D, c.cfg.vocab_size + 1, s);
+    if (c.cfg.precision == BEVGEN_PRECISION_F16X3) muse_blocks_split(c, w, s);
+    else muse_blocks_f32(c, w, s);
+    launch_layernorm(w.x, D, w.norm_g, nullptr, w.xn, D, rows, D, 1e-5f, s);
 }
 
 }  // namespace
 
-void muse_forward(Ctx& c, const int64_t* ids, const int64_t* cond, const float* I_inv, const float* E_inv, int B, float* logits, float* embed, hipStream_t s) {
+void muse_forward(Ctx& c, const MuseBatch& in, const int64_t* ids, float* logits, float* embed, hipStream_t s) {
     BG_REQUIRE(c.cfg.route == BEVGEN_ROUTE_MASKGIT, "context was not created for the MaskGit route");
-    BG_REQUIRE(B >= 1, "batch must be positive");
+    BG_REQUIRE(in.B >= 1, "batch must be positive");
     MuseWs w;
-    muse_prepare(c, w, cond, I_inv, E_inv, B, s);
+    muse_prepare(c, w, in, false, s);
     muse_blocks(c, w, ids, s);
     const int rows = (int)w.rows;
     if (embed) HIP_CHECK(hipMemcpyAsync(embed, w.xn, (size_t)rows * c.D * sizeof(float), hipMemcpyDeviceToDevice, s));
-    if (logits) gemm(w.xn, c.D, c.pf("transformer.to_logits.weight"), c.D, logits, c.V, rows, c.V, c.D, nullptr, 0, s);
+    if (logits) gemm({w.xn, c.D}, gemm_args(c, {w.to_logits, c.D}, {logits, c.V}, rows, c.V, c.D), s);
 }
 
-void maskgit_generate(Ctx& c, const int64_t* cond, const float* I_inv, const float* E_inv, int B, int timesteps, const int32_t* sched, float temperature,
-                      int topk_k, float critic_noise_scale, const float* gumbel_u, const float* critic_u, const int64_t* init_ids, int64_t* out, hipStream_t s,
-                      unsigned long long noise_seed, int score_mode, int samples_per_layout) {
+void maskgit_generate(Ctx& c, const MuseBatch& in, const MaskgitSampling& sp, int64_t* out, hipStream_t s) {
+    const int timesteps = sp.timesteps, score_mode = sp.score_mode;
     BG_REQUIRE(c.cfg.route == BEVGEN_ROUTE_MASKGIT, "context was not created for the MaskGit route");
-    BG_REQUIRE(B >= 1 && timesteps >= 1 && sched, "bad generate arguments");
+    BG_REQUIRE(in.B >= 1 && timesteps >= 1 && sp.sched, "bad generate arguments");
     BG_REQUIRE(score_mode != 0 || c.find("token_critic.to_pred.weight"), "maskgit_generate: the context holds no token critic (token_critic.to_pred.*): use score_mode 1 / 2");
     BG_REQUIRE(score_mode >= 0 && score_mode <= 2, "score_mode %d: 0 token critic, 1 softmax confidence, 2 softmax confidence with re-masking of earlier tokens", score_mode);
     MuseWs w;
-    muse_prepare(c, w, cond, I_inv, E_inv, B, s, samples_per_layout, true);
+    muse_prepare(c, w, in, true, s);
     const int rows = (int)w.rows;            // B*C*T token rows
-    const int seqs = B * c.cfg.num_cams;     // rows of the [B*C, T] id matrix
+    const int seqs = in.B * c.cfg.num_cams;  // rows of the [B*C, T] id matrix
     const int T = c.T, V = c.V, D = c.D;
     float *logits = w.logits, *scores = w.scores;
     const int64_t mask_id = c.cfg.vocab_size;
@@ -443,17 +439,17 @@ void maskgit_generate(Ctx& c, const int64_t* cond, const float* I_inv, const flo
     for (int step = 0; step < timesteps; ++step) {
         const int steps_until_x0 = timesteps - 1 - step;
         const double frac = (double)steps_until_x0 / (double)timesteps;
-        launch_remask(ids, scores, init_ids, seqs, T, sched[step], mask_id, s);
+        launch_remask(ids, scores, sp.init_ids, seqs, T, sp.sched[step], mask_id, s);
         muse_blocks(c, w, ids, s);
-        gemm(w.xn, D, c.pf("transformer.to_logits.weight"), D, logits, V, rows, V, D, nullptr, 0, s);
+        gemm({w.xn, D}, gemm_args(c, {w.to_logits, D}, {logits, V}, rows, V, D), s);
         // score_mode 1 / 2 (force_not_use_token_critic, muse_net:611-622): the scores come out of the pick itself (1 - softmax(logits)[pred]) and the critic forward
         // is not run at all - 18 transformer forwards per call instead of 35
-        launch_maskgit_pick(ids, logits, V, gumbel_u ? gumbel_u + (size_t)step * rows * V : nullptr, rows, V, topk_k, (float)((double)temperature * frac), mask_id, s,
-                            noise_seed, (unsigned)step, score_mode ? scores : nullptr, score_mode);
+        launch_maskgit_pick(ids, logits, V, sp.gumbel_u ? sp.gumbel_u + (size_t)step * rows * V : nullptr, rows, V, sp.topk_k, (float)((double)sp.temperature * frac), mask_id, s,
+                            sp.noise_seed, (unsigned)step, score_mode ? scores : nullptr, score_mode);
         if (score_mode == 0 && step + 1 < timesteps) {  // the critic scores only select what the NEXT iteration re-masks
             muse_blocks(c, w, ids, s);
-            launch_critic_scores(w.xn, D, c.pf("token_critic.to_pred.weight"), c.pf("token_critic.to_pred.bias"),
-                                 critic_u ? critic_u + (size_t)step * rows : nullptr, critic_noise_scale, (float)frac, scores, rows, D, s, noise_seed, (unsigned)step);
+            launch_critic_scores(w.xn, D, w.critic_w, w.critic_b, sp.critic_u ? sp.critic_u + (size_t)step * rows : nullptr, sp.critic_noise_scale, (float)frac, scores, rows, D, s,
+                                 sp.noise_seed, (unsigned)step);
         }
     }
 }

@@ -8,6 +8,7 @@
 #                       with the gpurun snapshot and is git-ignored)
 #               env     an environment switch:                 spec = "VAR=v1,v2[,v3 ...]"
 #   ROUNDS (default 2 for decode, 3 for m) repetitions; results also appended to gpurun_out/ab_<workload>.txt
+#   workload m: every bench run has its own time limit (LIMIT seconds, default 600) and the first run that fails ends the script - nothing more is started on the GPU
 R=${GRAFT_REPO_ROOT:-/root/repo}; O=$R/gpurun_out; mkdir -p $O; cd $R
 W=$1; AXIS=$2; SPEC=$3; shift 3
 case $AXIS in
@@ -24,10 +25,11 @@ select_variant() {
 OUT=$O/ab_$W.txt; : > $OUT
 if [ $W = m ]; then
   export BEVGEN_BENCH_NO_PMC=1
+  set -o pipefail
   for i in $(seq ${ROUNDS:-3}); do for v in $VARIANTS; do
     select_variant $v
-    python bench.py --full --steps 3 --warmup 1 --no-decode-leg --no-extra-legs --no-cpu-baseline --no-exact-leg "$@" 2>/dev/null | python -c "
-import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); l=d['legs']; print('$TAG', 'scenes/s', round(d['value'],3), 'ms/step', round(d['ms_per_step'],1), 'it', round(l['ms_per_maskgit_iteration'],2), 'vq/scene', round(l.get('vqgan_decode_ms_per_scene',0),2), {k: round(x,3) for k,x in l['kernel_time_share'].items()}, {k: round(x,1) for k,x in l['kernel_tflops'].items()})" | tee -a $OUT
+    timeout -k 10 ${LIMIT:-600} python bench.py --full --steps 3 --warmup 1 --no-decode-leg --no-extra-legs --no-cpu-baseline --no-exact-leg "$@" 2>/dev/null | python -c "
+import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); l=d['legs']; print('$TAG', 'scenes/s', round(d['value'],3), 'ms/step', round(d['ms_per_step'],1), 'it', round(l['ms_per_maskgit_iteration'],2), 'vq/scene', round(l.get('vqgan_decode_ms_per_scene',0),2), {k: round(x,3) for k,x in l['kernel_time_share'].items()}, {k: round(x,1) for k,x in l['kernel_tflops'].items()})" | tee -a $OUT || { echo "run $TAG of round $i failed: stopping" | tee -a $OUT; exit 1; }
   done; done
 elif [ $W = decode ]; then
   STEPS=${1:-2100}; MODES=${2:-"f16:f16 f16:f32 f32:f32"}
