@@ -12,6 +12,7 @@
 #include "common.h"
 #include "kernels.h"
 #include "profiler.h"
+#include "vq_plan.h"
 
 namespace bevgen {
 
@@ -135,6 +136,7 @@ struct Ctx {
     AttnBlockW enc_mid_attn;
     const float *enc_norm_out_w = nullptr, *enc_norm_out_b = nullptr;
     float* codebook_sqnorm = nullptr;
+    VqShape vq_dec_shape, vq_enc_shape;   // what vq_plan.h needs to know of the loaded decoder / encoder (vq_finalize)
 
     // ---- split-precision mode (BEVGEN_PRECISION_F16X3): (hi, lo) f16 planes of every GEMM / conv weight, keyed by its fp32 device pointer
     std::unordered_map<const float*, SplitPlanes> split;

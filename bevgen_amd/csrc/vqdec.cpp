@@ -9,6 +9,9 @@
 //   1x1 conv  -> plain GEMM over pixels
 //   AttnBlock -> four 1x1 GEMMs + batched Q K^T / softmax / P V GEMMs (single head of width C, 256 tokens)
 // GroupNorm(32)+swish is a stats pass + an elementwise pass; residual adds ride in the GEMM epilogues.
+//
+// Structure: vq_plan.h holds what is pure (sizes, pass cut, site count, upsample form); `Pass` below holds one pass over up to 48 images - its buffers, the current
+// activation and every launch that writes one; vq_decode / vq_encode are the list of steps.
 #include "model.h"
 
 namespace bevgen {
@@ -52,221 +55,440 @@ AttnBlockW load_attn(Ctx& c, const std::string& p) {
     return a;
 }
 
-struct Act { float* p; int n, h, w, c; long elems() const { return (long)n * h * w * c; } };
+// the plan's shape (vq_plan.h) of one direction, from the configuration and, level by level, from the loaded weights
+VqShape shape_of(const bevgen_cfg& g, bool encoder, int cin_pad, const ResBlockW& mid1, const ResBlockW& mid2) {
+    VqShape sh;
+    sh.encoder = encoder;
+    sh.levels = g.vq_num_levels; sh.ch = g.vq_ch; sh.cin_pad = cin_pad;
+    for (int l = 0; l < sh.levels; ++l) sh.ch_mult[l] = g.vq_ch_mult[l];
+    sh.mid_nin = (mid1.has_nin ? 1 : 0) + (mid2.has_nin ? 1 : 0);
+    return sh;
+}
+void shape_level(VqShape& sh, int lvl, const std::vector<ResBlockW>& blocks, bool attn, bool resample) {
+    for (const ResBlockW& r : blocks) sh.nin[lvl] += r.has_nin ? 1 : 0;
+    sh.first_nin[lvl] = !blocks.empty() && blocks[0].has_nin;
+    sh.attn[lvl] = attn;
+    sh.resample[lvl] = resample;
+}
+
+// the four A/B switches of this file, read once per process
+const VqSwitches& vq_switches() {
+    static const VqSwitches sw = [] {
+        const auto on = [](const char* name) { const char* v = getenv(name); return !v || atoi(v) != 0; };   // unset = on
+        VqSwitches r;
+        r.gn_epilogue = on("BEVGEN_GN_EPILOGUE");
+        r.enc_fuse = on("BEVGEN_VQ_ENC_FUSE");
+        r.up_planes = on("BEVGEN_VQ_UP_PLANES");
+        r.tail = on("BEVGEN_VQ_TAIL");
+        return r;
+    }();
+    return sw;
+}
+
+// planes: p holds the interleaved (hi, lo) f16 plane image of the activation (written by Pass::gn / Pass::to_planes) instead of fp32
+struct Act { float* p; int n, h, w, c; bool planes = false; long elems() const { return (long)n * h * w * c; } };
 
 // GroupNorm statistics of a tensor as partial sums out of the epilogue of the convolution that produced it (GemmArgs::gn_part): `of` names the tensor they describe.
-// Every writer of an activation buffer goes through note_write() so that a stale association can never be used.
+// Every writer of an activation buffer is a method of Pass and goes through note_write() so that a stale association can never be used.
 struct GnPart { float* buf = nullptr; const float* of = nullptr; };
-static void note_write(GnPart* gp, const float* y) { if (gp && gp->of == y) gp->of = nullptr; }
-
-static bool gn_epilogue() {
-    static const int gn_epi = getenv("BEVGEN_GN_EPILOGUE") ? atoi(getenv("BEVGEN_GN_EPILOGUE")) : 1;   // (0: always the statistics pass, for A/B runs)
-    return gn_epi != 0;
-}
-
-// planes: x.p holds the interleaved (hi, lo) f16 plane image of the activation (written by gn(..., planes = true)) instead of fp32
-void conv3(const Act& x, const ConvW& w, float* y, const float* residual, int up, hipStream_t s, bool planes = false, GnPart* gp = nullptr) {
-    GemmArgs g;
-    note_write(gp, y);
-    const int oh = up ? x.h * 2 : x.h, ow = up ? x.w * 2 : x.w;
-    g.mode = MODE_CONV3;
-    if (planes) { g.A_hi = reinterpret_cast<const uint16_t*>(x.p); g.A_lo = g.A_hi + 32; }
-    else g.A = x.p;
-    g.B = w.w; g.C = y; g.R = residual; g.bias_n = w.b;
-    g.M = x.n * oh * ow; g.N = w.cout; g.K = 9 * w.cin;
-    g.lda = w.cin; g.ldb = 9 * w.cin; g.ldc = w.cout; g.ldr = w.cout;
-    g.conv_h = oh; g.conv_w = ow; g.conv_cin = w.cin; g.conv_up = up;
-    // the LDS-DMA kernel (plane input) also leaves the GroupNorm partial sums of its output where the shape allows: the consumer's statistics pass disappears
-    if (gn_epilogue() && gp && gp->buf && planes && groupnorm_partials_supported(oh * ow, w.cout)) { g.gn_part = gp->buf; gp->of = y; }
-    launch_gemm(g, s);
-}
-
-void conv1(const float* x, long rows, const ConvW& w, float* y, const float* residual, hipStream_t s, GnPart* gp = nullptr) {
-    note_write(gp, y);
-    GemmArgs g;
-    g.A = x; g.B = w.w; g.C = y; g.R = residual; g.bias_n = w.b;
-    g.M = (int)rows; g.N = w.cout; g.K = w.cin;
-    g.lda = w.cin; g.ldb = w.cin; g.ldc = w.cout; g.ldr = w.cout;
-    launch_gemm(g, s);
-}
+void note_write(GnPart& gp, const float* y) { if (gp.of == y) gp.of = nullptr; }
 
 // Range-safe mode (cfg.vq_range, split precision): the sites where an UN-normalised activation becomes an f16 operand take a per-tensor exponent from the next slot
 // (kernels.h launch_range_*).  Decoder: conv_in (reads post_quant_conv's output), every nin_shortcut and every upsample convolution (both read the residual stream).
 // Encoder: conv_in (reads the caller's image), every nin_shortcut and every downsample convolution (residual stream), quant_conv (reads conv_out's output).
 // Everything else on the path reads a GroupNorm output or softmax-weighted values of one, or runs on the exact-fp32 kernel (the batched attention products, the
 // quantizer's codebook products); the codebook and the weights are parameters, refused as before.
-// pre_of: the tensor whose exponent a fused pass has already left in the next slot (range_next_slot): the site that reads it takes the slot without a pass of its own.
+// cap is vq_sites_per_pass x passes (vq_plan.h) and a decode / encode call must use exactly that many (sites_done).
+// pre_of: the tensor whose exponent a fused pass has already left in the next slot (next_slot): the site that reads it takes the slot without a pass of its own.
 struct RangeSites { int* exps = nullptr; unsigned* amax = nullptr; int used = 0, cap = 0; const float* pre_of = nullptr; };
 
-struct DecWs {
-    float *a, *b, *t;   // ping-pong activations + temp (each max_act floats)
-    float* stats;       // [n*32*2]
-    void* gn_ws;
-    float *q, *k, *vT, *S;
-    float *o, *zq, *img, *dots, *zz;   // third rotating activation buffer; latents; decode: pixel staging / encode: codebook products and row norms
-    GnPart part;        // epilogue partials of the most recent convolution output (buf: groupnorm_part_floats of the widest level, or null)
-    RangeSites* range = nullptr;   // non-null: range-safe mode
+// the slots of a decode / encode call of `cap` sites (0: not the range-safe mode), zeroed
+RangeSites sites_reserve(Ctx& c, int cap, hipStream_t s) {
+    RangeSites r;
+    c.vq_range_used = 0;
+    if (cap == 0) return r;
+    r.cap = cap;
+    c.vq_range_slots.reserve((size_t)cap * 8);
+    r.exps = reinterpret_cast<int*>(c.vq_range_slots.base);
+    r.amax = reinterpret_cast<unsigned*>(r.exps + cap);
+    HIP_CHECK(hipMemsetAsync(r.exps, 0, (size_t)cap * 8, s));
+    return r;
+}
+void sites_done(Ctx& c, const RangeSites& r) {
+    BG_REQUIRE(r.used == r.cap, "vq: the passes ran %d range-safe sites, the plan counted %d", r.used, r.cap);
+    c.vq_range_used = r.used;
+}
+
+// a 3x3 convolution of x as an implicit GEMM: 'same' (stride 1, padding 1), behind a fused nearest-2x upsample, or the encoder's Downsample (stage1/model.py:56-75:
+// F.pad(x, (0,1,0,1)) + stride 2, padding 0; x.h and x.w even; the bottom / right zero padding is the gather's bounds test).  The caller adds C and R.
+enum ConvGeom { CONV_SAME, CONV_UP2, CONV_DOWN2 };
+GemmArgs conv3_args(const Act& x, const ConvW& w, ConvGeom geom) {
+    GemmArgs g;
+    const int oh = geom == CONV_UP2 ? x.h * 2 : geom == CONV_DOWN2 ? x.h / 2 : x.h, ow = geom == CONV_UP2 ? x.w * 2 : geom == CONV_DOWN2 ? x.w / 2 : x.w;
+    g.mode = MODE_CONV3;
+    if (x.planes) { g.A_hi = reinterpret_cast<const uint16_t*>(x.p); g.A_lo = g.A_hi + 32; }
+    else g.A = x.p;
+    g.B = w.w; g.bias_n = w.b;
+    g.M = x.n * oh * ow; g.N = w.cout; g.K = 9 * w.cin;
+    g.lda = w.cin; g.ldb = 9 * w.cin; g.ldc = w.cout; g.ldr = w.cout;
+    g.conv_h = oh; g.conv_w = ow; g.conv_cin = w.cin; g.conv_up = geom == CONV_UP2;
+    if (geom == CONV_DOWN2) { g.conv_hin = x.h; g.conv_win = x.w; g.conv_stride = 2; g.conv_pad = 0; }
+    return g;
+}
+
+// One range-safe site: x 2^-e into `tmp` (x's size), W x' without the bias, then y = 2^e y + b.
+struct RangedOpts {
+    int k = 3;                    // 1: a 1x1 convolution (geom unused)
+    ConvGeom geom = CONV_SAME;
+    bool plane_operand = false;   // x 2^-e is written as the (hi, lo) plane image and the convolution runs on the LDS-DMA kernel, instead of fp32
+    bool leave_partials = false;  // the last pass also leaves the GroupNorm partials of y where the convolution's epilogue would have (it cannot: they would describe the unscaled sums)
+    bool y_feeds_site = false;    // y is the next site's operand: the last pass also leaves that site's exponent (next_slot)
+    const int* e = nullptr;       // the exponent, where the caller has one; null: the next slot (range_exponent)
 };
 
-const int* range_exponent(DecWs& ws, const Act& x, hipStream_t s) {
-    RangeSites& r = *ws.range;
-    BG_REQUIRE(r.used < r.cap, "vq: more range-safe sites than counted (%d)", r.cap);
-    BG_REQUIRE(!r.pre_of || r.pre_of == x.p, "vq: the next range-safe slot was prepared for another tensor");
-    if (r.pre_of) r.pre_of = nullptr;
-    else launch_range_exponent(x.p, x.elems(), r.amax + r.used, r.exps + r.used, s);
-    return r.exps + r.used++;
-}
+// the decoder's last step: out_mode as in vq_decode; mean / stdv are read for out_mode != 0 only; img: [n, h w, 4] scratch of the three-kernel form
+struct TailOut { void* out; int out_mode; const float *mean, *stdv; float* img; bool fused; };
 
-// the slot the NEXT site takes, for a pass that writes that site's operand `of` and leaves its exponent on the way (launch_*_amax)
-struct NextSlot { unsigned* amax; int* e; };
-NextSlot range_next_slot(DecWs& ws, const float* of) {
-    RangeSites& r = *ws.range;
-    BG_REQUIRE(r.used < r.cap && !r.pre_of, "vq: more range-safe sites than counted (%d)", r.cap);
-    r.pre_of = of;
-    return NextSlot{r.amax + r.used, r.exps + r.used};
-}
+// One pass over n images: the carved buffers, the current activation and every launch that writes an activation buffer.
+struct Pass {
+    hipStream_t s = nullptr;
+    // three rotating activation buffers (input / scratch / output of a block) + t for the normalised tensor (each per_img x n floats)
+    float *a = nullptr, *b = nullptr, *o = nullptr, *t = nullptr;
+    float* stats = nullptr;   // [n*32*2]
+    void* gn_ws = nullptr;
+    float *q = nullptr, *k = nullptr, *vT = nullptr, *S = nullptr;
+    float* zq = nullptr;      // latents [n, lat_h lat_w, embed_dim]
+    Act x{};                  // the current activation: in a, b or o
+    GnPart part;              // epilogue partials of the most recent convolution output (buf: groupnorm_part_floats of the widest level, or null)
+    RangeSites* range = nullptr;   // non-null: range-safe mode
+    bool planes = false;      // split-precision mode: GroupNorm writes (hi, lo) planes, convolutions read them by LDS-DMA
+    bool encoder = false;
 
-// the encoder's two fused passes (0: their unfused pairs, for A/B runs)
-static bool enc_fuse() {
-    static const int fuse = getenv("BEVGEN_VQ_ENC_FUSE") ? atoi(getenv("BEVGEN_VQ_ENC_FUSE")) : 1;
-    return fuse != 0;
-}
-
-// range-safe form of a convolution that reads the un-normalised fp32 tensor x itself: x 2^-e into `tmp` (x's size), W x' without the bias, then y = 2^e y + b.
-// k = 1: 1x1, k = 3: 3x3 (up: fused nearest-2x upsample; down: the encoder's Downsample, conv3_down).  y_feeds_site: y is the next site's operand - the last pass also
-// leaves that site's exponent (range_next_slot)
-void conv3_down(const Act& x, const ConvW& w, float* y, hipStream_t s);
-void conv_ranged(const Act& x, const ConvW& w, int k, int up, float* tmp, float* y, DecWs& ws, hipStream_t s, int down = 0, bool y_feeds_site = false) {
-    const int* e = range_exponent(ws, x, s);
-    note_write(&ws.part, tmp);
-    launch_range_scale(x.p, tmp, x.elems(), e, s);
-    ConvW wb = w;
-    wb.b = nullptr;
-    const long rows = down ? (long)x.n * (x.h / 2) * (x.w / 2) : (long)x.n * x.h * x.w * (up ? 4 : 1);
-    if (k == 1) conv1(tmp, rows, wb, y, nullptr, s, &ws.part);
-    else if (down) { note_write(&ws.part, y); conv3_down(Act{tmp, x.n, x.h, x.w, x.c}, wb, y, s); }
-    else conv3(Act{tmp, x.n, x.h, x.w, x.c}, wb, y, nullptr, up, s, false, &ws.part);
-    if (y_feeds_site && enc_fuse()) {
-        const NextSlot nx = range_next_slot(ws, y);
-        launch_range_unscale_amax(y, w.b, rows, w.cout, e, nx.amax, nx.e, s);
-    } else {
-        launch_range_unscale(y, w.b, nullptr, rows, w.cout, e, nullptr, s);
+    // ---- the rotation: the buffers that are not x
+    struct Two { float *first, *second; };
+    Two others() const {
+        float* r[2] = {nullptr, nullptr};
+        int i = 0;
+        for (float* buf : {a, b, o}) if (buf != x.p && i < 2) r[i++] = buf;
+        return Two{r[0], r[1]};
     }
-}
+    float* other() const { return others().first; }
 
-// statistics of x: from the producing convolution's epilogue partials when they describe exactly this tensor, else the pass over the tensor
-void gn_stats(const Act& x, DecWs& ws, hipStream_t s) {
-    if (ws.part.of == x.p && ws.part.buf) launch_groupnorm_stats_from_partials(ws.part.buf, ws.stats, x.n, x.h * x.w, x.c, 1e-6f, s);
-    else launch_groupnorm_stats(x.p, ws.stats, ws.gn_ws, x.n, x.h * x.w, x.c, 1e-6f, s);
-}
-
-void gn(const Act& x, const float* w, const float* b, float* y, int swish, DecWs& ws, hipStream_t s, bool planes = false) {
-    gn_stats(x, ws, s);
-    note_write(&ws.part, y);
-    if (planes) launch_groupnorm_apply_planes(x.p, ws.stats, w, b, y, x.n, x.h * x.w, x.c, swish, s);
-    else launch_groupnorm_apply(x.p, ws.stats, w, b, y, x.n, x.h * x.w, x.c, swish, s);
-}
-
-// x (in ws.a-or-b) -> out buffer `y`; uses ws.t and the other ping-pong buffer as scratch
-void resblock(const ResBlockW& r, Act& x, float* y, float* scratch, DecWs& ws, hipStream_t s, bool planes) {
-    // h = conv1(swish(norm1(x)));  split-precision mode: the normalised activation is written directly as the (hi, lo) planes the convolution reads
-    gn(x, r.n1w, r.n1b, ws.t, 1, ws, s, planes);
-    Act t{ws.t, x.n, x.h, x.w, r.cin};
-    conv3(t, r.c1, scratch, nullptr, 0, s, planes, &ws.part);
-    Act h1{scratch, x.n, x.h, x.w, r.cout};
-    gn(h1, r.n2w, r.n2b, ws.t, 1, ws, s, planes);
-    Act t2{ws.t, x.n, x.h, x.w, r.cout};
-    const float* shortcut = x.p;
-    if (r.has_nin) {  // x = nin_shortcut(x)  (1x1), written over h1 (no longer needed after norm2)
-        if (ws.range) conv_ranged(x, r.nin, 1, 0, y, scratch, ws, s);   // (y is free until conv2 writes it)
-        else conv1(x.p, (long)x.n * x.h * x.w, r.nin, scratch, nullptr, s, &ws.part);
-        shortcut = scratch;
+    // ---- range-safe slots
+    const int* range_exponent(const Act& in) {
+        RangeSites& r = *range;
+        BG_REQUIRE(r.used < r.cap, "vq: more range-safe sites than counted (%d)", r.cap);
+        BG_REQUIRE(!r.pre_of || r.pre_of == in.p, "vq: the next range-safe slot was prepared for another tensor");
+        if (r.pre_of) r.pre_of = nullptr;
+        else launch_range_exponent(in.p, in.elems(), r.amax + r.used, r.exps + r.used, s);
+        return r.exps + r.used++;
     }
-    conv3(t2, r.c2, y, shortcut, 0, s, planes, &ws.part);  // y = x + conv2(...); its epilogue also leaves the statistics the next block's norm1 needs
-    x = Act{y, x.n, x.h, x.w, r.cout};
-}
+    // the slot the NEXT site takes, for a pass that writes that site's operand `of` and leaves its exponent on the way (launch_*_amax)
+    struct NextSlot { unsigned* amax; int* e; };
+    NextSlot next_slot(const float* of) {
+        RangeSites& r = *range;
+        BG_REQUIRE(r.used < r.cap && !r.pre_of, "vq: more range-safe sites than counted (%d)", r.cap);
+        r.pre_of = of;
+        return NextSlot{r.amax + r.used, r.exps + r.used};
+    }
 
-void attnblock(const AttnBlockW& a, Act& x, float* y, DecWs& ws, hipStream_t s) {
-    const int hw = x.h * x.w, C = a.c, n = x.n;
-    const int hwp = (int)round_up(hw, 32);   // key dimension padded to the GEMM's k granularity (non-square latents: 14 x 25 = 350 -> 352); pad keys carry P = 0, v = 0
-    const long rows = (long)n * hw;
-    gn(x, a.nw, a.nb, ws.t, 0, ws, s);
-    conv1(ws.t, rows, a.q, ws.q, nullptr, s);
-    conv1(ws.t, rows, a.k, ws.k, nullptr, s);
-    if (hwp != hw) HIP_CHECK(hipMemsetAsync(ws.vT, 0, (size_t)n * C * hwp * sizeof(float), s));
-    {   // vT[img] [C, hw] = Wv [C,C] * h_img^T + bias (per row)
+    // ---- writers: every launch into a, b, o or t
+    void conv1(const float* in, long rows, const ConvW& w, float* y, const float* residual) {
+        note_write(part, y);
         GemmArgs g;
-        g.A = a.v.w; g.B = ws.t; g.C = ws.vT; g.bias_m = a.v.b;
-        g.M = C; g.N = hw; g.K = C; g.lda = C; g.ldb = C; g.ldc = hwp;
-        g.batch = n; g.strideA = 0; g.strideB = (long)hw * C; g.strideC = (long)C * hwp;
+        g.A = in; g.B = w.w; g.C = y; g.R = residual; g.bias_n = w.b;
+        g.M = (int)rows; g.N = w.cout; g.K = w.cin;
+        g.lda = w.cin; g.ldb = w.cin; g.ldc = w.cout; g.ldr = w.cout;
         launch_gemm(g, s);
     }
-    {   // S[img] [hw, hw] = q k^T
-        GemmArgs g;
-        g.A = ws.q; g.B = ws.k; g.C = ws.S;
-        g.M = hw; g.N = hw; g.K = C; g.lda = C; g.ldb = C; g.ldc = hwp;
-        g.batch = n; g.strideA = (long)hw * C; g.strideB = (long)hw * C; g.strideC = (long)hw * hwp;
+    // stats: the LDS-DMA kernel (plane input) also leaves the GroupNorm partial sums of its output where the shape allows: the consumer's statistics pass disappears
+    void conv3(const Act& in, const ConvW& w, float* y, ConvGeom geom, const float* residual = nullptr, bool stats = true) {
+        note_write(part, y);
+        GemmArgs g = conv3_args(in, w, geom);
+        g.C = y; g.R = residual;
+        if (stats && vq_switches().gn_epilogue && part.buf && in.planes && groupnorm_partials_supported(g.conv_h * g.conv_w, w.cout)) { g.gn_part = part.buf; part.of = y; }
         launch_gemm(g, s);
     }
-    launch_row_softmax(ws.S, (int)rows, hw, 1.0f / sqrtf((float)C), s, hwp);  // w_ * int(c)**-0.5, softmax over keys
-    {   // O[img] [hw, C] = P [hw,hw] * v [hw, C]  (B operand = vT [C, hw])
-        GemmArgs g;
-        g.A = ws.S; g.B = ws.vT; g.C = ws.q;  // reuse q as the output buffer
-        g.M = hw; g.N = C; g.K = hwp; g.lda = hwp; g.ldb = hwp; g.ldc = C;
-        g.batch = n; g.strideA = (long)hw * hwp; g.strideB = (long)C * hwp; g.strideC = (long)hw * C;
-        launch_gemm(g, s);
+    // statistics of `in`: from the producing convolution's epilogue partials when they describe exactly this tensor, else the pass over the tensor
+    void gn_stats(const Act& in) {
+        if (part.of == in.p && part.buf) launch_groupnorm_stats_from_partials(part.buf, stats, in.n, in.h * in.w, in.c, 1e-6f, s);
+        else launch_groupnorm_stats(in.p, stats, gn_ws, in.n, in.h * in.w, in.c, 1e-6f, s);
     }
-    conv1(ws.q, rows, a.proj, y, x.p, s, &ws.part);  // x + proj_out(h)
-    x = Act{y, n, x.h, x.w, C};
+    Act gn(const Act& in, const float* w, const float* b_, float* y, int swish, bool as_planes) {
+        gn_stats(in);
+        note_write(part, y);
+        if (as_planes) launch_groupnorm_apply_planes(in.p, stats, w, b_, y, in.n, in.h * in.w, in.c, swish, s);
+        else launch_groupnorm_apply(in.p, stats, w, b_, y, in.n, in.h * in.w, in.c, swish, s);
+        return Act{y, in.n, in.h, in.w, in.c, as_planes};
+    }
+    // `in` (x 2^-e with an exponent) as the (hi, lo) plane image
+    Act to_planes(const Act& in, float* y, const int* e) {
+        note_write(part, y);
+        if (e) launch_range_split(in.p, y, (long)in.n * in.h * in.w, in.c, e, s);
+        else launch_to_planes(in.p, y, in.n, in.h * in.w, in.c, s);
+        return Act{y, in.n, in.h, in.w, in.c, true};
+    }
+    Act scale(const Act& in, float* y, const int* e) {
+        note_write(part, y);
+        launch_range_scale(in.p, y, in.elems(), e, s);
+        return Act{y, in.n, in.h, in.w, in.c};
+    }
+    // y = 2^e y + b over y [n, hw, w.cout]
+    void unscale(float* y, const ConvW& w, int n, int hw, const int* e, const RangedOpts& o_) {
+        note_write(part, y);
+        const long rows = (long)n * hw;
+        if (o_.y_feeds_site && vq_switches().enc_fuse) {
+            const NextSlot nx = next_slot(y);
+            launch_range_unscale_amax(y, w.b, rows, w.cout, e, nx.amax, nx.e, s);
+            return;
+        }
+        const bool leave = o_.leave_partials && vq_switches().gn_epilogue && part.buf && groupnorm_partials_supported(hw, w.cout);
+        launch_range_unscale(y, w.b, nullptr, rows, w.cout, e, leave ? part.buf : nullptr, s);
+        if (leave) part.of = y;
+    }
+    // the encoder's image, NCHW -> NHWC with the channels padded, into t; range-safe mode: the layout change also leaves the image's exponent, so that conv_in's site needs
+    // no pass of its own over the padded tensor
+    Act load_image(const float* x_nchw, int n, int h, int w, int cin, int cin_pad) {
+        note_write(part, t);
+        if (range && vq_switches().enc_fuse) {
+            const NextSlot nx = next_slot(t);
+            launch_nchw_to_nhwc_pad_amax(x_nchw, t, n, h * w, cin, cin_pad, nx.amax, nx.e, s);
+        } else {
+            launch_nchw_to_nhwc_pad(x_nchw, t, n, h * w, cin, cin_pad, s);
+        }
+        return Act{t, n, h, w, cin_pad};
+    }
+
+    // ---- the range-safe site (RangedOpts)
+    void ranged(const Act& in, const ConvW& w, float* tmp, float* y, const RangedOpts& o_) {
+        const int* e = o_.e ? o_.e : range_exponent(in);
+        const Act xs = o_.plane_operand ? to_planes(in, tmp, e) : scale(in, tmp, e);
+        ConvW wb = w;
+        wb.b = nullptr;
+        const int hw = o_.k == 1 || o_.geom == CONV_SAME ? in.h * in.w : o_.geom == CONV_UP2 ? 4 * in.h * in.w : (in.h / 2) * (in.w / 2);
+        if (o_.k == 1) conv1(tmp, (long)in.n * hw, wb, y, nullptr);
+        else conv3(xs, wb, y, o_.geom, nullptr, false);
+        unscale(y, w, in.n, hw, e, o_);
+    }
+
+    // ---- steps: x -> the step's output
+    void conv_in(const Act& in, const ConvW& w) {   // `in` is in t
+        if (range) ranged(in, w, b, a, RangedOpts{});
+        else conv3(in, w, a, CONV_SAME);
+        x = Act{a, in.n, in.h, in.w, w.cout};
+    }
+    void res(const ResBlockW& r) {
+        const Two free = others();
+        float *scratch = free.first, *y = free.second;
+        // h = conv1(swish(norm1(x)));  split-precision mode: the normalised activation is written directly as the (hi, lo) planes the convolution reads
+        conv3(gn(x, r.n1w, r.n1b, t, 1, planes), r.c1, scratch, CONV_SAME);
+        const Act t2 = gn(Act{scratch, x.n, x.h, x.w, r.cout}, r.n2w, r.n2b, t, 1, planes);
+        const float* shortcut = x.p;
+        if (r.has_nin) {  // x = nin_shortcut(x)  (1x1), written over h1 (no longer needed after norm2)
+            RangedOpts one;
+            one.k = 1;
+            if (range) ranged(x, r.nin, y, scratch, one);   // (y is free until conv2 writes it)
+            else conv1(x.p, (long)x.n * x.h * x.w, r.nin, scratch, nullptr);
+            shortcut = scratch;
+        }
+        conv3(t2, r.c2, y, CONV_SAME, shortcut);  // y = x + conv2(...); its epilogue also leaves the statistics the next block's norm1 needs
+        x = Act{y, x.n, x.h, x.w, r.cout};
+    }
+    void attn(const AttnBlockW& ab) {
+        float* y = encoder ? others().second : other();   // (the two directions have always rotated differently here)
+        const int hw = x.h * x.w, C = ab.c, n = x.n;
+        const int hwp = (int)round_up(hw, 32);   // key dimension padded to the GEMM's k granularity (non-square latents: 14 x 25 = 350 -> 352); pad keys carry P = 0, v = 0
+        const long rows = (long)n * hw;
+        gn(x, ab.nw, ab.nb, t, 0, false);
+        conv1(t, rows, ab.q, q, nullptr);
+        conv1(t, rows, ab.k, k, nullptr);
+        if (hwp != hw) HIP_CHECK(hipMemsetAsync(vT, 0, (size_t)n * C * hwp * sizeof(float), s));
+        {   // vT[img] [C, hw] = Wv [C,C] * h_img^T + bias (per row)
+            GemmArgs g;
+            g.A = ab.v.w; g.B = t; g.C = vT; g.bias_m = ab.v.b;
+            g.M = C; g.N = hw; g.K = C; g.lda = C; g.ldb = C; g.ldc = hwp;
+            g.batch = n; g.strideA = 0; g.strideB = (long)hw * C; g.strideC = (long)C * hwp;
+            launch_gemm(g, s);
+        }
+        {   // S[img] [hw, hw] = q k^T
+            GemmArgs g;
+            g.A = q; g.B = k; g.C = S;
+            g.M = hw; g.N = hw; g.K = C; g.lda = C; g.ldb = C; g.ldc = hwp;
+            g.batch = n; g.strideA = (long)hw * C; g.strideB = (long)hw * C; g.strideC = (long)hw * hwp;
+            launch_gemm(g, s);
+        }
+        launch_row_softmax(S, (int)rows, hw, 1.0f / sqrtf((float)C), s, hwp);  // w_ * int(c)**-0.5, softmax over keys
+        {   // O[img] [hw, C] = P [hw,hw] * v [hw, C]  (B operand = vT [C, hw])
+            GemmArgs g;
+            g.A = S; g.B = vT; g.C = q;  // reuse q as the output buffer
+            g.M = hw; g.N = C; g.K = hwp; g.lda = hwp; g.ldb = hwp; g.ldc = C;
+            g.batch = n; g.strideA = (long)hw * hwp; g.strideB = (long)C * hwp; g.strideC = (long)hw * C;
+            launch_gemm(g, s);
+        }
+        conv1(q, rows, ab.proj, y, x.p);  // x + proj_out(h)
+        x = Act{y, n, x.h, x.w, C};
+    }
+    // Upsample: nearest 2x + 3x3 conv, fused (the three forms: vq_plan.h)
+    void up(const ConvW& w) {
+        float* y = other();
+        RangedOpts ro;
+        ro.geom = CONV_UP2;
+        switch (vq_up_form(x.c, planes, range != nullptr, vq_switches())) {
+        case VQ_UP_PLANES:
+            ro.plane_operand = ro.leave_partials = true;
+            if (range) ranged(x, w, t, y, ro);
+            else conv3(to_planes(x, t, nullptr), w, y, CONV_UP2);
+            break;
+        case VQ_UP_RANGED_F32: ranged(x, w, t, y, ro); break;
+        case VQ_UP_PLAIN: conv3(x, w, y, CONV_UP2); break;
+        }
+        x = Act{y, x.n, x.h * 2, x.w * 2, w.cout};
+    }
+    // Downsample; feeds_site: the output is the operand of the next level's nin_shortcut (vq_feeds_nin)
+    void down(const ConvW& w, bool feeds_site) {
+        const Two free = others();
+        RangedOpts ro;
+        ro.geom = CONV_DOWN2;
+        ro.y_feeds_site = feeds_site;
+        if (range) ranged(x, w, free.first, free.second, ro);
+        else conv3(x, w, free.second, CONV_DOWN2);
+        x = Act{free.second, x.n, x.h / 2, x.w / 2, w.cout};
+    }
+    // Decoder.forward's last operators (norm_out, swish, conv_out) + denormalise + NCHW / uint8 store: one kernel, or (TailOut::fused = false, or a shape it does not take) three
+    void tail(const float* nw, const float* nb, const ConvW& co, const TailOut& to) {
+        const int denorm = to.out_mode != 0;
+        const float *mean = denorm ? to.mean : nullptr, *stdv = denorm ? to.stdv : nullptr;
+        float* of = to.out_mode == 2 ? nullptr : reinterpret_cast<float*>(to.out);
+        uint8_t* o8 = to.out_mode == 2 ? reinterpret_cast<uint8_t*>(to.out) : nullptr;
+        if (to.fused && vq_out_conv_supported(x.c, co.cout)) {   // norm_out + swish + conv_out + denormalise + layout in one kernel
+            gn_stats(x);
+            launch_vq_out_conv(x.p, stats, nw, nb, co.w, co.b, mean, stdv, denorm, of, o8, x.n, x.h, x.w, x.c, co.cout, s);
+            return;
+        }
+        conv3(gn(x, nw, nb, t, 1, planes), co, to.img, CONV_SAME, nullptr, false);  // [n, h w, cout]
+        launch_nhwc_to_nchw(to.img, of, x.n, x.h * x.w, co.cout, co.cout, mean, stdv, denorm, s, o8);
+    }
+    // Encoder.forward's last operators and quant_conv (1x1): x -> zq [n, lat_h lat_w, embed_dim]
+    void to_latents(const float* nw, const float* nb, const ConvW& conv_out, const ConvW& quant_conv) {
+        const Two free = others();
+        conv3(gn(x, nw, nb, t, 1, planes), conv_out, free.second, CONV_SAME, nullptr, false);   // [n, lat_h lat_w, z_channels]
+        RangedOpts one;
+        one.k = 1;
+        if (range) ranged(Act{free.second, x.n, x.h, x.w, conv_out.cout}, quant_conv, free.first, zq, one);
+        else conv1(free.second, (long)x.n * x.h * x.w, quant_conv, zq, nullptr);
+    }
+};
+
+// The workspace of a pass over n images (layout functions, arena.h): metered for the largest pass, carved per pass.  Allocation order and sizes are part of the measured
+// arena bytes and stay as they are.
+struct DecBufs { float* img = nullptr; };                    // pixel staging of the three-kernel tail [n, RH RW, 4]
+struct EncBufs { float *dots = nullptr, *zz = nullptr; };   // codebook products [n lat_h lat_w, n_embed] and row norms of the quantizer
+
+DecBufs dec_layout(Arena& a, Pass& p, const VqSizes& z, int embed_dim, int n) {
+    DecBufs d;
+    if (p.planes) p.part.buf = a.get<float>((size_t)z.per_img * n / 64 + 64);   // GroupNorm partials of one tensor: (pixels / 32) x (channels / 4) x 2
+    p.a = a.get<float>((size_t)z.per_img * n);
+    p.b = a.get<float>((size_t)z.per_img * n);
+    p.t = a.get<float>((size_t)z.per_img * n);
+    p.stats = a.get<float>((size_t)n * 64);
+    p.gn_ws = a.alloc(groupnorm_ws_bytes(n, z.RH * z.RW));
+    p.q = a.get<float>((size_t)n * z.attn_hwp * z.max_c);
+    p.k = a.get<float>((size_t)n * z.attn_hwp * z.max_c);
+    p.vT = a.get<float>((size_t)n * z.attn_hwp * z.max_c);
+    p.S = a.get<float>((size_t)n * z.attn_hwp * z.attn_hwp);
+    p.zq = a.get<float>((size_t)n * z.lat_h * z.lat_w * embed_dim);
+    d.img = a.get<float>((size_t)n * z.RH * z.RW * 4);
+    p.o = a.get<float>((size_t)z.per_img * n);
+    return d;
 }
 
-// Downsample (stage1/model.py:56-75): F.pad(x, (0,1,0,1)) + 3x3 convolution, stride 2, padding 0; x.h and x.w even.  The bottom / right zero padding is the gather's bounds test.
-void conv3_down(const Act& x, const ConvW& w, float* y, hipStream_t s) {
-    GemmArgs ga;
-    ga.mode = MODE_CONV3;
-    ga.A = x.p; ga.B = w.w; ga.C = y; ga.bias_n = w.b;
-    ga.M = x.n * (x.h / 2) * (x.w / 2); ga.N = w.cout; ga.K = 9 * w.cin;
-    ga.lda = w.cin; ga.ldb = 9 * w.cin; ga.ldc = w.cout;
-    ga.conv_h = x.h / 2; ga.conv_w = x.w / 2; ga.conv_cin = w.cin; ga.conv_up = 0;
-    ga.conv_hin = x.h; ga.conv_win = x.w; ga.conv_stride = 2; ga.conv_pad = 0;
-    launch_gemm(ga, s);
+// The encoder allocates NO partials buffer (p.part.buf stays null), so its convolutions never leave epilogue statistics and every GroupNorm runs the statistics pass:
+// an asymmetry with the decoder that is measured behaviour, kept as it is.
+EncBufs enc_layout(Arena& a, Pass& p, const VqSizes& z, int embed_dim, int n_embed, int n) {
+    EncBufs e;
+    const size_t lrows = (size_t)n * z.lat_h * z.lat_w;
+    p.a = a.get<float>((size_t)z.per_img * n);
+    p.b = a.get<float>((size_t)z.per_img * n);
+    p.t = a.get<float>((size_t)z.per_img * n);
+    p.o = a.get<float>((size_t)z.per_img * n);
+    p.stats = a.get<float>((size_t)n * 64);
+    p.gn_ws = a.alloc(groupnorm_ws_bytes(n, z.RH * z.RW));
+    p.q = a.get<float>((size_t)n * z.attn_hwp * z.max_c);
+    p.k = a.get<float>((size_t)n * z.attn_hwp * z.max_c);
+    p.vT = a.get<float>((size_t)n * z.attn_hwp * z.max_c);
+    p.S = a.get<float>((size_t)n * z.attn_hwp * z.attn_hwp);
+    e.dots = a.get<float>(lrows * n_embed);
+    p.zq = a.get<float>(lrows * embed_dim);
+    e.zz = a.get<float>(lrows);
+    return e;
 }
 
 // VectorQuantizer2.forward (stage1/quantize.py:271-312): ids = argmin_j (|z|^2 + |e_j|^2) - 2 z.e_j, exact fp32 products (the codebook is never split); ee = |e_j|^2
-void quantize(const float* z, const float* codebook, const float* ee, float* zz, float* dots, int64_t* ids, long rows, int n_e, int D, hipStream_t s) {
-    launch_row_sqnorm(z, zz, rows, D, s);
+struct Codebook { const float *e, *ee; int n_e, D; };
+void quantize(const float* z, long rows, const Codebook& cb, float* zz, float* dots, int64_t* ids, hipStream_t s) {
+    launch_row_sqnorm(z, zz, rows, cb.D, s);
     GemmArgs gd;
-    gd.A = z; gd.B = codebook; gd.C = dots;
-    gd.M = (int)rows; gd.N = n_e; gd.K = D; gd.lda = D; gd.ldb = D; gd.ldc = n_e;
+    gd.A = z; gd.B = cb.e; gd.C = dots;
+    gd.M = (int)rows; gd.N = cb.n_e; gd.K = cb.D; gd.lda = cb.D; gd.ldb = cb.D; gd.ldc = cb.n_e;
     launch_gemm(gd, s);
-    launch_vq_argmin(dots, zz, ee, ids, rows, n_e, s);
+    launch_vq_argmin(dots, zz, cb.ee, ids, rows, cb.n_e, s);
 }
 
-// Decoder.forward's last operators (norm_out, swish, conv_out) + denormalise + NCHW / uint8 store: one kernel, or (fused = false, or a shape it does not take) three.
-// out_mode as in vq_decode; mean / stdv are read for out_mode != 0 only; img: [n, h w, cout] scratch of the three-kernel form
-void out_tail(const Act& x, const float* nw, const float* nb, const ConvW& co, const float* mean, const float* stdv, int out_mode, bool fused, void* out, float* img, DecWs& ws,
-              bool planes, hipStream_t s) {
-    const int denorm = out_mode != 0;
-    float* of = out_mode == 2 ? nullptr : reinterpret_cast<float*>(out);
-    uint8_t* o8 = out_mode == 2 ? reinterpret_cast<uint8_t*>(out) : nullptr;
-    if (fused && vq_out_conv_supported(x.c, co.cout)) {   // norm_out + swish + conv_out + denormalise + layout in one kernel
-        gn_stats(x, ws, s);
-        launch_vq_out_conv(x.p, ws.stats, nw, nb, co.w, co.b, denorm ? mean : nullptr, denorm ? stdv : nullptr, denorm ? 1 : 0, of, o8, x.n, x.h, x.w, x.c, co.cout, s);
-        return;
+ConvW load_conv_in_padded(Ctx& c, const std::string& name, int cin_pad) {
+    const DevTensor& w = c.need(kPrefix + name + ".weight");
+    BG_REQUIRE(w.shape.size() == 4 && w.shape[2] == 3 && w.shape[3] == 3, "conv '%s' is not a 3x3 kernel", name.c_str());
+    ConvW cw;
+    cw.cout = (int)w.shape[0];
+    cw.cin = cin_pad;
+    cw.k = 3;
+    cw.b = c.pf(kPrefix + name + ".bias");
+    cw.w = reinterpret_cast<float*>(c.own((size_t)cw.cout * 9 * cin_pad * sizeof(float)));
+    launch_relayout_conv_weight_pad(w.f(), cw.w, cw.cout, (int)w.shape[1], cin_pad, 3, 3, 0);
+    c.split_weight(cw.w, (long)cw.cout * 9 * cin_pad);
+    return cw;
+}
+
+// Encoder + quantizer weights (vq_encode below)
+void vq_enc_finalize(Ctx& c) {
+    const auto& g = c.cfg;
+    BG_REQUIRE(g.vq_in_channels >= 1, "vq_in_channels must be set for the encoder");
+    c.enc_cin_pad = (int)round_up(g.vq_in_channels, 32);
+    c.enc_conv_in = load_conv_in_padded(c, "encoder.conv_in", c.enc_cin_pad);
+    c.down.clear();
+    c.down.resize(g.vq_num_levels);
+    int res = g.vq_resolution;
+    for (int lvl = 0; lvl < g.vq_num_levels; ++lvl) {
+        DownLevelW& d = c.down[lvl];
+        const std::string p = "encoder.down." + std::to_string(lvl) + ".";
+        for (int b = 0; b < g.vq_num_res_blocks; ++b) {
+            d.blocks.push_back(load_res(c, p + "block." + std::to_string(b) + "."));
+            if (res == g.vq_attn_resolution) d.attns.push_back(load_attn(c, p + "attn." + std::to_string(b) + "."));
+        }
+        d.has_down = lvl != g.vq_num_levels - 1;
+        if (d.has_down) {
+            d.down = load_conv(c, p + "downsample.conv", 3);
+            res /= 2;
+        }
     }
-    gn(x, nw, nb, ws.t, 1, ws, s, planes);
-    Act t{ws.t, x.n, x.h, x.w, x.c};
-    conv3(t, co, img, nullptr, 0, s, planes);  // [n, h w, cout]
-    launch_nhwc_to_nchw(img, of, x.n, x.h * x.w, co.cout, co.cout, denorm ? mean : nullptr, denorm ? stdv : nullptr, denorm ? 1 : 0, s, o8);
+    c.enc_mid1 = load_res(c, "encoder.mid.block_1.");
+    c.enc_mid_attn = load_attn(c, "encoder.mid.attn_1.");
+    c.enc_mid2 = load_res(c, "encoder.mid.block_2.");
+    c.enc_norm_out_w = c.pf(kPrefix + "encoder.norm_out.weight");
+    c.enc_norm_out_b = c.pf(kPrefix + "encoder.norm_out.bias");
+    c.enc_conv_out = load_conv(c, "encoder.conv_out", 3);
+    c.quant_conv = load_conv(c, "quant_conv", 1);
+    BG_REQUIRE(c.enc_conv_out.cout == g.vq_z_channels && c.quant_conv.cout == g.vq_embed_dim, "encoder output channels do not match z_channels / embed_dim (double_z must be False)");
+    c.codebook_sqnorm = reinterpret_cast<float*>(c.own((size_t)g.vq_n_embed * sizeof(float)));
+    launch_row_sqnorm(c.codebook, c.codebook_sqnorm, g.vq_n_embed, g.vq_embed_dim, 0);
+    c.vq_enc_shape = shape_of(g, true, c.enc_cin_pad, c.enc_mid1, c.enc_mid2);
+    for (int lvl = 0; lvl < g.vq_num_levels; ++lvl) shape_level(c.vq_enc_shape, lvl, c.down[lvl].blocks, !c.down[lvl].attns.empty(), c.down[lvl].has_down);
 }
 
 }  // namespace
 
-static void vq_enc_finalize(Ctx& c);
-
 void vq_finalize(Ctx& c) {
     const auto& g = c.cfg;
-    BG_REQUIRE(g.vq_num_levels >= 1 && g.vq_num_levels <= 8, "vq_num_levels out of range");
+    BG_REQUIRE(g.vq_num_levels >= 1 && g.vq_num_levels <= kVqMaxLevels, "vq_num_levels out of range");
     const DevTensor& cb = c.need(kPrefix + "quantize.embedding.weight");
     BG_REQUIRE(cb.shape.size() == 2 && cb.shape[0] == g.vq_n_embed && cb.shape[1] == g.vq_embed_dim, "codebook must be [n_embed, embed_dim]");
     c.codebook = cb.f();
@@ -304,156 +526,51 @@ void vq_finalize(Ctx& c) {
     c.denorm_std = reinterpret_cast<float*>(c.own(sizeof stdv));
     HIP_CHECK(hipMemcpy(c.denorm_mean, mean, sizeof mean, hipMemcpyHostToDevice));
     HIP_CHECK(hipMemcpy(c.denorm_std, stdv, sizeof stdv, hipMemcpyHostToDevice));
+    c.vq_dec_shape = shape_of(g, false, 0, c.mid1, c.mid2);
+    for (int lvl = 0; lvl < g.vq_num_levels; ++lvl) shape_level(c.vq_dec_shape, lvl, c.up[lvl].blocks, !c.up[lvl].attns.empty(), c.up[lvl].has_up);
 }
 
-// The decoder is fully convolutional (stage1/model.py:506-537): the latent grid is lat_h x lat_w (cam_latent_res, e.g. 16 x 16 or nuScenes' 14 x 25), the output
-// (lat_h << (levels-1)) x (lat_w << (levels-1)); which levels carry AttnBlocks is decided by ddconfig.resolution alone (curr_res == attn_resolutions, :466-480).
+// The decoder on a latent grid of lat_h x lat_w (sizes: vq_scan).
 // out_mode: 0 = raw fp32, 1 = denormalised fp32 in [0,1], 2 = denormalised uint8 round(x*255) (`out` then points to uint8).
 void vq_decode(Ctx& c, const int64_t* ids, const float* latents_nchw, int n_total, int lat_h, int lat_w, int out_mode, void* out, hipStream_t s) {
     BG_REQUIRE(c.has_vq, "this context holds no VQGAN decoder weights (decoder.* tensors were not loaded)");
     const auto& g = c.cfg;
-    const bool planes = g.precision == BEVGEN_PRECISION_F16X3;   // split-precision mode: GroupNorm writes (hi, lo) planes, convolutions read them by LDS-DMA
     BG_REQUIRE(lat_h >= 1 && lat_w >= 1, "vq_decode: latent grid %d x %d", lat_h, lat_w);
-    const int denorm = out_mode != 0;
+    BG_REQUIRE(out_mode == 0 || g.vq_out_ch == 3, "denormalize needs 3 output channels");
+    Pass proto;
+    proto.s = s;
+    proto.planes = g.precision == BEVGEN_PRECISION_F16X3;
+    const VqSizes z = vq_scan(c.vq_dec_shape, lat_h, lat_w);
+    const VqPasses cut = vq_pass_cut(n_total);
     const long lat_hw = (long)lat_h * lat_w;
-    const int RH = lat_h << (g.vq_num_levels - 1), RW = lat_w << (g.vq_num_levels - 1);
-    BG_REQUIRE(!denorm || g.vq_out_ch == 3, "denormalize needs 3 output channels");
-    // widest activation per image: max over levels of h*w * channels; most attention tokens over the levels that carry AttnBlocks
-    long per_img = 0, attn_hw = lat_hw;
-    int max_c = 0;
-    {
-        long hw = lat_hw;
-        for (int lvl = g.vq_num_levels - 1; lvl >= 0; --lvl) {
-            const int ch = g.vq_ch * g.vq_ch_mult[lvl];
-            const int ch_in = lvl == g.vq_num_levels - 1 ? ch : g.vq_ch * g.vq_ch_mult[lvl + 1];
-            per_img = std::max<long>(per_img, hw * std::max(ch, ch_in));
-            max_c = std::max(max_c, std::max(ch, ch_in));
-            if (!c.up[lvl].attns.empty()) attn_hw = std::max(attn_hw, hw);
-            if (lvl != 0) hw *= 4;
-        }
-    }
-    const long attn_hwp = round_up(attn_hw, 32);
-    // images per pass: the 16 x 16 stages only fill the chip (256 x 128 tiles on 256 CUs) from ~48 images; 148 -> 128 ms per 96 images vs 16, arena ~10 GB.  (Round 5: smaller
-    // passes whose full-resolution tensors would fit the 256 MB memory-side cache between conv -> statistics -> apply -> conv are slower throughout: 6 / 12 / 24 images per
-    // pass 11.96 / 9.14 / 7.96 ms per scene against 7.47, profiles/r05_ab_vq.txt)
-    const int chunk_max = 48;
-    const int attn_c = max_c;
-    const int chunk = std::min(n_total, chunk_max);
-    // the workspace of a pass over n images (a layout function, arena.h): metered for the largest pass, carved per pass
-    auto layout = [&](Arena& a, DecWs& ws, int n) {
-        if (planes) ws.part.buf = a.get<float>((size_t)per_img * n / 64 + 64);   // GroupNorm partials of one tensor: (pixels / 32) x (channels / 4) x 2
-        ws.a = a.get<float>((size_t)per_img * n);
-        ws.b = a.get<float>((size_t)per_img * n);
-        ws.t = a.get<float>((size_t)per_img * n);
-        ws.stats = a.get<float>((size_t)n * 64);
-        ws.gn_ws = a.alloc(groupnorm_ws_bytes(n, RH * RW));
-        ws.q = a.get<float>((size_t)n * attn_hwp * attn_c);
-        ws.k = a.get<float>((size_t)n * attn_hwp * attn_c);
-        ws.vT = a.get<float>((size_t)n * attn_hwp * attn_c);
-        ws.S = a.get<float>((size_t)n * attn_hwp * attn_hwp);
-        ws.zq = a.get<float>((size_t)n * lat_hw * g.vq_embed_dim);
-        ws.img = a.get<float>((size_t)n * RH * RW * 4);
-        ws.o = a.get<float>((size_t)per_img * n);
-    };
-    c.arena.reserve(Arena::measure([&](Arena& a) { DecWs ws; layout(a, ws, chunk); }));
-    RangeSites sites;
-    c.vq_range_used = 0;
-    if (planes && g.vq_range) {
-        int per_pass = 1;   // conv_in
-        auto count = [&](const ResBlockW& r) { per_pass += r.has_nin ? 1 : 0; };
-        count(c.mid1); count(c.mid2);
-        for (const UpLevelW& u : c.up) {
-            for (const ResBlockW& r : u.blocks) count(r);
-            per_pass += u.has_up ? 1 : 0;
-        }
-        sites.cap = per_pass * cdiv(n_total, chunk);
-        c.vq_range_slots.reserve((size_t)sites.cap * 8);
-        sites.exps = reinterpret_cast<int*>(c.vq_range_slots.base);
-        sites.amax = reinterpret_cast<unsigned*>(sites.exps + sites.cap);
-        HIP_CHECK(hipMemsetAsync(sites.exps, 0, (size_t)sites.cap * 8, s));
-    }
-    for (int i0 = 0; i0 < n_total; i0 += chunk) {
-        const int n = std::min(chunk, n_total - i0);
+    c.arena.reserve(Arena::measure([&](Arena& a) { Pass p = proto; dec_layout(a, p, z, g.vq_embed_dim, cut.chunk); }));
+    RangeSites sites = sites_reserve(c, proto.planes && g.vq_range ? vq_sites_per_pass(c.vq_dec_shape) * cut.passes : 0, s);
+    if (sites.cap) proto.range = &sites;
+    for (int i0 = 0; i0 < n_total; i0 += cut.chunk) {
+        const int n = std::min(cut.chunk, n_total - i0);
         c.arena.reset();
-        DecWs ws;
-        if (sites.cap) ws.range = &sites;
-        layout(c.arena, ws, n);
-        float *zq = ws.zq, *img = ws.img;
-
-        const long lrows = (long)n * lat_hw;
-        if (ids) launch_codebook_gather(ids + (long)i0 * lat_hw, c.codebook, zq, (int)lrows, g.vq_embed_dim, g.vq_n_embed, s);
-        else launch_nchw_to_nhwc(latents_nchw + (long)i0 * g.vq_embed_dim * lat_hw, zq, n, (int)lat_hw, g.vq_embed_dim, s);
-        conv1(zq, lrows, c.post_quant, ws.t, nullptr, s);                       // post_quant_conv
-        Act x{ws.t, n, lat_h, lat_w, g.vq_z_channels};
-        if (ws.range) conv_ranged(x, c.conv_in, 3, 0, ws.b, ws.a, ws, s);
-        else conv3(x, c.conv_in, ws.a, nullptr, 0, s, false, &ws.part);          // conv_in
-        x = Act{ws.a, n, lat_h, lat_w, c.conv_in.cout};
-        // three rotating activation buffers (input / scratch / output of a block) + ws.t for the normalised tensor
-        float* o = ws.o;
-        auto res_step = [&](const ResBlockW& r) {
-            // buffers: x.p in {a,b,o}; pick scratch and y as the two others
-            float* bufs[3] = {ws.a, ws.b, o};
-            float* scratch = nullptr; float* y = nullptr;
-            for (float* b : bufs) { if (b != x.p) { if (!scratch) scratch = b; else y = b; } }
-            resblock(r, x, y, scratch, ws, s, planes);
-        };
-        auto attn_step = [&](const AttnBlockW& ab) {
-            float* bufs[3] = {ws.a, ws.b, o};
-            float* y = nullptr;
-            for (float* b : bufs) if (b != x.p) { y = b; break; }
-            attnblock(ab, x, y, ws, s);
-        };
-        res_step(c.mid1);
-        attn_step(c.mid_attn);
-        res_step(c.mid2);
+        Pass p = proto;
+        const DecBufs d = dec_layout(c.arena, p, z, g.vq_embed_dim, n);
+        if (ids) launch_codebook_gather(ids + (long)i0 * lat_hw, c.codebook, p.zq, (int)(n * lat_hw), g.vq_embed_dim, g.vq_n_embed, s);
+        else launch_nchw_to_nhwc(latents_nchw + (long)i0 * g.vq_embed_dim * lat_hw, p.zq, n, (int)lat_hw, g.vq_embed_dim, s);
+        p.conv1(p.zq, n * lat_hw, c.post_quant, p.t, nullptr);                       // post_quant_conv
+        p.conv_in(Act{p.t, n, lat_h, lat_w, g.vq_z_channels}, c.conv_in);
+        p.res(c.mid1);
+        p.attn(c.mid_attn);
+        p.res(c.mid2);
         for (int lvl = g.vq_num_levels - 1; lvl >= 0; --lvl) {
             const UpLevelW& u = c.up[lvl];
             for (size_t b = 0; b < u.blocks.size(); ++b) {
-                res_step(u.blocks[b]);
-                if (!u.attns.empty()) attn_step(u.attns[b]);
+                p.res(u.blocks[b]);
+                if (!u.attns.empty()) p.attn(u.attns[b]);
             }
-            if (u.has_up) {  // nearest 2x + 3x3 conv, fused
-                float* bufs[3] = {ws.a, ws.b, o};
-                float* y = nullptr;
-                for (float* b : bufs) if (b != x.p) { y = b; break; }
-                // The upsample convolution reads the block output directly (no GroupNorm in front of it, s1model:49-53): in split-precision mode the tensor is first
-                // re-laid out as (hi, lo) planes (one elementwise pass over the SMALL pre-upsample tensor) so that the 4x larger convolution runs on the LDS-DMA kernel
-                // instead of the register-staged one ($BEVGEN_VQ_UP_PLANES=0: as in rounds 2-4)
-                static const int up_planes = getenv("BEVGEN_VQ_UP_PLANES") ? atoi(getenv("BEVGEN_VQ_UP_PLANES")) : 1;
-                const int q4 = x.c >> 2;
-                if (planes && up_planes && (q4 & (q4 - 1)) == 0 && x.c % 32 == 0) {
-                    note_write(&ws.part, ws.t);
-                    Act xp{ws.t, x.n, x.h, x.w, x.c};
-                    if (ws.range) {
-                        // x 2^-e as planes, the convolution without its bias and without the epilogue statistics (they would describe the unscaled sums), then
-                        // y = 2^e y + b in one pass that also leaves those statistics where the epilogue would have
-                        const int* e = range_exponent(ws, x, s);
-                        launch_range_split(x.p, ws.t, (long)x.n * x.h * x.w, x.c, e, s);
-                        ConvW wb = u.up;
-                        wb.b = nullptr;
-                        conv3(xp, wb, y, nullptr, 1, s, true, nullptr);
-                        note_write(&ws.part, y);
-                        const bool part = gn_epilogue() && ws.part.buf && groupnorm_partials_supported(4 * x.h * x.w, u.up.cout);
-                        launch_range_unscale(y, u.up.b, nullptr, 4L * x.n * x.h * x.w, u.up.cout, e, part ? ws.part.buf : nullptr, s);
-                        if (part) ws.part.of = y;
-                    } else {
-                        launch_to_planes(x.p, ws.t, x.n, x.h * x.w, x.c, s);
-                        conv3(xp, u.up, y, nullptr, 1, s, true, &ws.part);
-                    }
-                } else if (ws.range) {
-                    conv_ranged(x, u.up, 3, 1, ws.t, y, ws, s);
-                } else {
-                    conv3(x, u.up, y, nullptr, 1, s, false, &ws.part);
-                }
-                x = Act{y, x.n, x.h * 2, x.w * 2, u.up.cout};
-            }
+            if (u.has_up) p.up(u.up);
         }
-        const long o_off = (long)i0 * g.vq_out_ch * RH * RW;
-        static const bool tail_off = getenv("BEVGEN_VQ_TAIL") && atoi(getenv("BEVGEN_VQ_TAIL")) == 0;   // (A/B switch: 0 = the three-kernel tail)
+        const long o_off = (long)i0 * g.vq_out_ch * z.RH * z.RW;
         void* o_ptr = out_mode == 2 ? static_cast<void*>(reinterpret_cast<uint8_t*>(out) + o_off) : static_cast<void*>(reinterpret_cast<float*>(out) + o_off);
-        out_tail(x, c.norm_out_w, c.norm_out_b, c.conv_out, c.denorm_mean, c.denorm_std, out_mode, !tail_off, o_ptr, img, ws, planes, s);
+        p.tail(c.norm_out_w, c.norm_out_b, c.conv_out, TailOut{o_ptr, out_mode, c.denorm_mean, c.denorm_std, d.img, vq_switches().tail});
     }
-    c.vq_range_used = sites.used;
+    sites_done(c, sites);
 }
 
 // exponents of the most recent decode / encode call (host array); synchronises
@@ -470,172 +587,48 @@ int vq_range_exponents(Ctx& c, int32_t* out, int cap) {
 //   VQModel.encode         stage1/vqgan.py:84-116    (geometric_embedding=False in the released configs)
 //   VectorQuantizer2.forward  stage1/quantize.py:271-312
 // =====================================================================================================
-static ConvW load_conv_in_padded(Ctx& c, const std::string& name, int cin_pad) {
-    const DevTensor& w = c.need(kPrefix + name + ".weight");
-    BG_REQUIRE(w.shape.size() == 4 && w.shape[2] == 3 && w.shape[3] == 3, "conv '%s' is not a 3x3 kernel", name.c_str());
-    ConvW cw;
-    cw.cout = (int)w.shape[0];
-    cw.cin = cin_pad;
-    cw.k = 3;
-    cw.b = c.pf(kPrefix + name + ".bias");
-    cw.w = reinterpret_cast<float*>(c.own((size_t)cw.cout * 9 * cin_pad * sizeof(float)));
-    launch_relayout_conv_weight_pad(w.f(), cw.w, cw.cout, (int)w.shape[1], cin_pad, 3, 3, 0);
-    c.split_weight(cw.w, (long)cw.cout * 9 * cin_pad);
-    return cw;
-}
-
-static void vq_enc_finalize(Ctx& c) {
-    const auto& g = c.cfg;
-    BG_REQUIRE(g.vq_in_channels >= 1, "vq_in_channels must be set for the encoder");
-    c.enc_cin_pad = (int)round_up(g.vq_in_channels, 32);
-    c.enc_conv_in = load_conv_in_padded(c, "encoder.conv_in", c.enc_cin_pad);
-    c.down.clear();
-    c.down.resize(g.vq_num_levels);
-    int res = g.vq_resolution;
-    for (int lvl = 0; lvl < g.vq_num_levels; ++lvl) {
-        DownLevelW& d = c.down[lvl];
-        const std::string p = "encoder.down." + std::to_string(lvl) + ".";
-        for (int b = 0; b < g.vq_num_res_blocks; ++b) {
-            d.blocks.push_back(load_res(c, p + "block." + std::to_string(b) + "."));
-            if (res == g.vq_attn_resolution) d.attns.push_back(load_attn(c, p + "attn." + std::to_string(b) + "."));
-        }
-        d.has_down = lvl != g.vq_num_levels - 1;
-        if (d.has_down) {
-            d.down = load_conv(c, p + "downsample.conv", 3);
-            res /= 2;
-        }
-    }
-    c.enc_mid1 = load_res(c, "encoder.mid.block_1.");
-    c.enc_mid_attn = load_attn(c, "encoder.mid.attn_1.");
-    c.enc_mid2 = load_res(c, "encoder.mid.block_2.");
-    c.enc_norm_out_w = c.pf(kPrefix + "encoder.norm_out.weight");
-    c.enc_norm_out_b = c.pf(kPrefix + "encoder.norm_out.bias");
-    c.enc_conv_out = load_conv(c, "encoder.conv_out", 3);
-    c.quant_conv = load_conv(c, "quant_conv", 1);
-    BG_REQUIRE(c.enc_conv_out.cout == g.vq_z_channels && c.quant_conv.cout == g.vq_embed_dim, "encoder output channels do not match z_channels / embed_dim (double_z must be False)");
-    c.codebook_sqnorm = reinterpret_cast<float*>(c.own((size_t)g.vq_n_embed * sizeof(float)));
-    launch_row_sqnorm(c.codebook, c.codebook_sqnorm, g.vq_n_embed, g.vq_embed_dim, 0);
-}
-
 // x [n, in_channels, RH, RW] with RH, RW multiples of 2^(levels-1) (fully convolutional: 256 x 256 or nuScenes' 224 x 400) -> ids [n, (RH >> (levels-1)) * (RW >> (levels-1))]
 void vq_encode(Ctx& c, const float* x_nchw, int n_total, int RH, int RW, int64_t* ids, hipStream_t s) {
     BG_REQUIRE(c.has_vq_enc, "this context holds no VQGAN encoder weights (encoder.* tensors were not loaded)");
     const auto& g = c.cfg;
-    const bool planes = g.precision == BEVGEN_PRECISION_F16X3;   // split-precision mode: GroupNorm writes (hi, lo) planes, convolutions read them by LDS-DMA
     const int f = 1 << (g.vq_num_levels - 1);
     BG_REQUIRE(RH >= f && RW >= f && RH % f == 0 && RW % f == 0, "vq_encode: image %d x %d is not a multiple of the downsampling factor %d", RH, RW, f);
-    const int lat_h = RH / f, lat_w = RW / f;
-    const long lat_hw = (long)lat_h * lat_w;
-    long per_img = (long)RH * RW * std::max(c.enc_cin_pad, g.vq_ch), attn_hw = lat_hw;
-    int max_c = g.vq_ch;
-    {
-        long hw = (long)RH * RW;
-        for (int lvl = 0; lvl < g.vq_num_levels; ++lvl) {
-            const int ch = g.vq_ch * g.vq_ch_mult[lvl];
-            per_img = std::max<long>(per_img, hw * ch);
-            max_c = std::max(max_c, ch);
-            if (!c.down[lvl].attns.empty()) attn_hw = std::max(attn_hw, hw);
-            if (lvl != g.vq_num_levels - 1) hw /= 4;
-        }
-    }
-    const int chunk = std::min(n_total, 48);
-    const long attn_hwp = round_up(attn_hw, 32);
-    // the workspace of a pass over n images (a layout function, arena.h): metered for the largest pass, carved per pass
-    auto layout = [&](Arena& a, DecWs& ws, int n) {
-        ws.a = a.get<float>((size_t)per_img * n);
-        ws.b = a.get<float>((size_t)per_img * n);
-        ws.t = a.get<float>((size_t)per_img * n);
-        ws.o = a.get<float>((size_t)per_img * n);
-        ws.stats = a.get<float>((size_t)n * 64);
-        ws.gn_ws = a.alloc(groupnorm_ws_bytes(n, RH * RW));
-        ws.q = a.get<float>((size_t)n * attn_hwp * max_c);
-        ws.k = a.get<float>((size_t)n * attn_hwp * max_c);
-        ws.vT = a.get<float>((size_t)n * attn_hwp * max_c);
-        ws.S = a.get<float>((size_t)n * attn_hwp * attn_hwp);
-        ws.dots = a.get<float>((size_t)n * lat_hw * g.vq_n_embed);
-        ws.zq = a.get<float>((size_t)n * lat_hw * g.vq_embed_dim);
-        ws.zz = a.get<float>((size_t)n * lat_hw);
-    };
-    c.arena.reserve(Arena::measure([&](Arena& a) { DecWs ws; layout(a, ws, chunk); }));
-    RangeSites sites;
-    c.vq_range_used = 0;
-    if (planes && g.vq_range) {
-        int per_pass = 2;   // conv_in, quant_conv
-        auto count = [&](const ResBlockW& r) { per_pass += r.has_nin ? 1 : 0; };
-        for (const DownLevelW& d : c.down) {
-            for (const ResBlockW& r : d.blocks) count(r);
-            per_pass += d.has_down ? 1 : 0;
-        }
-        count(c.enc_mid1); count(c.enc_mid2);
-        sites.cap = per_pass * cdiv(n_total, chunk);
-        c.vq_range_slots.reserve((size_t)sites.cap * 8);
-        sites.exps = reinterpret_cast<int*>(c.vq_range_slots.base);
-        sites.amax = reinterpret_cast<unsigned*>(sites.exps + sites.cap);
-        HIP_CHECK(hipMemsetAsync(sites.exps, 0, (size_t)sites.cap * 8, s));
-    }
-    for (int i0 = 0; i0 < n_total; i0 += chunk) {
-        const int n = std::min(chunk, n_total - i0);
+    Pass proto;
+    proto.s = s;
+    proto.planes = g.precision == BEVGEN_PRECISION_F16X3;
+    proto.encoder = true;
+    const VqSizes z = vq_scan(c.vq_enc_shape, RH, RW);
+    const VqPasses cut = vq_pass_cut(n_total);
+    const long lat_hw = (long)z.lat_h * z.lat_w;
+    c.arena.reserve(Arena::measure([&](Arena& a) { Pass p = proto; enc_layout(a, p, z, g.vq_embed_dim, g.vq_n_embed, cut.chunk); }));
+    RangeSites sites = sites_reserve(c, proto.planes && g.vq_range ? vq_sites_per_pass(c.vq_enc_shape) * cut.passes : 0, s);
+    if (sites.cap) proto.range = &sites;
+    for (int i0 = 0; i0 < n_total; i0 += cut.chunk) {
+        const int n = std::min(cut.chunk, n_total - i0);
         c.arena.reset();
-        DecWs ws;
-        if (sites.cap) ws.range = &sites;
-        layout(c.arena, ws, n);
-        const long lrows = (long)n * lat_hw;
-        float *o = ws.o, *dots = ws.dots, *zq = ws.zq, *zz = ws.zz;
-
-        const float* x_in = x_nchw + (long)i0 * g.vq_in_channels * RH * RW;
-        Act x{ws.t, n, RH, RW, c.enc_cin_pad};
-        if (ws.range) {   // the layout change also leaves the image's exponent: conv_in's site needs no pass of its own over the padded tensor
-            if (enc_fuse()) {
-                const NextSlot nx = range_next_slot(ws, ws.t);
-                launch_nchw_to_nhwc_pad_amax(x_in, ws.t, n, RH * RW, g.vq_in_channels, c.enc_cin_pad, nx.amax, nx.e, s);
-            } else {
-                launch_nchw_to_nhwc_pad(x_in, ws.t, n, RH * RW, g.vq_in_channels, c.enc_cin_pad, s);
-            }
-            conv_ranged(x, c.enc_conv_in, 3, 0, ws.b, ws.a, ws, s);
-        } else {
-            launch_nchw_to_nhwc_pad(x_in, ws.t, n, RH * RW, g.vq_in_channels, c.enc_cin_pad, s);
-            conv3(x, c.enc_conv_in, ws.a, nullptr, 0, s);
-        }
-        x = Act{ws.a, n, RH, RW, c.enc_conv_in.cout};
-        auto pick2 = [&](float*& scratch, float*& y) {
-            float* bufs[3] = {ws.a, ws.b, o};
-            scratch = nullptr; y = nullptr;
-            for (float* b : bufs) { if (b != x.p) { if (!scratch) scratch = b; else y = b; } }
-        };
-        auto res_step = [&](const ResBlockW& r) { float *sc, *y; pick2(sc, y); resblock(r, x, y, sc, ws, s, planes); };
-        auto attn_step = [&](const AttnBlockW& ab) { float *sc, *y; pick2(sc, y); attnblock(ab, x, y, ws, s); };
+        Pass p = proto;
+        const EncBufs e = enc_layout(c.arena, p, z, g.vq_embed_dim, g.vq_n_embed, n);
+        p.conv_in(p.load_image(x_nchw + (long)i0 * g.vq_in_channels * RH * RW, n, RH, RW, g.vq_in_channels, c.enc_cin_pad), c.enc_conv_in);
         for (int lvl = 0; lvl < g.vq_num_levels; ++lvl) {
             const DownLevelW& d = c.down[lvl];
             for (size_t b = 0; b < d.blocks.size(); ++b) {
-                res_step(d.blocks[b]);
-                if (!d.attns.empty()) attn_step(d.attns[b]);
+                p.res(d.blocks[b]);
+                if (!d.attns.empty()) p.attn(d.attns[b]);
             }
-            if (d.has_down) {  // F.pad(x, (0,1,0,1)) + conv 3x3 stride 2 padding 0
-                float *sc, *y; pick2(sc, y);
-                // (its output is the next level's residual stream: where that level opens with a nin_shortcut, that site's operand)
-                const bool feeds_nin = !c.down[lvl + 1].blocks.empty() && c.down[lvl + 1].blocks[0].has_nin;
-                if (ws.range) conv_ranged(x, d.down, 3, 0, sc, y, ws, s, 1, feeds_nin);
-                else conv3_down(x, d.down, y, s);
-                x = Act{y, x.n, x.h / 2, x.w / 2, d.down.cout};
-            }
+            if (d.has_down) p.down(d.down, vq_feeds_nin(c.vq_enc_shape, lvl));
         }
-        res_step(c.enc_mid1);
-        attn_step(c.enc_mid_attn);
-        res_step(c.enc_mid2);
-        gn(x, c.enc_norm_out_w, c.enc_norm_out_b, ws.t, 1, ws, s, planes);
-        Act t{ws.t, x.n, x.h, x.w, x.c};
-        float *sc, *y; pick2(sc, y);
-        conv3(t, c.enc_conv_out, y, nullptr, 0, s, planes);                     // [n, lat*lat, z_channels]
-        if (ws.range) conv_ranged(Act{y, x.n, x.h, x.w, g.vq_z_channels}, c.quant_conv, 1, 0, sc, zq, ws, s);
-        else conv1(y, lrows, c.quant_conv, zq, nullptr, s);             // quant_conv (1x1)
-        quantize(zq, c.codebook, c.codebook_sqnorm, zz, dots, ids + (long)i0 * lat_hw, lrows, g.vq_n_embed, g.vq_embed_dim, s);
+        p.res(c.enc_mid1);
+        p.attn(c.enc_mid_attn);
+        p.res(c.enc_mid2);
+        p.to_latents(c.enc_norm_out_w, c.enc_norm_out_b, c.enc_conv_out, c.quant_conv);
+        quantize(p.zq, n * lat_hw, Codebook{c.codebook, c.codebook_sqnorm, g.vq_n_embed, g.vq_embed_dim}, e.zz, e.dots, ids + (long)i0 * lat_hw, s);
     }
-    c.vq_range_used = sites.used;
+    sites_done(c, sites);
 }
 
 // =====================================================================================================
-// Operator entries (bevgen_op_* in api.cpp): the pieces above on caller-supplied device tensors, at shapes of their own.  They forward to the launchers / helpers the model
-// path uses and add no arithmetic.  Weights arrive as the checkpoint stores them ([Cout][Cin][kh][kw]) and are prepared the way load_conv prepares them, into the arena.
+// Operator entries (bevgen_op_* in api.cpp): the pieces above on caller-supplied device tensors, at shapes of their own.  They forward to the launchers / Pass methods the
+// model path uses and add no arithmetic.  Weights arrive as the checkpoint stores them ([Cout][Cin][kh][kw]) and are prepared the way load_conv prepares them, into the arena.
 // =====================================================================================================
 namespace {
 
@@ -674,6 +667,15 @@ struct OpWeights {
     }
 };
 
+// an operator's pass: the caller's input is the current activation
+Pass op_pass(const Ctx& c, hipStream_t s, const float* x, int n, int h, int w, int C) {
+    Pass p;
+    p.s = s;
+    p.planes = c.cfg.precision == BEVGEN_PRECISION_F16X3;
+    p.x = Act{const_cast<float*>(x), n, h, w, C};
+    return p;
+}
+
 }  // namespace
 
 void vq_op_conv3x3_down(Ctx& c, const float* x, const float* w, const float* bias, float* y, int n, int H, int W, int Cin, int Cout, hipStream_t s) {
@@ -683,11 +685,12 @@ void vq_op_conv3x3_down(Ctx& c, const float* x, const float* w, const float* bia
     c.arena.carve([&](Arena& a) { wb = OpWeights::take(c, a, Cout, Cin, 3); });
     OpWeights ow(c, s);
     const ConvW cw = ow.conv(wb, w, bias, Cout, Cin, 3);
-    conv3_down(Act{const_cast<float*>(x), n, H, W, Cin}, cw, y, s);
+    Pass p = op_pass(c, s, x, n, H, W, Cin);
+    p.conv3(p.x, cw, y, CONV_DOWN2);
 }
 
-// one range-safe site as vq_decode / vq_encode run it (conv_ranged); kind 0: 1x1, 1: 3x3, 2: the Downsample.  kind 2 ends in the fused pass (y_feeds_site) as a
-// downsample in front of a nin_shortcut does; the exponent that pass leaves for y stays in the arena.
+// one range-safe site as vq_decode / vq_encode run it (Pass::ranged); kind 0: 1x1, 1: 3x3, 2: the Downsample.  kind 2 ends in the fused pass (y_feeds_site) as a
+// downsample in front of a nin_shortcut does; the exponent that pass leaves for y stays in the arena.  Two slots, of which kinds 0 and 1 use one.
 void vq_op_conv_ranged(Ctx& c, const float* x, const float* w, const float* bias, int kind, float* y, int32_t* d_exp, int n, int H, int W, int Cin, int Cout, hipStream_t s) {
     BG_REQUIRE(c.cfg.precision == BEVGEN_PRECISION_F16X3, "op_conv_ranged: the range-safe sites belong to the split-precision mode (precision = f16x3)");
     BG_REQUIRE(kind >= 0 && kind <= 2, "op_conv_ranged: kind %d (0 = 1x1, 1 = 3x3, 2 = downsample)", kind);
@@ -708,9 +711,12 @@ void vq_op_conv_ranged(Ctx& c, const float* x, const float* w, const float* bias
     HIP_CHECK(hipMemsetAsync(sites.exps, 0, (size_t)sites.cap * 8, s));
     OpWeights ow(c, s);
     const ConvW cw = ow.conv(wb, w, bias, Cout, Cin, k);
-    DecWs ws{};
-    ws.range = &sites;
-    conv_ranged(Act{const_cast<float*>(x), n, H, W, Cin}, cw, k, 0, tmp, y, ws, s, kind == 2, kind == 2);
+    Pass p = op_pass(c, s, x, n, H, W, Cin);
+    p.range = &sites;
+    RangedOpts ro;
+    ro.k = k;
+    if (kind == 2) { ro.geom = CONV_DOWN2; ro.y_feeds_site = true; }
+    p.ranged(p.x, cw, tmp, y, ro);
     HIP_CHECK(hipMemcpyAsync(d_exp, sites.exps, sizeof(int32_t), hipMemcpyDeviceToDevice, s));
 }
 
@@ -722,28 +728,28 @@ void vq_op_attn_block(Ctx& c, const float* x, const float* norm_w, const float* 
     const size_t f = sizeof(float);
     const size_t qb = (size_t)n * hwp * C * f, sb = (size_t)n * hwp * hwp * f;
     OpWeights::Buf wb[4];
-    DecWs ws{};
+    Pass p = op_pass(c, s, x, n, h, w, C);
+    p.a = y;   // the rotation's one free buffer: the caller's output
     c.arena.carve([&](Arena& ar) {
         for (OpWeights::Buf& b : wb) b = OpWeights::take(c, ar, C, C, 1);
-        ws.t = ar.get<float>((size_t)n * hw * C);
-        ws.stats = ar.get<float>((size_t)n * 64);
-        ws.gn_ws = ar.alloc(groupnorm_ws_bytes(n, (int)hw));
-        ws.q = ar.get<float>(qb / f);
-        ws.k = ar.get<float>(qb / f);
-        ws.vT = ar.get<float>(qb / f);
-        ws.S = ar.get<float>(sb / f);
+        p.t = ar.get<float>((size_t)n * hw * C);
+        p.stats = ar.get<float>((size_t)n * 64);
+        p.gn_ws = ar.alloc(groupnorm_ws_bytes(n, (int)hw));
+        p.q = ar.get<float>(qb / f);
+        p.k = ar.get<float>(qb / f);
+        p.vT = ar.get<float>(qb / f);
+        p.S = ar.get<float>(sb / f);
     });
     OpWeights ow(c, s);
     AttnBlockW a;
     a.nw = norm_w; a.nb = norm_b; a.c = C;
     a.q = ow.conv(wb[0], wq, bq, C, C, 1); a.k = ow.conv(wb[1], wk, bk, C, C, 1); a.v = ow.conv(wb[2], wv, bv, C, C, 1); a.proj = ow.conv(wb[3], wp, bp, C, C, 1);
     // the model's workspace holds whatever the previous kernels left there: NaN bit patterns here, so that a pad column that is read without having been written shows
-    HIP_CHECK(hipMemsetAsync(ws.q, 0xFF, qb, s));
-    HIP_CHECK(hipMemsetAsync(ws.k, 0xFF, qb, s));
-    HIP_CHECK(hipMemsetAsync(ws.vT, 0xFF, qb, s));
-    HIP_CHECK(hipMemsetAsync(ws.S, 0xFF, sb, s));
-    Act xa{const_cast<float*>(x), n, h, w, C};
-    attnblock(a, xa, y, ws, s);
+    HIP_CHECK(hipMemsetAsync(p.q, 0xFF, qb, s));
+    HIP_CHECK(hipMemsetAsync(p.k, 0xFF, qb, s));
+    HIP_CHECK(hipMemsetAsync(p.vT, 0xFF, qb, s));
+    HIP_CHECK(hipMemsetAsync(p.S, 0xFF, sb, s));
+    p.attn(a);
 }
 
 void vq_op_out_tail(Ctx& c, const float* x, const float* norm_w, const float* norm_b, const float* w, const float* bias, const float* mean, const float* stdv, int out_mode,
@@ -751,20 +757,20 @@ void vq_op_out_tail(Ctx& c, const float* x, const float* norm_w, const float* no
     const int cout = 3;
     BG_REQUIRE(n >= 1 && H >= 1 && W >= 1 && C >= 32 && C % 32 == 0 && C <= 1024, "op_vq_out_tail: C=%d must be a multiple of 32 (at most 1024)", C);
     BG_REQUIRE(out_mode >= 0 && out_mode <= 2 && (out_mode == 0 || (mean && stdv)), "op_vq_out_tail: out_mode 0 / 1 / 2; 1 and 2 need mean and std");
-    const bool planes = c.cfg.precision == BEVGEN_PRECISION_F16X3;
     const long hw = (long)H * W;
     OpWeights::Buf wb;
-    DecWs ws{};
+    Pass p = op_pass(c, s, x, n, H, W, C);
+    float* img;
     c.arena.carve([&](Arena& a) {
         wb = OpWeights::take(c, a, cout, C, 3);
-        ws.t = a.get<float>((size_t)n * hw * C);
-        ws.stats = a.get<float>((size_t)n * 64);
-        ws.gn_ws = a.alloc(groupnorm_ws_bytes(n, (int)hw));
-        ws.img = a.get<float>((size_t)n * hw * 4);
+        p.t = a.get<float>((size_t)n * hw * C);
+        p.stats = a.get<float>((size_t)n * 64);
+        p.gn_ws = a.alloc(groupnorm_ws_bytes(n, (int)hw));
+        img = a.get<float>((size_t)n * hw * 4);
     });
     OpWeights ow(c, s);
     const ConvW co = ow.conv(wb, w, bias, cout, C, 3);
-    out_tail(Act{const_cast<float*>(x), n, H, W, C}, norm_w, norm_b, co, mean, stdv, out_mode, three_kernels == 0, out, ws.img, ws, planes, s);
+    p.tail(norm_w, norm_b, co, TailOut{out, out_mode, mean, stdv, img, three_kernels == 0});
 }
 
 void vq_op_quantize(Ctx& c, const float* z, const float* codebook, int64_t* ids, float* zz_out, float* ee_out, long rows, int n_e, int D, hipStream_t s) {
@@ -776,7 +782,7 @@ void vq_op_quantize(Ctx& c, const float* z, const float* codebook, int64_t* ids,
         ee = a.get<float>((size_t)n_e);
     });
     launch_row_sqnorm(codebook, ee, n_e, D, s);   // (the model: once, at finalize)
-    quantize(z, codebook, ee, zz, dots, ids, rows, n_e, D, s);
+    quantize(z, rows, Codebook{codebook, ee, n_e, D}, zz, dots, ids, s);
     if (zz_out) HIP_CHECK(hipMemcpyAsync(zz_out, zz, (size_t)rows * sizeof(float), hipMemcpyDeviceToDevice, s));
     if (ee_out) HIP_CHECK(hipMemcpyAsync(ee_out, ee, (size_t)n_e * sizeof(float), hipMemcpyDeviceToDevice, s));
 }
@@ -784,7 +790,7 @@ void vq_op_quantize(Ctx& c, const float* z, const float* codebook, int64_t* ids,
 void vq_op_conv3x3_gn_stats(Ctx& c, const float* x, const float* w, const float* bias, int range_route, float* y, float* part, float* stats, int n, int H, int W, int Cin,
                             int Cout, hipStream_t s) {
     BG_REQUIRE(c.cfg.precision == BEVGEN_PRECISION_F16X3, "op_conv3x3_gn_stats: the convolution epilogue that leaves GroupNorm partials belongs to the split-precision mode (precision = f16x3)");
-    BG_REQUIRE(gn_epilogue(), "op_conv3x3_gn_stats: the epilogue statistics are switched off (BEVGEN_GN_EPILOGUE=0)");
+    BG_REQUIRE(vq_switches().gn_epilogue, "op_conv3x3_gn_stats: the epilogue statistics are switched off (BEVGEN_GN_EPILOGUE=0)");
     const int hw = H * W, q4 = Cin >> 2;
     BG_REQUIRE(n >= 1 && H >= 1 && W >= 1 && Cin >= 32 && Cin % 32 == 0 && (q4 & (q4 - 1)) == 0 && bias, "op_conv3x3_gn_stats: needs a bias and Cin / 4 a power of two >= 8 (Cin=%d)", Cin);
     BG_REQUIRE(groupnorm_partials_supported(hw, Cout), "groupnorm from partials: unsupported shape hw=%d C=%d", hw, Cout);
@@ -797,22 +803,19 @@ void vq_op_conv3x3_gn_stats(Ctx& c, const float* x, const float* w, const float*
         e = range_route ? a.get<int>(1) : nullptr;
     });
     OpWeights ow(c, s);
-    ConvW cw = ow.conv(wbuf, w, bias, Cout, Cin, 3);
-    Act xp{planes, n, H, W, Cin};
-    if (range_route) {   // the upsample site of the range-safe mode without the upsample, exponent 0: planes, the convolution without its bias, then bias + statistics in one pass
+    const ConvW cw = ow.conv(wbuf, w, bias, Cout, Cin, 3);
+    Pass p = op_pass(c, s, x, n, H, W, Cin);
+    p.part.buf = part;
+    if (range_route) {   // the upsample site of the range-safe mode without the upsample, with a zeroed exponent: planes, the convolution without its bias, then bias + statistics in one pass
         HIP_CHECK(hipMemsetAsync(e, 0, sizeof(int), s));
-        launch_range_split(x, planes, (long)n * hw, Cin, e, s);
-        ConvW wb = cw;
-        wb.b = nullptr;
-        conv3(xp, wb, y, nullptr, 0, s, true, nullptr);
-        launch_range_unscale(y, cw.b, nullptr, (long)n * hw, Cout, e, part, s);
+        RangedOpts ro;
+        ro.plane_operand = ro.leave_partials = true;
+        ro.e = e;
+        p.ranged(p.x, cw, planes, y, ro);
     } else {
-        launch_to_planes(x, planes, n, hw, Cin, s);
-        GnPart gp;
-        gp.buf = part;
-        conv3(xp, cw, y, nullptr, 0, s, true, &gp);
-        BG_REQUIRE(gp.of == y, "op_conv3x3_gn_stats: the convolution did not leave partials");
+        p.conv3(p.to_planes(p.x, planes, nullptr), cw, y, CONV_SAME);
     }
+    BG_REQUIRE(p.part.of == y, "op_conv3x3_gn_stats: the convolution did not leave partials");
     launch_groupnorm_stats_from_partials(part, stats, n, hw, Cout, 1e-6f, s);
 }
 

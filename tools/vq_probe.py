@@ -34,11 +34,12 @@ for _ in range(reps):
     out = run()
     torch.cuda.synchronize()
     ts.append(time.time() - t0)
+exps = ctx.vq_range_exponents().tolist()   # of the last timed call (precision f16x3r; else empty)
 head = f"n={n} precision={precision} {what}: {min(ts) * 1e3 / (n / 6):.3f} ms per six-view scene (best of {reps}; mean {sum(ts) / len(ts) * 1e3 / (n / 6):.3f})"
 if what == "encode":   # the ids are the fingerprint for A/B runs over kernel variants that must not change results
-    print(f"{head}, ids sha256 {hashlib.sha256(out.cpu().numpy().tobytes()).hexdigest()[:16]}, range exponents {ctx.vq_range_exponents().tolist()}")
+    print(f"{head}, ids sha256 {hashlib.sha256(out.cpu().numpy().tobytes()).hexdigest()[:16]}, range exponents {exps}")
 else:
     pix = ctx.vq_decode(arg[:12], uint8=False)   # fp32 pixels of two scenes: a bit-level fingerprint for A/B runs over kernel variants that must not change results
     sha = hashlib.sha256(pix.cpu().numpy().tobytes()).hexdigest()[:16]
-    print(f"{head}, checksum {int(out.long().sum())}, fp32 pixels sha256 {sha}")
+    print(f"{head}, checksum {int(out.long().sum())}, fp32 pixels sha256 {sha}, range exponents {exps}")
 ctx.close()
