@@ -77,6 +77,9 @@ SIGNATURES = {
     "bevgen_vq_encode": (_i, [_p, _p, _i, _i, _i, _p, _p]),
     "bevgen_vq_range_exponents": (_i, [_p, C.POINTER(C.c_int32), _i, C.POINTER(_i)]),
     "bevgen_op_gemm": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _p]),
+    "bevgen_op_muse_qkv": (_i, [_p, _i, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _f, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p]),
+    "bevgen_op_muse_ff": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p]),
+    "bevgen_op_layernorm_planes": (_i, [_p, _p, _i, _p, _p, _p, _i, _i, _i, _i, _p]),
     "bevgen_op_ln_gemm": (_i, [_p, _p, _p, _p, _f, _p, _p, _p, _i, _i, _i, _i, _i, C.POINTER(_i), _p]),
     "bevgen_op_mlp_fused": (_i, [_p, _p, _p, _p, _f, _p, _p, _p, _p, _i, _p, _i, _i, _p]),
     "bevgen_op_remask": (_i, [_p, _p, _p, _p, _i, _i, _i, C.c_int64, _p]),

@@ -323,6 +323,139 @@ int bevgen_op_gemm(bevgen_ctx* ctx, const float* a, const float* w, const float*
     });
 }
 
+int bevgen_op_muse_qkv(bevgen_ctx* ctx, int kind, const float* a, const float* w, const float* ln_gamma, const float* q_scale, const float* k_scale, const float* null_kv, int B,
+                       int T, int H, int K, int ld, float post, int block, int weights, int form, int ksplit, void* qh, void* ql, void* kh, void* kl, void* vth, void* vtl,
+                       void* stream) {
+    return guarded(ctx, [&] {
+        hipStream_t s = (hipStream_t)stream;
+        const bool has_q = kind == 0 || kind == 2, has_kv = kind == 1 || kind == 2;
+        BG_REQUIRE(ctx->cfg.precision == BEVGEN_PRECISION_F16X3, "op_muse_qkv: needs a split-precision (f16x3) context");
+        BG_REQUIRE(kind >= 0 && kind <= 2 && a && w && B >= 1 && T >= 1 && H >= 1 && K >= 32 && K % 32 == 0 && (long)B * T * K < (1L << 30) && 192L * H * K < (1L << 30),
+                   "op_muse_qkv: bad arguments (the plane images are addressed with 32-bit byte offsets)");
+        BG_REQUIRE((!has_q || (q_scale && qh && ql)) && (!has_kv || (k_scale && null_kv && kh && kl && vth && vtl && ld >= T + 1)),
+                   "op_muse_qkv: kind %d needs its scales, its output planes and ld >= T + 1 (ld=%d T=%d)", kind, ld, T);
+        BG_REQUIRE((block == 0 || block == 4) && weights >= 0 && weights <= 2 && (form == 0 || (form == 1 && kind != 2)) && ksplit >= 1 && ksplit <= 8 && (form == 1 || ksplit == 1),
+                   "op_muse_qkv: block 0 | 4, weights 0..2, form 0 | 1 (1: kind 0 or 1), ksplit 1..8 (form 1 only)");
+        const int M = B * T, HD = H * 64, N = HD * (kind + 1);
+        uint16_t *ap, *bp;
+        float *wr, *raw, *kpart;
+        void* aux;
+        ctx->arena.carve([&](Arena& ar) {
+            ap = ar.get<uint16_t>((size_t)M * K * 2);
+            bp = ar.get<uint16_t>((size_t)N * K * 2);
+            wr = weights ? ar.get<float>((size_t)N * K) : nullptr;   // round_to_f16 rounds in place: a copy of the caller's matrix
+            aux = has_kv ? ar.alloc((size_t)4 * HD * sizeof(_Float16)) : nullptr;
+            raw = form == 1 ? ar.get<float>((size_t)M * N) : nullptr;
+            kpart = form == 1 && ksplit > 1 ? ar.get<float>((size_t)ksplit * M * N) : nullptr;
+        });
+        if (ln_gamma) launch_layernorm_planes(a, K, ln_gamma, nullptr, ap, K, M, K, 1e-5f, s);
+        else launch_split_weight(a, ap, (long)M * K, s);
+        const float* wu = w;
+        if (weights) {
+            HIP_CHECK(hipMemcpyAsync(wr, w, (size_t)N * K * sizeof(float), hipMemcpyDeviceToDevice, s));
+            launch_round_to_f16(wr, nullptr, (long)N * K, s);
+            wu = wr;
+        }
+        launch_split_weight(wu, bp, (long)N * K, s);
+        if (has_kv) launch_muse_null_kv_prep(null_kv, k_scale, aux, H, s);
+        GemmArgs g;
+        g.A_hi = ap; g.A_lo = ap + 32; g.B = wu; g.B_hi = bp; g.B_lo = bp + 32;
+        g.M = M; g.N = N; g.K = K; g.lda = K; g.ldb = K; g.ldc = N;
+        g.b_lo_zero = weights >= 1; g.a_hi_only = weights == 2;
+        g.force_wm = block;
+        if (form == 1) {   // muse.cpp project(): the projection into the raw matrix, then the preparation kernel
+            g.C = raw; g.ksplit = ksplit; g.kpart = kpart;
+            launch_gemm_split_glds(g, s);
+            if (kind == 0) launch_muse_q_prep_split(raw, q_scale, qh, ql, B, H, T, post, s);
+            else launch_muse_kv_prep_split(raw, null_kv, k_scale, kh, kl, vth, vtl, B, H, T, ld, s);
+            return;
+        }
+        g.epi = kind == 0 ? EPI_MUSE_Q : kind == 1 ? EPI_MUSE_KV : EPI_MUSE_QKV;
+        g.epi_rows = T; g.epi_heads = H;
+        if (kind == 0) { g.epi_scale = q_scale; g.epi_hi = qh; g.epi_lo = ql; g.epi_post = post; }
+        else {
+            g.epi_scale = k_scale; g.epi_hi = kh; g.epi_lo = kl; g.epi_hi2 = vth; g.epi_lo2 = vtl; g.epi_aux = aux; g.epi_ld = ld;
+            if (kind == 2) { g.epi_qh = qh; g.epi_ql = ql; g.epi_qscale = q_scale; g.epi_post = post; }
+        }
+        launch_gemm_split_glds(g, s);
+    });
+}
+
+int bevgen_op_muse_ff(bevgen_ctx* ctx, const float* x, const float* w1, const float* gamma3, const float* w4, const float* residual, int M, int D, int F, int Dout, int level,
+                      int merge, int block, float* h_out, void* g_planes, float* g_sums, float* rowstat_out, void* y_planes, float* y_sums, float* y_out, void* stream) {
+    return guarded(ctx, [&] {
+        hipStream_t s = (hipStream_t)stream;
+        BG_REQUIRE(ctx->cfg.precision == BEVGEN_PRECISION_F16X3, "op_muse_ff: needs a split-precision (f16x3) context");
+        BG_REQUIRE(x && w1 && gamma3 && w4 && residual && M >= 1 && D >= 32 && D % 32 == 0 && F >= 1 && F <= 3072 && Dout >= 32 && Dout % 32 == 0 && (long)M * std::max(D, F + 64) < (1L << 30) &&
+                       (long)Dout * (F + 64) < (1L << 30) && (long)M * Dout < (1L << 29),
+                   "op_muse_ff: bad arguments (the plane images are addressed with 32-bit byte offsets)");
+        BG_REQUIRE(level >= 0 && level <= 2 && (merge == 0 || merge == 1) && (block == 0 || block == 4), "op_muse_ff: level 0..2, merge 0 | 1, block 0 | 4");
+        BG_REQUIRE(reinterpret_cast<uintptr_t>(residual) % 16 == 0 && reinterpret_cast<uintptr_t>(y_out) % 16 == 0 && reinterpret_cast<uintptr_t>(h_out) % 16 == 0,
+                   "op_muse_ff: residual, y and h must be 16-byte aligned");
+        const int Fpad = (int)round_up(F, 64), GF = Fpad / 32, GD = Dout / 32;
+        uint16_t *xp, *w1p, *w4p;
+        float *w1o, *w4pad, *w4g, *cs, *h, *gs, *rs, *ys, *y;
+        void *gp, *yp;
+        ctx->arena.carve([&](Arena& ar) {
+            xp = ar.get<uint16_t>((size_t)M * D * 2);
+            w1o = ar.get<float>((size_t)2 * Fpad * D);
+            w1p = ar.get<uint16_t>((size_t)2 * Fpad * D * 2);
+            w4pad = ar.get<float>((size_t)Dout * Fpad);
+            w4g = level >= 1 ? ar.get<float>((size_t)Dout * Fpad) : nullptr;
+            cs = level >= 1 ? ar.get<float>((size_t)Dout) : nullptr;
+            w4p = ar.get<uint16_t>((size_t)Dout * Fpad * 2);
+            h = level == 0 && !h_out ? ar.get<float>((size_t)M * Fpad) : h_out;
+            gp = level == 0 || !g_planes ? ar.alloc((size_t)M * Fpad * 4) : g_planes;   // (level 0: the NORMALISED planes - not the image the caller's buffer is for)
+            gs = level >= 1 && !g_sums ? ar.get<float>((size_t)GF * M * 2) : g_sums;
+            rs = level >= 1 && merge == 0 && !rowstat_out ? ar.get<float>((size_t)M * 2) : rowstat_out;
+            yp = level == 2 && !y_planes ? ar.alloc((size_t)M * Dout * 4) : y_planes;
+            ys = level == 2 && !y_sums ? ar.get<float>((size_t)GD * M * 2) : y_sums;
+            y = !y_out ? ar.get<float>((size_t)M * Dout) : y_out;
+        });
+        // operands as bevgen_finalize prepares them: the GEGLU row order of W1, W4 zero-padded to Fpad columns, and (folded forms) W4 o gamma3 with its row sums
+        launch_split_weight(x, xp, (long)M * D, s);
+        launch_geglu_weight_order(w1, w1o, F, Fpad, D, s);
+        launch_split_weight(w1o, w1p, 2L * Fpad * D, s);
+        launch_pad_rows(w4, F, w4pad, Fpad, Dout, F, s);
+        if (level >= 1) launch_ln_fold_weight(w4pad, gamma3, w4g, cs, Dout, Fpad, F, s);
+        const float* w4u = level >= 1 ? w4g : w4pad;
+        launch_split_weight(w4u, w4p, (long)Dout * Fpad, s);
+        // up-projection with GEGLU in its epilogue (muse.cpp feed_forward_split)
+        GemmArgs ge;
+        ge.A_hi = xp; ge.A_lo = xp + 32; ge.B = w1o; ge.B_hi = w1p; ge.B_lo = w1p + 32;
+        ge.M = M; ge.N = 2 * Fpad; ge.K = D; ge.lda = D; ge.ldb = D; ge.ldc = Fpad;
+        ge.C = h; ge.epi = EPI_GEGLU; ge.force_wm = block;
+        if (level >= 1) { ge.ln_out_planes = gp; ge.ln_out_stats = gs; ge.ln_out_ld = Fpad; ge.ln_rows = M; }
+        launch_gemm_split_glds(ge, s);
+        if (level == 0) launch_layernorm_planes(h, Fpad, gamma3, nullptr, gp, Fpad, M, F, 1e-5f, s);
+        // down-projection + residual
+        GemmArgs gd;
+        gd.A_hi = reinterpret_cast<const uint16_t*>(gp); gd.A_lo = gd.A_hi + 32; gd.B = w4u; gd.B_hi = w4p; gd.B_lo = w4p + 32;
+        gd.M = M; gd.N = Dout; gd.K = Fpad; gd.lda = Fpad; gd.ldb = Fpad; gd.ldc = Dout; gd.ldr = Dout;
+        gd.C = y; gd.R = residual; gd.force_wm = block;
+        if (level >= 1) {
+            gd.ln_in_cs = cs; gd.ln_rows = M;
+            if (merge == 0) { launch_ln_stats_finalize(gs, rs, M, GF, F, 1e-5f, s); gd.ln_in_stats = rs; }
+            else { gd.ln_in_gsums = gs; gd.ln_in_groups = GF; gd.ln_in_count = F; }
+        }
+        if (level == 2) { gd.ln_out_planes = yp; gd.ln_out_stats = ys; gd.ln_out_ld = Dout; gd.ln_rows = M; }
+        launch_gemm_split_glds(gd, s);
+    });
+}
+
+int bevgen_op_layernorm_planes(bevgen_ctx* ctx, const float* x, int ldx, const float* gamma, const float* beta, void* planes, int ldy, int rows, int D, int geglu, void* stream) {
+    return guarded(ctx, [&] {
+        BG_REQUIRE(x && gamma && planes && rows >= 1 && D >= 1 && ldy >= D && ldy % 32 == 0, "op_layernorm_planes: bad arguments");
+        if (geglu) {
+            BG_REQUIRE(!beta && ldx >= 2 * D, "op_layernorm_planes: the GEGLU form has no beta and reads rows of 2 D columns (ldx=%d D=%d)", ldx, D);
+            launch_geglu_layernorm_planes(x, ldx, gamma, planes, ldy, rows, D, 1e-5f, (hipStream_t)stream);
+        } else {
+            BG_REQUIRE(ldx >= D, "op_layernorm_planes: ldx=%d < D=%d", ldx, D);
+            launch_layernorm_planes(x, ldx, gamma, beta, planes, ldy, rows, D, 1e-5f, (hipStream_t)stream);
+        }
+    });
+}
+
 int bevgen_op_ln_gemm(bevgen_ctx* ctx, const float* a, const float* ln_w, const float* ln_b, float eps, const float* w, const float* bias, float* c, int M, int N, int K,
                       int act_gelu, int ksplit, int* ksplit_out, void* stream) {
     return guarded(ctx, [&] {

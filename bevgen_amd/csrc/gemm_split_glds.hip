@@ -63,6 +63,14 @@ struct RowDiv {
         return fmaf(e, r, q0);
     }
 };
+// a b as an fp32 value of its own.  The last product of a fused epilogue feeds a (hi, lo) split - lo = (v - hi) 2048 - or a sum; left to the compiler, the product is
+// contracted into that subtraction / addition (one fma on the UNROUNDED product) in the direct store forms, while the staged forms round it on its way through LDS, and
+// which addend of a sum takes the fma is the compiler's choice per form: the low planes and the LayerNorm group sums then differ in their last bits between the forms that
+// are promised to be bit-identical (tests/test_muse_proj_ops_gpu.py compares them).  Same instruction count: the rounded product is needed for the hi plane anyway.
+__device__ __forceinline__ float mul_rounded(float a, float b) {
+#pragma clang fp contract(off)
+    return a * b;
+}
 constexpr int GBN = 128, GBK = 32;
 // 1: the k loop issues v_mfma_f32_16x16x32_f16 (one MFMA per 16x16 tile and k-tile), 0: v_mfma_f32_32x32x16_f16 (two per 32x32 tile and k-tile).  Compile time only (csrc/Makefile
 // passes it): two loops per instantiation would double the compile time of the largest kernels.  See the header comment; measurements in profiles/r10_ab_gemm_mfma16.txt.
@@ -832,7 +840,7 @@ __device__ __forceinline__ void gemm_tile(const GemmArgs& g, const int tx, const
                     half4_t hi4, lo4;
 #pragma unroll
                     for (int e = 0; e < 4; ++e) {
-                        const float qv = (rdiv(v[j][qq * 4 + e]) * sc[e]) * g.epi_post;   // epi_post: the attention's score scale, folded into q
+                        const float qv = mul_rounded(rdiv(v[j][qq * 4 + e]) * sc[e], g.epi_post);   // epi_post: the attention's score scale, folded into q
                         hi4[e] = split_hi(qv);
                         lo4[e] = split_lo(qv, hi4[e]);
                     }
@@ -1012,7 +1020,7 @@ __device__ __forceinline__ void gemm_tile(const GemmArgs& g, const int tx, const
                         half4_t hi4, lo4;
 #pragma unroll
                         for (int e = 0; e < 4; ++e) {
-                            const float kv = rdiv(v[j][qq * 4 + e]) * sc[e];
+                            const float kv = mul_rounded(rdiv(v[j][qq * 4 + e]), sc[e]);
                             hi4[e] = split_hi(kv);
                             lo4[e] = split_lo(kv, hi4[e]);
                         }
@@ -1071,7 +1079,7 @@ __device__ __forceinline__ void gemm_tile(const GemmArgs& g, const int tx, const
                             const int q = qq * 4 + e;
                             const float xa = (accM[i][0][q] + accC[i][0][q] * kGLoInv) * g.alpha;
                             const float gt = (accM[i][1][q] + accC[i][1][q] * kGLoInv) * g.alpha;
-                            v[e] = gt * gelu_erf(xa);
+                            v[e] = mul_rounded(gt, gelu_erf(xa));
                         }
                         s1 += (v[0] + v[1]) + (v[2] + v[3]);
                         s2 += fmaf(v[0], v[0], v[1] * v[1]) + fmaf(v[2], v[2], v[3] * v[3]);
@@ -1112,7 +1120,7 @@ __device__ __forceinline__ void gemm_tile(const GemmArgs& g, const int tx, const
                     const int q = qq * 4 + e;
                     const float xa = (accM[i][0][q] + accC[i][0][q] * kGLoInv) * g.alpha;
                     const float gt = (accM[i][1][q] + accC[i][1][q] * kGLoInv) * g.alpha;
-                    v[e] = gt * gelu_erf(xa);
+                    v[e] = mul_rounded(gt, gelu_erf(xa));
                 }
                 if (Pp) {
                     // 16-byte plane stores: the lane halves of a row hold neighbouring 4-column groups - the lower half stores the hi parts of the pair's 8 columns,

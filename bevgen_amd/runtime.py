@@ -468,6 +468,45 @@ class Context:
         self._check(self.lib.bevgen_op_gemm(self._h, _ptr(a), _ptr(w), _ptr(bias), _ptr(residual), _ptr(c), M, N, K, int(gelu), int(skinny), self._s()))
         return c
 
+    def op_muse_qkv(self, kind, a, w, *, B, T, H, ld=0, q_scale=None, k_scale=None, null_kv=None, ln_gamma=None, post=1.0, block=0, weights=0, form=0, ksplit=1, out=None):
+        """Route M's to_q / to_kv / q|k|v projection (kind 'q' | 'kv' | 'qkv') with its fused epilogue (form 0) or un-fused (form 1) on a [B T, K] and w [N, K].
+        Returns the f16 planes it wrote as a dict: Qh, Ql [B, H, T, 64]; Kh, Kl [B, H, ld, 64]; VTh, VTl [B, H, 64, ld].  `out`: caller-owned planes of those names
+        (any float16 tensors of the right size - the library never clears them); missing ones are allocated zero-filled."""
+        k = {"q": 0, "kv": 1, "qkv": 2}[kind]
+        K = a.shape[1]
+        out = dict(out or {})
+        shapes = {"Qh": (B, H, T, 64), "Ql": (B, H, T, 64), "Kh": (B, H, ld, 64), "Kl": (B, H, ld, 64), "VTh": (B, H, 64, ld), "VTl": (B, H, 64, ld)}
+        for name in (("Qh", "Ql") if k != 1 else ()) + (("Kh", "Kl", "VTh", "VTl") if k != 0 else ()):
+            if name not in out:
+                out[name] = torch.zeros(shapes[name], dtype=torch.float16, device=self.device)
+        self._check(self.lib.bevgen_op_muse_qkv(self._h, k, _ptr(a), _ptr(w), _ptr(ln_gamma), _ptr(q_scale), _ptr(k_scale), _ptr(null_kv), int(B), int(T), int(H), int(K), int(ld),
+                                                float(post), int(block), int(weights), int(form), int(ksplit), _ptr(out.get("Qh")), _ptr(out.get("Ql")), _ptr(out.get("Kh")),
+                                                _ptr(out.get("Kl")), _ptr(out.get("VTh")), _ptr(out.get("VTl")), self._s()))
+        return out
+
+    def op_muse_ff(self, x, w1, gamma3, w4, residual, *, level=0, merge=0, block=0, out=None):
+        """Route M's feed-forward behind its first LayerNorm, y = LN_gamma3(GEGLU(x w1^T)) w4^T + residual, in fold form `level` (include/bevgen_hip.h).  `out`: caller-owned
+        outputs by name - h [M, Fpad] fp32, g_planes [M, Fpad / 32, 2, 32] f16, g_sums [Fpad / 32, M, 2], rowstat [M, 2], y_planes [M, Dout / 32, 2, 32] f16,
+        y_sums [Dout / 32, M, 2], y [M, Dout]; y is allocated when missing, the others stay library scratch.  Returns the dict."""
+        M, D = x.shape
+        F, Dout = gamma3.numel(), w4.shape[0]
+        out = dict(out or {})
+        if "y" not in out:
+            out["y"] = torch.empty((M, Dout), dtype=torch.float32, device=self.device)
+        self._check(self.lib.bevgen_op_muse_ff(self._h, _ptr(x), _ptr(w1), _ptr(gamma3), _ptr(w4), _ptr(residual), M, D, F, Dout, int(level), int(merge), int(block),
+                                               _ptr(out.get("h")), _ptr(out.get("g_planes")), _ptr(out.get("g_sums")), _ptr(out.get("rowstat")), _ptr(out.get("y_planes")),
+                                               _ptr(out.get("y_sums")), _ptr(out["y"]), self._s()))
+        return out
+
+    def op_layernorm_planes(self, x, gamma, beta=None, *, D, ldy, geglu=False, planes=None, rows=None):
+        """LayerNorm over the first D columns of x's rows (geglu: x = (a | gate) of 2 D columns, the rows normalised are gate * gelu(a)) as the interleaved f16 plane image
+        [rows, ldy / 32, 2, 32] = (hi 32 | lo 32) per 32 columns.  `planes`: a caller-owned image (never cleared); `rows`: fewer rows than x / planes hold."""
+        rows = x.shape[0] if rows is None else int(rows)
+        if planes is None:
+            planes = torch.zeros((rows, ldy // 32, 2, 32), dtype=torch.float16, device=self.device)
+        self._check(self.lib.bevgen_op_layernorm_planes(self._h, _ptr(x), x.stride(0), _ptr(gamma), _ptr(beta), _ptr(planes), int(ldy), rows, int(D), int(geglu), self._s()))
+        return planes
+
     def op_ln_gemm(self, a, w, ln_w=None, ln_b=None, bias=None, gelu=False, ksplit=0, eps=1e-5):
         """Decode-step projection kernel: act(LN?(a) w^T + bias); with K split over workgroups the partial sums are added here (the model path folds
         that sum into the consumer's row fetch)."""

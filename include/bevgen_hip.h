@@ -302,6 +302,29 @@ int bevgen_op_gemm(bevgen_ctx* ctx, const float* d_a, const float* d_w, const fl
                                                                                                kernels (tests / probes), 5 = 3 with the k range split over three slices, 6 = 3 in its stream-K form;
                                                                                                single-product (BEVGEN_PRECISION_F16X1) forms, w's low plane ignored: 7 = 4 computing
                                                                                                f16(A) f16(W)^T, 8 = 7 with the k range in three slices, 9 = 2 single-product */
+/* Route M's projections with their fused epilogues (gemm_split_glds.hip EPI_MUSE_Q / _KV / _QKV), operands built the way bevgen_finalize and muse.cpp build them
+ * (f16x3 contexts).  kind 0 = to_q, 1 = to_kv, 2 = q | k | v over d_a [B T, K] and d_w [64 H (kind + 1), K]; d_ln_gamma non-NULL: the A planes come from the LayerNorm
+ * kernel (gamma only) instead of a plain split of d_a.  Outputs are caller-owned f16 planes, never cleared here: Qh / Ql [B, H, T, 64] (kind 0, 2), Kh / Kl [B, H, ld, 64]
+ * with key row 1 + token and the prepared null key at row 0, VTh / VTl [B, H, 64, ld] (kind 1, 2; ld >= T + 1).  block: 0 = the launcher's choice, 4 = 256-row blocks.
+ * weights: 0 = the split planes of d_w, 1 = d_w rounded to f16 (two products), 2 = additionally the single-product form.  form 0 = the fused epilogue; 1 (kind 0, 1) =
+ * un-fused as the small-batch path runs it: the plain projection (k range in `ksplit` slices, added in slice order) and the preparation kernel - which also zero-fills
+ * the value columns (T, ld).  Unsupported arguments return BEVGEN_ERR_INVALID without a launch. */
+int bevgen_op_muse_qkv(bevgen_ctx* ctx, int kind, const float* d_a, const float* d_w, const float* d_ln_gamma /* or NULL */, const float* d_q_scale, const float* d_k_scale,
+                       const float* d_null_kv /* [2, H, 64] */, int B, int T, int H, int K, int ld, float post, int block, int weights, int form, int ksplit, void* d_qh, void* d_ql,
+                       void* d_kh, void* d_kl, void* d_vth, void* d_vtl, void* stream);
+/* Route M's feed-forward behind its first LayerNorm: y [M, Dout] = LN_gamma3(gate * gelu(a)) W4^T + residual with (a | gate) = x W1^T, Fpad = round_up(F, 64), x [M, D],
+ * w1 [2 F, D], w4 [Dout, F]; D % 32 == 0, Dout % 32 == 0.  level 0: GEGLU epilogue to fp32 d_h [M, Fpad], the LayerNorm kernel, the plain down-projection; 1: the
+ * up-projection writes the raw planes d_g_planes [M][Fpad / 32][hi 32 | lo 32] and the group sums d_g_sums [Fpad / 32][M][2] instead, the down-projection consumes them
+ * (W4 o gamma3); 2: the down-projection also writes the planes d_y_planes [M][Dout / 32][64] and sums d_y_sums [Dout / 32][M][2] of its own output rows.  merge 0: the
+ * statistics kernel ((mean, rstd) in d_rowstat [M][2]), 1: the consuming tiles merge the group sums.  block as above, on both projections.  Every output may be NULL
+ * (scratch is used); none is cleared; a level never writes the outputs of another level. */
+int bevgen_op_muse_ff(bevgen_ctx* ctx, const float* d_x, const float* d_w1, const float* d_gamma3, const float* d_w4, const float* d_residual, int M, int D, int F, int Dout,
+                      int level, int merge, int block, float* d_h, void* d_g_planes, float* d_g_sums, float* d_rowstat, void* d_y_planes, float* d_y_sums, float* d_y,
+                      void* stream);
+/* LayerNorm (gamma, optional beta; eps 1e-5) of d_x [rows, ldx] over D columns written as the interleaved plane image d_planes [rows][ldy / 32][hi 32 | lo 32] (columns
+ * [D, ldy) zero); geglu != 0: d_x is [rows, 2 D] = (a | gate), row stride ldx, and the rows normalised are gate * gelu(a) (no beta). */
+int bevgen_op_layernorm_planes(bevgen_ctx* ctx, const float* d_x, int ldx, const float* d_gamma, const float* d_beta /* or NULL */, void* d_planes, int ldy, int rows, int D,
+                               int geglu, void* stream);
 /* Decode-step projection (decode_fused.hip): C = act(LayerNorm?(A) W^T + bias) for M <= 64 rows; d_ln_w NULL = no LayerNorm; ksplit > 1 (no LayerNorm, no bias / act):
  * d_c receives the split-K partial sums [ksplit, M, N] that the consumer adds; ksplit 0 = the library's choice for (N, K), returned through *ksplit_out if non-NULL;
  * ksplit -1 (LayerNorm with beta and bias): one K slice, the LayerNorm folded into the product the way the decode step launches ln2 + MLP-up. */
