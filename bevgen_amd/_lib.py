@@ -103,6 +103,13 @@ SIGNATURES = {
     "bevgen_op_vq_quantize": (_i, [_p, _p, _p, _p, _p, _p, _l, _i, _i, _p]),
     "bevgen_op_conv3x3_gn_stats": (_i, [_p, _p, _p, _p, _i, _p, _p, _p, _i, _i, _i, _i, _i, _p]),
     "bevgen_op_conv_ranged": (_i, [_p, _p, _p, _p, _i, _p, _p, _i, _i, _i, _i, _i, _p]),
+    "bevgen_op_camera_embed": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p]),
+    "bevgen_op_cond_embed": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _p]),
+    "bevgen_op_token_rows": (_i, [_p, _i, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p]),
+    "bevgen_op_muse_qkv_prep_f32": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _p]),
+    "bevgen_op_kv_cache_write": (_i, [_p, _i, _p, _p, _p, _p, _i, _i, _i, _i, _i, _p, _i, _i, _i, _i, _i, _i, _p]),
+    "bevgen_op_attn_tables": (_i, [_p, _i, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _l, _l, _f, _p]),
+    "bevgen_op_attention_tiles": (_i, [_p, _p, _p, _p, _p, _i, _p, _i, _i, _i, _i, _f, _i, _i, _i, _p, _p]),
     "bevgen_decode_attention_splits": (_i, [_i, _i, _i]),
     "bevgen_profile_begin": (_i, [_p]),
     "bevgen_profile_end": (_i, [_p, C.POINTER(C.c_double)]),

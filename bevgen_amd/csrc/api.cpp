@@ -843,6 +843,139 @@ int bevgen_op_conv_ranged(bevgen_ctx* ctx, const float* x, const float* w, const
     });
 }
 
+// ---- the kernels around the layer stacks: each entry is the model's launcher on caller buffers (nothing is cleared, nothing staged)
+int bevgen_op_camera_embed(bevgen_ctx* ctx, const float* I_inv, const float* E_inv, const float* plane, const float* wimg, const float* wcam, float* img, float* c_embed, int B,
+                           int C, int T, int D, void* stream) {
+    return guarded(ctx, [&] {
+        BG_REQUIRE(I_inv && E_inv && plane && wimg && wcam && img && c_embed && B >= 1 && C >= 1 && T >= 1 && D >= 1, "op_camera_embed: bad arguments");
+        launch_camera_embed(I_inv, E_inv, plane, wimg, wcam, img, c_embed, B, C, T, D, (hipStream_t)stream);
+    });
+}
+
+int bevgen_op_cond_embed(bevgen_ctx* ctx, const int64_t* cond_ids, const float* cond_tok, const float* cond_pos, const float* bev_grid, const float* wbev, const float* bbev,
+                         const float* bev_cam_pos, const float* c_embed, float* out, int B, int C, int K, int D, int cond_vocab, void* stream) {
+    return guarded(ctx, [&] {
+        BG_REQUIRE(cond_ids && cond_tok && cond_pos && out && B >= 1 && C >= 0 && K >= 1 && D >= 1 && cond_vocab >= 1, "op_cond_embed: bad arguments");
+        BG_REQUIRE(!bev_grid || (wbev && bbev && bev_cam_pos && c_embed), "op_cond_embed: the grid form needs bev_embed's weight and bias, bev_cam_pos_emb and c_embed");
+        launch_cond_embed(cond_ids, cond_tok, cond_pos, bev_grid, wbev, bbev, bev_cam_pos, c_embed, out, B, C, K, D, cond_vocab, (hipStream_t)stream);
+    });
+}
+
+int bevgen_op_token_rows(bevgen_ctx* ctx, int kind, const int64_t* ids, const float* table, const float* img, const float* pos, const int64_t* fwd_idx, const int* d_step,
+                         void* out, int B, int N, int D, int vocab_rows, int C, int T, int n_steps, int rows_per_seq, int row0, void* stream) {
+    return guarded(ctx, [&] {
+        hipStream_t s = (hipStream_t)stream;
+        BG_REQUIRE(kind >= 0 && kind <= 4 && out && B >= 1, "op_token_rows: bad arguments");
+        float* x = reinterpret_cast<float*>(out);
+        if (kind == 0) {
+            BG_REQUIRE(ids && table && pos && N >= 1 && D >= 1 && vocab_rows >= 1, "op_token_rows (token_embed): bad arguments");
+            launch_token_embed(ids, table, img, pos, x, B, N, D, vocab_rows, s);
+        } else if (kind == 1) {
+            BG_REQUIRE(ids && table && pos && fwd_idx && d_step && D >= 1 && vocab_rows >= 1 && C >= 1 && T >= 1, "op_token_rows (ar_step_embed): bad arguments");
+            launch_ar_step_embed(ids, table, img, pos, fwd_idx, d_step, x, B, C, T, D, vocab_rows, s);
+        } else if (kind == 2) {
+            BG_REQUIRE(ids && table && pos && fwd_idx && N >= 1 && D >= 1 && vocab_rows >= 1 && row0 >= 0, "op_token_rows (ar_seq_embed): bad arguments");
+            launch_ar_seq_embed(ids, table, img, pos, fwd_idx, x, B, n_steps, rows_per_seq, row0, N, D, vocab_rows, s);
+        } else if (kind == 3) {
+            BG_REQUIRE(table && D >= 1 && row0 >= 0 && row0 < rows_per_seq, "op_token_rows (gather_rows): bad arguments");
+            launch_gather_rows(table, x, B, row0, rows_per_seq, D, s);
+        } else {
+            BG_REQUIRE(ids && fwd_idx && d_step && N >= 1, "op_token_rows (store_tokens): bad arguments");
+            launch_store_tokens(ids, fwd_idx, d_step, reinterpret_cast<int64_t*>(out), B, N, s);
+        }
+    });
+}
+
+int bevgen_op_muse_qkv_prep_f32(bevgen_ctx* ctx, const float* qraw, const float* kvraw, const float* null_kv, const float* q_scale, const float* k_scale, float* q, float* k,
+                                float* v, int B, int H, int Nq, int Nk, int Nk_pad, void* stream) {
+    return guarded(ctx, [&] {
+        BG_REQUIRE(B >= 1 && H >= 1 && (qraw || kvraw), "op_muse_qkv_prep_f32: bad arguments");
+        BG_REQUIRE(!qraw || (q_scale && q && Nq >= 1), "op_muse_qkv_prep_f32: the query form needs q_scale and d_q");
+        BG_REQUIRE(!kvraw || (null_kv && k_scale && k && v && Nk >= 1 && Nk_pad >= Nk + 1), "op_muse_qkv_prep_f32: the key / value form needs null_kv, k_scale, d_k, d_v and Nk_pad >= Nk + 1");
+        if (qraw) launch_muse_q_prep(qraw, q_scale, q, B, H, Nq, (hipStream_t)stream);
+        if (kvraw) launch_muse_kv_prep(kvraw, null_kv, k_scale, k, v, B, H, Nk, Nk_pad, (hipStream_t)stream);
+    });
+}
+
+int bevgen_op_kv_cache_write(bevgen_ctx* ctx, int kind, const float* qkv, float* q, void* kc, void* vc, int kv_dtype, int B, int H, int n, int pos0, const int* d_pos, int Lmax,
+                             int layers, int rows, int src, int dst0, int count, void* stream) {
+    return guarded(ctx, [&] {
+        hipStream_t s = (hipStream_t)stream;
+        BG_REQUIRE(kind >= 0 && kind <= 2 && kc && vc && (kv_dtype == 0 || kv_dtype == 1) && B >= 1 && H >= 1 && Lmax >= 1, "op_kv_cache_write: bad arguments");
+        if (kind == 0) {
+            BG_REQUIRE(qkv && n >= 1 && pos0 >= 0 && pos0 + n <= Lmax, "op_kv_cache_write (scatter): rows [%d, %d) do not fit Lmax = %d", pos0, pos0 + n, Lmax);
+            launch_ar_qkv_scatter(qkv, q, kc, vc, kv_dtype, B, H, n, pos0, Lmax, s);
+        } else if (kind == 1) {
+            BG_REQUIRE(qkv && d_pos && pos0 >= 0 && pos0 < Lmax, "op_kv_cache_write (append): bad arguments");
+            launch_ar_kv_append(qkv, kc, vc, kv_dtype, B, H, pos0, d_pos, Lmax, s);
+        } else {
+            BG_REQUIRE(layers >= 1 && rows >= 0 && rows <= Lmax && src >= 0 && src < B && dst0 >= 0 && count >= 0 && dst0 + count <= B,
+                       "op_kv_cache_write (replicate_prefix): slots [%d, %d) / source %d / %d rows do not fit B = %d, Lmax = %d", dst0, dst0 + count, src, rows, B, Lmax);
+            launch_replicate_prefix(kc, vc, layers, B, H, Lmax, rows, src, dst0, count, kv_dtype == 0 ? 4 : 2, s);
+        }
+    });
+}
+
+int bevgen_op_attn_tables(bevgen_ctx* ctx, int kind, const void* in0, const void* in1, const void* in2, void* out0, void* out1, int heads, int L, int rows, int cols, int blk,
+                          int ld0, int ld1, long hs0, long hs1, float scale, void* stream) {
+    return guarded(ctx, [&] {
+        hipStream_t s = (hipStream_t)stream;
+        const float* f0 = reinterpret_cast<const float*>(in0);
+        BG_REQUIRE(kind >= 0 && kind <= 5 && out0, "op_attn_tables: bad arguments");
+        if (kind == 0) {
+            BG_REQUIRE(L >= 1, "op_attn_tables (attn_bias): bad arguments");
+            launch_build_attn_bias(f0, reinterpret_cast<const float*>(in1), reinterpret_cast<float*>(out0), L, s);
+        } else if (kind == 1) {
+            BG_REQUIRE(in0 && out1 && rows >= 1 && cols >= 1 && L >= rows + cols && ld0 >= 1 && ld1 >= 1, "op_attn_tables (muse_bias): bad arguments");
+            launch_build_muse_bias(f0, L, cols, rows, reinterpret_cast<float*>(out0), ld0, reinterpret_cast<float*>(out1), ld1, s);
+        } else if (kind == 2) {
+            BG_REQUIRE(in0 && rows >= 1 && cols >= 1, "op_attn_tables (allowed): bad arguments");
+            launch_build_allowed(f0, reinterpret_cast<uint8_t*>(out0), (long)rows * cols, s);
+        } else if (kind == 3) {
+            BG_REQUIRE(in0 && out1 && heads >= 1 && blk >= 1 && L >= 1 && L % blk == 0 && ld1 >= (L + 15) / 16 + 1, "op_attn_tables (layout): bad arguments");
+            launch_build_layout(reinterpret_cast<const int64_t*>(in0), reinterpret_cast<uint8_t*>(out0), reinterpret_cast<uint16_t*>(out1), heads, L / blk, blk, L, ld1, s);
+        } else if (kind == 4) {
+            BG_REQUIRE(heads >= 1 && rows >= 1 && cols >= 1 && ld1 >= cols && (!in0 || ld0 >= cols), "op_attn_tables (masked_bias): bad arguments");
+            BG_REQUIRE(!in1 || (L >= rows && L >= cols), "op_attn_tables (masked_bias): the element mask is [L, L]");
+            BG_REQUIRE(!in2 || (blk >= 1 && L % blk == 0 && L >= rows && L >= cols), "op_attn_tables (masked_bias): the block layout covers L = %d keys in blocks of %d", L, blk);
+            SparseVis v;
+            if (in1) { v.allowed = reinterpret_cast<const uint8_t*>(in1); v.ldallowed = L; v.allowed_head_stride = hs0; }
+            if (in2) { v.lay = reinterpret_cast<const uint8_t*>(in2); v.lay_head_stride = hs1; v.nb = L / blk; v.blk = blk; }
+            launch_build_masked_bias(f0, v, reinterpret_cast<float*>(out0), heads, rows, cols, ld1, ld0, scale, s);
+        } else {
+            BG_REQUIRE(in0 && heads >= 1 && rows >= 1 && cols >= 32 && cols % 32 == 0 && ld0 >= cols, "op_attn_tables (attn_tiles): bad arguments");
+            launch_build_attn_tiles(f0, hs0, ld0, heads, rows, cols, reinterpret_cast<uint16_t*>(out0), s);
+        }
+    });
+}
+
+int bevgen_op_attention_tiles(bevgen_ctx* ctx, const float* q, const float* k, const float* v, const float* bias, int ldbias, const float* residual, int B, int H, int Nq,
+                              int Nk_pad, float scale, int kv_group, int use_tiles, int out_layout, float* out, void* stream) {
+    return guarded(ctx, [&] {
+        hipStream_t s = (hipStream_t)stream;
+        BG_REQUIRE(q && k && v && bias && out && B >= 1 && H >= 1 && Nq >= 1, "op_attention_tiles: null argument");
+        BG_REQUIRE(Nk_pad >= 32 && Nk_pad % 32 == 0 && ldbias >= Nk_pad && ldbias % 4 == 0, "op_attention_tiles: Nk_pad %% 32, bias row stride %% 4 and >= Nk_pad");
+        BG_REQUIRE(kv_group >= 1 && B % kv_group == 0, "op_attention_tiles: batch %d is not a multiple of kv_group %d", B, kv_group);
+        BG_REQUIRE(out_layout == 0 || out_layout == 1, "op_attention_tiles: out_layout 0 = [B, Nq, 64 H], 1 = [B, H, Nq, 64]");
+        AttnArgs a{};
+        a.Q = q; a.K = k; a.V = v; a.bias = bias; a.R = residual; a.O = out;
+        a.B = B; a.H = H; a.Nq = Nq; a.Nk_pad = Nk_pad;
+        a.q_bstride = (long)H * Nq * 64; a.q_hstride = (long)Nq * 64;
+        a.kv_bstride = (long)H * Nk_pad * 64; a.kv_hstride = (long)Nk_pad * 64;
+        a.ldbias = ldbias; a.bias_head_stride = (long)Nq * ldbias; a.scale = scale;
+        a.kv_group = kv_group;
+        if (out_layout == 0) { a.o_bstride = (long)Nq * H * 64; a.o_qstride = (long)H * 64; a.o_hstride = 64; }
+        else { a.o_bstride = (long)H * Nq * 64; a.o_qstride = 64; a.o_hstride = (long)Nq * 64; }
+        if (use_tiles) {
+            uint16_t* tiles;
+            ctx->arena.carve([&](Arena& ar) { tiles = ar.get<uint16_t>(attn_tiles_elems(H, Nq, Nk_pad)); });
+            launch_build_attn_tiles(bias, a.bias_head_stride, ldbias, H, Nq, Nk_pad, tiles, s);
+            a.tiles = tiles; a.tiles_head_stride = (long)cdiv(Nq, 128) * (Nk_pad / 32 + 1); a.tiles_ld = Nk_pad / 32 + 1;
+        }
+        launch_attention(a, s);
+    });
+}
+
 int bevgen_decode_attention_splits(int B, int H, int n) { return decode_attention_splits(B, H, n); }
 
 int bevgen_profile_begin(bevgen_ctx* ctx) {

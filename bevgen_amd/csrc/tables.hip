@@ -53,8 +53,8 @@ __global__ __launch_bounds__(256) void build_layout_kernel(const int64_t* __rest
     for (int j = threadIdx.x; j < nb; j += blockDim.x) dst[j] = src[j] != 0 ? 1 : 0;
     const int nc = (L + 15) / 16;
     for (int c = threadIdx.x; c < nc; c += blockDim.x) {
-        bool any = false;
-        for (int k = c * 16; k < min(L, c * 16 + 16) && !any; k += (blk < 16 ? blk : 16)) any = src[k / blk] != 0;
+        bool any = false;   // probe the chunk's first key, then the first key of every block that starts inside it (any block size: a chunk may straddle two blocks)
+        for (int k = c * 16; k < min(L, c * 16 + 16) && !any; k = (k / blk + 1) * blk) any = src[k / blk] != 0;
         present[c] = any ? 1 : 0;
     }
     __syncthreads();

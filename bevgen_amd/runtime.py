@@ -716,3 +716,51 @@ class Context:
         self._check(self.lib.bevgen_op_conv3x3_gn_stats(self._h, _ptr(x_nhwc), _ptr(w_oihw), _ptr(bias), int(range_route), _ptr(y), _ptr(part), _ptr(stats), n, H, W, Cin, Cout,
                                                         self._s()))
         return y, part, stats
+
+    # the kernels around the layer stacks (embed.hip, tables.hip, attention.hip's tile lists): every output is a caller-owned tensor the library never clears, so a test
+    # can surround it with guards and fill it with a sentinel; all tensors are handed over as they are (contiguous, on this context's device)
+    def op_camera_embed(self, I_inv, E_inv, plane, wimg, wcam, img, c_embed):
+        """img [B, C, T, D] and c_embed [B, C, D] (written in place) of I_inv [B, C, 3, 3], E_inv [B, C, 4, 4], plane [3, T], wimg / wcam [D, 4]."""
+        B, C, T, D = img.shape
+        self._check(self.lib.bevgen_op_camera_embed(self._h, _ptr(I_inv), _ptr(E_inv), _ptr(plane), _ptr(wimg), _ptr(wcam), _ptr(img), _ptr(c_embed), B, C, T, D, self._s()))
+
+    def op_cond_embed(self, cond_ids, cond_tok, cond_pos, out, *, bev_grid=None, wbev=None, bbev=None, bev_cam_pos=None, c_embed=None, C=0):
+        """out [B, K, D] (in place) = (cond_tok[clamp(id)] + bev term) + cond_pos; the bev term only with bev_grid [2+, K] (then wbev [D, 2], bbev [D], bev_cam_pos [C, K, D],
+        c_embed [B, C, D])."""
+        B, K, D = out.shape
+        C = bev_cam_pos.shape[0] if bev_cam_pos is not None else int(C)
+        self._check(self.lib.bevgen_op_cond_embed(self._h, _ptr(cond_ids), _ptr(cond_tok), _ptr(cond_pos), _ptr(bev_grid), _ptr(wbev), _ptr(bbev), _ptr(bev_cam_pos),
+                                                  _ptr(c_embed), _ptr(out), B, C, K, D, cond_tok.shape[0], self._s()))
+
+    TOKEN_ROW_KINDS = {"token_embed": 0, "ar_step_embed": 1, "ar_seq_embed": 2, "gather_rows": 3, "store_tokens": 4}
+
+    def op_token_rows(self, kind, out, *, ids=None, table=None, img=None, pos=None, fwd_idx=None, step=None, B, N=0, D=0, vocab_rows=0, C_=0, T=0, n_steps=0, rows_per_seq=0,
+                      row0=0):
+        """One of the row kernels in TOKEN_ROW_KINDS (include/bevgen_hip.h bevgen_op_token_rows) writing into `out` in place."""
+        self._check(self.lib.bevgen_op_token_rows(self._h, self.TOKEN_ROW_KINDS[kind], _ptr(ids), _ptr(table), _ptr(img), _ptr(pos), _ptr(fwd_idx), _ptr(step), _ptr(out), int(B),
+                                                  int(N), int(D), int(vocab_rows), int(C_), int(T), int(n_steps), int(rows_per_seq), int(row0), self._s()))
+
+    def op_muse_qkv_prep_f32(self, *, B, H, qraw=None, kvraw=None, null_kv=None, q_scale=None, k_scale=None, q=None, k=None, v=None, Nq=0, Nk=0, Nk_pad=0):
+        """The fp32 Route M preparation: q [B, H, Nq, 64] from qraw [B Nq, 64 H]; k / v [B, H, Nk_pad, 64] rows [0, Nk] from null_kv [2, H, 64] and kvraw [B Nk, 128 H]."""
+        self._check(self.lib.bevgen_op_muse_qkv_prep_f32(self._h, _ptr(qraw), _ptr(kvraw), _ptr(null_kv), _ptr(q_scale), _ptr(k_scale), _ptr(q), _ptr(k), _ptr(v), int(B), int(H),
+                                                         int(Nq), int(Nk), int(Nk_pad), self._s()))
+
+    def op_kv_cache_write(self, kind, kcache, vcache, *, kv_dtype, B, H, Lmax, qkv=None, q=None, n=1, pos0=0, pos=None, layers=1, rows=0, src=0, dst0=0, count=0):
+        """kind 'scatter' | 'append' | 'replicate_prefix' on caches [(layers,) B, H, Lmax, 64] of kv_dtype 0 (fp32) / 1 (fp16); `pos`: the device int32 position of append."""
+        k = {"scatter": 0, "append": 1, "replicate_prefix": 2}[kind]
+        self._check(self.lib.bevgen_op_kv_cache_write(self._h, k, _ptr(qkv), _ptr(q), _ptr(kcache), _ptr(vcache), int(kv_dtype), int(B), int(H), int(n), int(pos0), _ptr(pos),
+                                                      int(Lmax), int(layers), int(rows), int(src), int(dst0), int(count), self._s()))
+
+    ATTN_TABLE_KINDS = {"attn_bias": 0, "muse_bias": 1, "allowed": 2, "layout": 3, "masked_bias": 4, "attn_tiles": 5}
+
+    def op_attn_tables(self, kind, out0, out1=None, *, in0=None, in1=None, in2=None, heads=1, L=0, rows=0, cols=0, blk=1, ld0=0, ld1=0, hs0=0, hs1=0, scale=1.0):
+        """One of the table builders in ATTN_TABLE_KINDS writing into out0 / out1 in place; the meaning of the operands per kind: include/bevgen_hip.h bevgen_op_attn_tables."""
+        self._check(self.lib.bevgen_op_attn_tables(self._h, self.ATTN_TABLE_KINDS[kind], _ptr(in0), _ptr(in1), _ptr(in2), _ptr(out0), _ptr(out1), int(heads), int(L), int(rows),
+                                                   int(cols), int(blk), int(ld0), int(ld1), int(hs0), int(hs1), float(scale), self._s()))
+
+    def op_attention_tiles(self, q, k, v, bias, out, *, scale, residual=None, kv_group=1, use_tiles=True, out_layout=0):
+        """Flash attention with a per-head masked bias [H, Nq, ld] and (use_tiles) the key-tile lists built from it; q [B, H, Nq, 64], k / v [B / kv_group, H, Nk_pad, 64];
+        out (in place) [B, Nq, 64 H] (out_layout 0) or [B, H, Nq, 64] (1), residual in the same layout."""
+        B, H, Nq, _ = q.shape
+        self._check(self.lib.bevgen_op_attention_tiles(self._h, _ptr(q), _ptr(k), _ptr(v), _ptr(bias), bias.shape[-1], _ptr(residual), B, H, Nq, k.shape[2], float(scale),
+                                                       int(kv_group), int(use_tiles), int(out_layout), _ptr(out), self._s()))

@@ -428,6 +428,53 @@ int bevgen_op_conv3x3_gn_stats(bevgen_ctx* ctx, const float* d_x_nhwc, const flo
  * raise BEVGEN_STATUS_F16_RANGE. */
 int bevgen_op_conv_ranged(bevgen_ctx* ctx, const float* d_x_nhwc, const float* d_w_oihw, const float* d_bias, int kind, float* d_y_nhwc, int32_t* d_exp, int n, int H, int W,
                           int Cin, int Cout, void* stream);
+/* The kernels in front of and around the layer stacks (embed.hip, tables.hip, the tile-list path of attention.hip), each through the launcher the model calls, with
+ * operands laid out as muse.cpp / ar.cpp / context.cpp lay them out.  No entry clears or pre-fills a caller buffer.
+ * camera_embed: d_img [B, C, T, D] = normalize(Wimg d - Wcam c) with d = E_inv [I_inv pix; 1], c = E_inv[..., 3] (norm + 1e-7), d_c_embed [B, C, D] = Wcam c;
+ * d_I_inv [B, C, 3, 3], d_E_inv [B, C, 4, 4], d_plane [3, T], d_wimg / d_wcam [D, 4]. */
+int bevgen_op_camera_embed(bevgen_ctx* ctx, const float* d_I_inv, const float* d_E_inv, const float* d_plane, const float* d_wimg, const float* d_wcam, float* d_img,
+                           float* d_c_embed, int B, int C, int T, int D, void* stream);
+/* cond_embed: d_out [B, K, D] = (d_cond_tok[clamp(id, 0, cond_vocab - 1)] + (bev_embed(grid) - sum_c (d_bev_cam_pos[c, k] + d_c_embed[b, c]))) + d_cond_pos[k]; the
+ * middle term only with d_bev_grid [>= 2, K] non-NULL (then d_wbev [D, 2], d_bbev [D], d_bev_cam_pos [C, K, D], d_c_embed [B, C, D] are required). */
+int bevgen_op_cond_embed(bevgen_ctx* ctx, const int64_t* d_cond_ids, const float* d_cond_tok, const float* d_cond_pos, const float* d_bev_grid /* or NULL */,
+                         const float* d_wbev, const float* d_bbev, const float* d_bev_cam_pos, const float* d_c_embed, float* d_out, int B, int C, int K, int D,
+                         int cond_vocab, void* stream);
+/* token_rows: one row (table[clamp(id, 0, vocab_rows - 1)] + d_img row) + d_pos row per token (d_img NULL: no geometric term); D % 4 == 0 for kinds 0 and 2.
+ *   kind 0 token_embed:   d_ids [B, N], d_img [B, N, D], d_pos [N, D] -> d_out [B, N, D]
+ *   kind 1 ar_step_embed: d_ids [B] (this step's tokens), d_img [B, C T, D], j = d_fwd_idx[*d_step] -> d_out [B, D]
+ *   kind 2 ar_seq_embed:  d_ids [B, N] camera-major, d_img [B, N, D], j = d_fwd_idx[s] -> d_out[b, row0 + s] of [B, rows_per_seq, D] for s < n_steps
+ *   kind 3 gather_rows:   d_out [B, D] = d_table[b, row0] of [B, rows_per_seq, D]
+ *   kind 4 store_tokens:  d_out (int64 [B, N]) [b, d_fwd_idx[*d_step]] = d_ids[b] */
+int bevgen_op_token_rows(bevgen_ctx* ctx, int kind, const int64_t* d_ids, const float* d_table, const float* d_img /* or NULL */, const float* d_pos,
+                         const int64_t* d_fwd_idx, const int* d_step, void* d_out, int B, int N, int D, int vocab_rows, int C, int T, int n_steps, int rows_per_seq, int row0,
+                         void* stream);
+/* The fp32 Route M q / k / v preparation: d_q [B, H, Nq, 64] = l2norm(8 d_qraw [B Nq, 64 H]) o d_q_scale (d_qraw NULL: skipped); d_k / d_v [B, H, Nk_pad, 64] rows
+ * [0, Nk] = (null key / value of d_null_kv [2, H, 64], then d_kvraw [B Nk, (k | v) 64 H]), keys l2-normalised o d_k_scale (d_kvraw NULL: skipped). */
+int bevgen_op_muse_qkv_prep_f32(bevgen_ctx* ctx, const float* d_qraw /* or NULL */, const float* d_kvraw /* or NULL */, const float* d_null_kv, const float* d_q_scale,
+                                const float* d_k_scale, float* d_q, float* d_k, float* d_v, int B, int H, int Nq, int Nk, int Nk_pad, void* stream);
+/* Route A's KV-cache writers on a cache [B, H, Lmax, 64] (kv_dtype 0 fp32 / 1 fp16; fp16 values outside the range raise BEVGEN_STATUS_F16_RANGE).
+ *   kind 0 scatter: rows [pos0, pos0 + n) of every (b, h) from d_qkv [B n, (q | k | v) 64 H]; d_q [B, H, n, 64] (or NULL) receives the queries
+ *   kind 1 append:  n = 1, row *d_pos + pos0 (d_pos a device int)
+ *   kind 2 replicate_prefix: cache [layers, B, H, Lmax, 64]: the first `rows` rows of sequence slot `src` are copied to slots [dst0, dst0 + count) of every layer and head */
+int bevgen_op_kv_cache_write(bevgen_ctx* ctx, int kind, const float* d_qkv, float* d_q /* or NULL */, void* d_kcache, void* d_vcache, int kv_dtype, int B, int H, int n,
+                             int pos0, const int* d_pos, int Lmax, int layers, int rows, int src, int dst0, int count, void* stream);
+/* The tables bevgen_finalize and the Route A prefill build (tables.hip, attention.hip), written into caller buffers.
+ *   kind 0 attn_bias:   d_out0 [L, L] = tril_scatter(d_in0 [L (L + 1) / 2] or NULL) + (d_in1 [L, L] or NULL)
+ *   kind 1 muse_bias:   d_in0 = attn_bias [L, L], rows = N, cols = K -> d_out0 [N, ld0] = (0 | attn_bias[K + q, K ..] | -1e30), d_out1 [N, ld1] = (0 | attn_bias[K + q, .. K) | -1e30)
+ *   kind 2 allowed:     d_out0 (uint8 [rows cols]) = d_in0 (fp32) != 0
+ *   kind 3 layout:      d_in0 int64 [heads, L / blk, L / blk] -> d_out0 uint8 of the same shape, d_out1 uint16 [heads, L / blk, ld1] = (count, ascending ids of the 16-key
+ *                       chunks that overlap a present block); ld1 >= ceil(L / 16) + 1; slots behind the count are not written
+ *   kind 4 masked_bias: d_out0 [heads, rows, ld1] = visible(h, r, c) ? scale d_in0[r, c] (row stride ld0; NULL: 0) : -1e30, columns >= cols -1e30; visible = element mask
+ *                       d_in1 (uint8 [L, L], head stride hs0; NULL: all) AND block layout d_in2 (uint8 [., L / blk, L / blk], head stride hs1; NULL: all)
+ *   kind 5 attn_tiles:  d_in0 = masked bias (row stride ld0, head stride hs0), rows = Nq, cols = Nk_pad -> d_out0 uint16 [heads, ceil(Nq / 128), Nk_pad / 32 + 1] =
+ *                       (count, ascending ids of the 32-key tiles in which a row of the 128-row block has a value above 0.5 * -1e30) */
+int bevgen_op_attn_tables(bevgen_ctx* ctx, int kind, const void* d_in0, const void* d_in1, const void* d_in2, void* d_out0, void* d_out1, int heads, int L, int rows, int cols,
+                          int blk, int ld0, int ld1, long hs0, long hs1, float scale, void* stream);
+/* The flash-attention kernel in the form Route A's prefill and bevgen_sparse_self_attention run it: d_bias [H, Nq, ldbias] a masked bias per head, use_tiles != 0: the
+ * tile lists built from it inside the call (launch_build_attn_tiles), d_k / d_v [B / kv_group, H, Nk_pad, 64], d_residual (or NULL) added in the output's layout,
+ * out_layout 0: d_out [B, Nq, 64 H], 1: [B, H, Nq, 64].  Every query row must see a key in a listed tile. */
+int bevgen_op_attention_tiles(bevgen_ctx* ctx, const float* d_q, const float* d_k, const float* d_v, const float* d_bias, int ldbias, const float* d_residual /* or NULL */,
+                              int B, int H, int Nq, int Nk_pad, float scale, int kv_group, int use_tiles, int out_layout, float* d_out, void* stream);
 
 /* Per-kernel timing support for bench.py's roofline leg: number of workgroup splits the decode-attention kernel uses. */
 int bevgen_decode_attention_splits(int B, int H, int n);

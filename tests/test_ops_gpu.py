@@ -349,6 +349,8 @@ def _ar_attn_reference(x, partial, rbias, ln_w, ln_b, wqkv, bqkv, kc, vc, n, bia
     (4, 2, 4, 300, 512, 16, True),      # two sequences per layout sharing a 64-key prefix
     (8, 4, 8, 333, 512, 32, True),      # four per layout, 32-key blocks (two chunks per block)
     (8, 4, 8, 64, 512, 16, False),      # nothing beyond the shared prefix yet except the new key at n - 1 = 63 ... prefix 48
+    (2, 1, 4, 333, 512, 32, "offset"),  # 32-key blocks, block column 0 absent: every row's chunk list starts behind chunk 0 (the diagonal block keeps the row's own key)
+    (2, 1, 4, 300, 480, 24, "offset"),  # 24-key blocks: every second block boundary falls inside a 16-key chunk
 ])
 def test_ar_attn_fused_operator(gpu_ctx, B, G, H, n, Lmax, blk, sparse, kv, split):
     """ar_attn_fused_kernel (ln1 + q/k/v + cache append + block-sparse decode attention + residual) against fp64, over batch sizes, context lengths incl. n = 1 and
@@ -372,6 +374,11 @@ def test_ar_attn_fused_operator(gpu_ctx, B, G, H, n, Lmax, blk, sparse, kv, spli
         layout = (torch.rand(H, Lmax // blk, Lmax // blk, generator=g) < 0.4).long()
         mask[:, 0] = 1
         layout[:, :, 0] = 1   # every row keeps something
+        if sparse == "offset":
+            idx = torch.arange(Lmax // blk)
+            layout[:, :, 0] = 0
+            layout[:, idx, idx] = 1
+            mask[torch.arange(Lmax), torch.arange(Lmax)] = 1
     if kv == "f16":
         kc, vc = kc.half().float(), vc.half().float()   # the cache holds fp16-representable values; the appended row is rounded by the kernel
     ref, k_new, v_new = _ar_attn_reference(x, partial, rbias, ln_w, ln_b, wqkv, bqkv, kc, vc, n, bias, mask, layout, blk, G, prefix)
