@@ -75,6 +75,7 @@ SIGNATURES = {
     "bevgen_vq_decode": (_i, [_p, _p, _i, _i, _i, _i, _p, _p]),
     "bevgen_vq_decode_latents": (_i, [_p, _p, _i, _i, _i, _i, _p, _p]),
     "bevgen_vq_encode": (_i, [_p, _p, _i, _i, _i, _p, _p]),
+    "bevgen_vq_encode_ex": (_i, [_p, _p, _i, _i, _i, _p, _p, _p, _f, _p, _p, _p, _p]),
     "bevgen_vq_range_exponents": (_i, [_p, C.POINTER(C.c_int32), _i, C.POINTER(_i)]),
     "bevgen_op_gemm": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _p]),
     "bevgen_op_muse_qkv": (_i, [_p, _i, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _f, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p]),
@@ -101,6 +102,8 @@ SIGNATURES = {
     "bevgen_op_vq_attn_block": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p]),
     "bevgen_op_vq_out_tail": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _p, _i, _i, _i, _i, _p]),
     "bevgen_op_vq_quantize": (_i, [_p, _p, _p, _p, _p, _p, _l, _i, _i, _p]),
+    "bevgen_op_vq_geo_embed": (_i, [_p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _p]),
+    "bevgen_op_vq_quant_error": (_i, [_p, _p, _p, _p, _f, _p, _p, _l, _i, _i, _p]),
     "bevgen_op_conv3x3_gn_stats": (_i, [_p, _p, _p, _p, _i, _p, _p, _p, _i, _i, _i, _i, _i, _p]),
     "bevgen_op_conv_ranged": (_i, [_p, _p, _p, _p, _i, _p, _p, _i, _i, _i, _i, _i, _p]),
     "bevgen_op_camera_embed": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p]),

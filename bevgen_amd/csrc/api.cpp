@@ -248,11 +248,19 @@ int bevgen_vq_decode(bevgen_ctx* ctx, const int64_t* ids, int n, int lat_h, int 
 }
 
 int bevgen_vq_encode(bevgen_ctx* ctx, const float* x, int n, int H, int W, int64_t* ids, void* stream) {
+    return bevgen_vq_encode_ex(ctx, x, n, H, W, nullptr, nullptr, nullptr, 0.25f, ids, nullptr, nullptr, stream);
+}
+
+int bevgen_vq_encode_ex(bevgen_ctx* ctx, const float* x, int n, int H, int W, const float* I_inv, const float* E_inv, const float* plane, float beta, int64_t* ids,
+                        float* row_err, float* loss, void* stream) {
     return guarded(ctx, [&] {
         need_final(ctx);
         BG_REQUIRE(x && ids && n >= 1, "vq_encode: bad arguments");
         if (H <= 0 || W <= 0) H = W = ctx->cfg.vq_resolution;
-        vq_encode(*ctx, x, n, H, W, ids, (hipStream_t)stream);
+        VqEncodeExtras ex;
+        ex.I_inv = I_inv; ex.E_inv = E_inv; ex.plane = plane;
+        ex.beta = beta; ex.row_err = row_err; ex.loss = loss;
+        vq_encode(*ctx, x, n, H, W, ids, ex, (hipStream_t)stream);
     });
 }
 
@@ -824,6 +832,22 @@ int bevgen_op_vq_quantize(bevgen_ctx* ctx, const float* z, const float* codebook
     return guarded(ctx, [&] {
         BG_REQUIRE(z && codebook && ids, "op_vq_quantize: null argument");
         vq_op_quantize(*ctx, z, codebook, ids, zz, ee, rows, n_e, D, (hipStream_t)stream);
+    });
+}
+
+int bevgen_op_vq_geo_embed(bevgen_ctx* ctx, float* h, const float* I_inv, const float* E_inv, const float* plane, const float* wimg, const float* wcam, int n, int T, int D,
+                           void* stream) {
+    return guarded(ctx, [&] {
+        BG_REQUIRE(h && I_inv && E_inv && plane && wimg && wcam, "op_vq_geo_embed: null argument");
+        launch_vq_geo_embed(h, I_inv, E_inv, plane, wimg, wcam, n, T, D, (hipStream_t)stream);
+    });
+}
+
+int bevgen_op_vq_quant_error(bevgen_ctx* ctx, const float* z, const float* codebook, const int64_t* ids, float beta, float* row_err, float* loss, long rows, int n_e, int D,
+                             void* stream) {
+    return guarded(ctx, [&] {
+        BG_REQUIRE(z && codebook && ids && row_err, "op_vq_quant_error: null argument");
+        vq_op_quant_error(z, codebook, ids, beta, row_err, loss, rows, n_e, D, (hipStream_t)stream);
     });
 }
 

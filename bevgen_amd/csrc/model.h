@@ -136,6 +136,9 @@ struct Ctx {
     AttnBlockW enc_mid_attn;
     const float *enc_norm_out_w = nullptr, *enc_norm_out_b = nullptr;
     float* codebook_sqnorm = nullptr;
+    // geometric embedding of a camera VQGAN (vqgan.py:62-69, 87-112): img_embed / cam_embed [z_channels, 4], present together or not at all (vq_enc_finalize)
+    bool has_vq_geo = false;
+    const float *vq_geo_wimg = nullptr, *vq_geo_wcam = nullptr;
     VqShape vq_dec_shape, vq_enc_shape;   // what vq_plan.h needs to know of the loaded decoder / encoder (vq_finalize)
 
     // ---- split-precision mode (BEVGEN_PRECISION_F16X3): (hi, lo) f16 planes of every GEMM / conv weight, keyed by its fp32 device pointer
@@ -216,7 +219,13 @@ void ar_forward(Ctx& c, const int64_t* cond, const float* I_inv, const float* E_
 // vqdec.cpp
 void vq_finalize(Ctx& c);
 void vq_decode(Ctx& c, const int64_t* ids, const float* latents_nchw, int n, int lat_h, int lat_w, int out_mode, void* out, hipStream_t s);
-void vq_encode(Ctx& c, const float* x_nchw, int n, int RH, int RW, int64_t* ids, hipStream_t s);
+// what bevgen_vq_encode_ex adds to an encode call: the geometry of a camera VQGAN (all three pointers or none) and the codebook loss (loss needs row_err)
+struct VqEncodeExtras {
+    const float *I_inv = nullptr, *E_inv = nullptr, *plane = nullptr;   // [n, 3, 3], [n, 4, 4], [3, lat_h lat_w]
+    float beta = 0.25f;
+    float *row_err = nullptr, *loss = nullptr;                          // [n, lat_h lat_w] (the caller's: the arena is reset per pass), one float
+};
+void vq_encode(Ctx& c, const float* x_nchw, int n, int RH, int RW, int64_t* ids, const VqEncodeExtras& ex, hipStream_t s);
 int vq_range_exponents(Ctx& c, int32_t* h_out, int cap);   // range-safe mode: exponents of the most recent vq_decode / vq_encode in site order (synchronises); returns their number
 // operator entries (bevgen_op_conv3x3_down, _vq_attn_block, _vq_out_tail, _vq_quantize, _conv3x3_gn_stats, _conv_ranged; include/bevgen_hip.h): the model's helpers on caller tensors
 void vq_op_conv3x3_down(Ctx& c, const float* x, const float* w, const float* bias, float* y, int n, int H, int W, int Cin, int Cout, hipStream_t s);
@@ -228,11 +237,15 @@ void vq_op_quantize(Ctx& c, const float* z, const float* codebook, int64_t* ids,
 void vq_op_conv3x3_gn_stats(Ctx& c, const float* x, const float* w, const float* bias, int range_route, float* y, float* part, float* stats, int n, int H, int W, int Cin,
                             int Cout, hipStream_t s);
 void vq_op_conv_ranged(Ctx& c, const float* x, const float* w, const float* bias, int kind, float* y, int32_t* d_exp, int n, int H, int W, int Cin, int Cout, hipStream_t s);
+void vq_op_quant_error(const float* z, const float* codebook, const int64_t* ids, float beta, float* row_err, float* loss, long rows, int n_e, int D, hipStream_t s);
 // vqenc_kernels.hip
 void launch_nchw_to_nhwc_pad(const float* x, float* y, int n, int hw, int C, int Cpad, hipStream_t s);
 void launch_relayout_conv_weight_pad(const float* w, float* o, int cout, int cin, int cin_pad, int kh, int kw, hipStream_t s);
 void launch_row_sqnorm(const float* x, float* out, long rows, int D, hipStream_t s);
 void launch_vq_argmin(const float* dots, const float* zz, const float* ee, int64_t* ids, long rows, int n_e, hipStream_t s);
+void launch_vq_geo_embed(float* h, const float* I_inv, const float* E_inv, const float* plane, const float* Wimg, const float* Wcam, int n, int T, int D, hipStream_t s);   // h [n, T, D] += normalised ray embedding, in place
+void launch_vq_row_err(const float* z, const float* codebook, const int64_t* ids, float* row_err, long rows, int n_e, int D, hipStream_t s);   // row_err[r] = |codebook[ids[r]] - z[r]|^2
+void launch_vq_loss(const float* row_err, long rows, int D, float beta, float* loss, hipStream_t s);   // loss[0] = (1 + beta) / (rows D) sum(row_err), double accumulation in a fixed order
 // tables.hip
 void launch_build_attn_bias(const float* tril_emb /*or null*/, const float* prob /*or null*/, float* out, int L, hipStream_t s);
 void launch_build_muse_bias(const float* attn_bias, int L, int K, int N, float* bias_self, int ldS, float* bias_cross, int ldC, hipStream_t s);

@@ -149,6 +149,9 @@ struct RangedOpts {
 // the decoder's last step: out_mode as in vq_decode; mean / stdv are read for out_mode != 0 only; img: [n, h w, 4] scratch of the three-kernel form
 struct TailOut { void* out; int out_mode; const float *mean, *stdv; float* img; bool fused; };
 
+// the geometric embedding of a pass (launch_vq_geo_embed): the matrices of the pass's images, the latent plane and the two weights [z_channels, 4]
+struct GeoEmbed { const float *I_inv, *E_inv, *plane, *wimg, *wcam; };
+
 // One pass over n images: the carved buffers, the current activation and every launch that writes an activation buffer.
 struct Pass {
     hipStream_t s = nullptr;
@@ -369,9 +372,14 @@ struct Pass {
         launch_nhwc_to_nchw(to.img, of, x.n, x.h * x.w, co.cout, co.cout, mean, stdv, denorm, s, o8);
     }
     // Encoder.forward's last operators and quant_conv (1x1): x -> zq [n, lat_h lat_w, embed_dim]
-    void to_latents(const float* nw, const float* nb, const ConvW& conv_out, const ConvW& quant_conv) {
+    // geo: the camera-ray embedding is added to conv_out's output in place, in front of quant_conv and of its range-safe site (whose exponent is therefore that of the sum)
+    void to_latents(const float* nw, const float* nb, const ConvW& conv_out, const ConvW& quant_conv, const GeoEmbed* geo) {
         const Two free = others();
         conv3(gn(x, nw, nb, t, 1, planes), conv_out, free.second, CONV_SAME, nullptr, false);   // [n, lat_h lat_w, z_channels]
+        if (geo) {
+            note_write(part, free.second);
+            launch_vq_geo_embed(free.second, geo->I_inv, geo->E_inv, geo->plane, geo->wimg, geo->wcam, x.n, x.h * x.w, conv_out.cout, s);
+        }
         RangedOpts one;
         one.k = 1;
         if (range) ranged(Act{free.second, x.n, x.h, x.w, conv_out.cout}, quant_conv, free.first, zq, one);
@@ -480,6 +488,17 @@ void vq_enc_finalize(Ctx& c) {
     BG_REQUIRE(c.enc_conv_out.cout == g.vq_z_channels && c.quant_conv.cout == g.vq_embed_dim, "encoder output channels do not match z_channels / embed_dim (double_z must be False)");
     c.codebook_sqnorm = reinterpret_cast<float*>(c.own((size_t)g.vq_n_embed * sizeof(float)));
     launch_row_sqnorm(c.codebook, c.codebook_sqnorm, g.vq_n_embed, g.vq_embed_dim, 0);
+    // img_embed / cam_embed of VQModel(geometric_embedding=True): 1x1 convolutions [z_channels, 4, 1, 1] without a bias, read as [z_channels, 4]
+    const DevTensor *wi = c.find(kPrefix + "img_embed.weight"), *wc = c.find(kPrefix + "cam_embed.weight");
+    BG_REQUIRE((wi != nullptr) == (wc != nullptr), "geometric embedding: img_embed.weight and cam_embed.weight come together ('%s' is missing)", wi ? "cam_embed.weight" : "img_embed.weight");
+    c.has_vq_geo = wi != nullptr;
+    if (c.has_vq_geo) {
+        for (const DevTensor* w : {wi, wc})
+            BG_REQUIRE(w->shape.size() == 4 && w->shape[0] == g.vq_z_channels && w->shape[1] == 4 && w->shape[2] == 1 && w->shape[3] == 1,
+                       "geometric embedding: img_embed.weight / cam_embed.weight must be [z_channels = %d, 4, 1, 1] (cam_emd_dim == z_channels)", g.vq_z_channels);
+        c.vq_geo_wimg = wi->f();
+        c.vq_geo_wcam = wc->f();
+    }
     c.vq_enc_shape = shape_of(g, true, c.enc_cin_pad, c.enc_mid1, c.enc_mid2);
     for (int lvl = 0; lvl < g.vq_num_levels; ++lvl) shape_level(c.vq_enc_shape, lvl, c.down[lvl].blocks, !c.down[lvl].attns.empty(), c.down[lvl].has_down);
 }
@@ -588,8 +607,14 @@ int vq_range_exponents(Ctx& c, int32_t* out, int cap) {
 //   VectorQuantizer2.forward  stage1/quantize.py:271-312
 // =====================================================================================================
 // x [n, in_channels, RH, RW] with RH, RW multiples of 2^(levels-1) (fully convolutional: 256 x 256 or nuScenes' 224 x 400) -> ids [n, (RH >> (levels-1)) * (RW >> (levels-1))]
-void vq_encode(Ctx& c, const float* x_nchw, int n_total, int RH, int RW, int64_t* ids, hipStream_t s) {
+// ex: per-image geometry (a context with img_embed / cam_embed needs it, one without refuses it), row_err [n, lat_h lat_w] and the codebook loss over all rows of the call
+void vq_encode(Ctx& c, const float* x_nchw, int n_total, int RH, int RW, int64_t* ids, const VqEncodeExtras& ex, hipStream_t s) {
     BG_REQUIRE(c.has_vq_enc, "this context holds no VQGAN encoder weights (encoder.* tensors were not loaded)");
+    const bool geo = ex.I_inv || ex.E_inv || ex.plane;
+    BG_REQUIRE(!geo || (ex.I_inv && ex.E_inv && ex.plane), "vq_encode: the geometry is I_inv, E_inv and the image plane together");
+    BG_REQUIRE(!c.has_vq_geo || geo, "vq_encode: this VQGAN has a geometric embedding (img_embed / cam_embed): the call needs I_inv, E_inv and the image plane");
+    BG_REQUIRE(c.has_vq_geo || !geo, "vq_encode: geometry was passed, but this VQGAN has no geometric embedding (img_embed.weight / cam_embed.weight were not loaded)");
+    BG_REQUIRE(!ex.loss || ex.row_err, "vq_encode: the loss is taken over row_err, which the caller provides");
     const auto& g = c.cfg;
     const int f = 1 << (g.vq_num_levels - 1);
     BG_REQUIRE(RH >= f && RW >= f && RH % f == 0 && RW % f == 0, "vq_encode: image %d x %d is not a multiple of the downsampling factor %d", RH, RW, f);
@@ -620,10 +645,13 @@ void vq_encode(Ctx& c, const float* x_nchw, int n_total, int RH, int RW, int64_t
         p.res(c.enc_mid1);
         p.attn(c.enc_mid_attn);
         p.res(c.enc_mid2);
-        p.to_latents(c.enc_norm_out_w, c.enc_norm_out_b, c.enc_conv_out, c.quant_conv);
+        const GeoEmbed ge{geo ? ex.I_inv + (long)i0 * 9 : nullptr, geo ? ex.E_inv + (long)i0 * 16 : nullptr, ex.plane, c.vq_geo_wimg, c.vq_geo_wcam};
+        p.to_latents(c.enc_norm_out_w, c.enc_norm_out_b, c.enc_conv_out, c.quant_conv, geo ? &ge : nullptr);
         quantize(p.zq, n * lat_hw, Codebook{c.codebook, c.codebook_sqnorm, g.vq_n_embed, g.vq_embed_dim}, e.zz, e.dots, ids + (long)i0 * lat_hw, s);
+        if (ex.row_err) launch_vq_row_err(p.zq, c.codebook, ids + (long)i0 * lat_hw, ex.row_err + (long)i0 * lat_hw, n * lat_hw, g.vq_n_embed, g.vq_embed_dim, s);
     }
     sites_done(c, sites);
+    if (ex.loss) launch_vq_loss(ex.row_err, (long)n_total * lat_hw, g.vq_embed_dim, ex.beta, ex.loss, s);   // once, over all rows of all passes
 }
 
 // =====================================================================================================
@@ -785,6 +813,12 @@ void vq_op_quantize(Ctx& c, const float* z, const float* codebook, int64_t* ids,
     quantize(z, rows, Codebook{codebook, ee, n_e, D}, zz, dots, ids, s);
     if (zz_out) HIP_CHECK(hipMemcpyAsync(zz_out, zz, (size_t)rows * sizeof(float), hipMemcpyDeviceToDevice, s));
     if (ee_out) HIP_CHECK(hipMemcpyAsync(ee_out, ee, (size_t)n_e * sizeof(float), hipMemcpyDeviceToDevice, s));
+}
+
+void vq_op_quant_error(const float* z, const float* codebook, const int64_t* ids, float beta, float* row_err, float* loss, long rows, int n_e, int D, hipStream_t s) {
+    BG_REQUIRE(rows >= 1 && rows <= 0x7FFFFFFFL && n_e >= 1 && D >= 32 && D % 32 == 0, "op_vq_quant_error: needs D %% 32 == 0 (rows=%ld n_e=%d D=%d)", rows, n_e, D);
+    launch_vq_row_err(z, codebook, ids, row_err, rows, n_e, D, s);
+    if (loss) launch_vq_loss(row_err, rows, D, beta, loss, s);
 }
 
 void vq_op_conv3x3_gn_stats(Ctx& c, const float* x, const float* w, const float* bias, int range_route, float* y, float* part, float* stats, int n, int H, int W, int Cin,

@@ -85,4 +85,106 @@ void launch_vq_argmin(const float* dots, const float* zz, const float* ee, int64
     LAUNCH_CHECK();
 }
 
+// VQModel.encode's geometric embedding (stage1/vqgan.py:87-112), added in place to the encoder output h [n, T, D] (NHWC): for image i and latent pixel t
+//   c4 = E_inv[i][:, 3];  d = E_inv[i] [I_inv[i] plane[:, t]; 1];  e[o] = Wimg[o,:].d - Wcam[o,:].c4;  h[i,t,:] += e / (|e| + 1e-7)
+// The arithmetic of camera_embed_kernel (embed.hip), four-term products as ((a+b)+c)+d.  One wave per latent pixel, four pixels per block: no LDS, no barrier; lane l
+// keeps channels l, l + 64, ... (NV of them, those >= D idle: D = 32 leaves half a wave without work) in registers between the sum of squares and the add, so h is read
+// and written once.  The wave index goes through readfirstlane, which makes pixel, image and with them the loads of the matrices and the plane scalar.
+template <int NV>
+__global__ __launch_bounds__(256) void vq_geo_embed_kernel(float* __restrict__ h, const float* __restrict__ I_inv, const float* __restrict__ E_inv,
+                                                           const float* __restrict__ plane, const float* __restrict__ Wimg, const float* __restrict__ Wcam, long pixels,
+                                                           int T, int D) {
+    const int lane = threadIdx.x & 63;
+    const long pix = (long)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    if (pix >= pixels) return;   // the tail block
+    const long i = (unsigned)pix / (unsigned)T;   // (pixels fits an int: the launcher checks it)
+    const int t = (int)(pix - i * T);
+    const float* Ii = I_inv + i * 9;
+    const float* Ei = E_inv + i * 16;
+    const float c4[4] = {Ei[3], Ei[7], Ei[11], Ei[15]};
+    const float px = plane[t], py = plane[T + t], pz = plane[2 * T + t];
+    float camv[4];
+#pragma unroll
+    for (int r = 0; r < 3; ++r) camv[r] = (Ii[3 * r] * px + Ii[3 * r + 1] * py) + Ii[3 * r + 2] * pz;
+    camv[3] = 1.f;
+    float d[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) d[r] = ((Ei[4 * r] * camv[0] + Ei[4 * r + 1] * camv[1]) + Ei[4 * r + 2] * camv[2]) + Ei[4 * r + 3] * camv[3];
+    float e[NV];
+    float ss = 0.f;
+#pragma unroll
+    for (int k = 0; k < NV; ++k) {
+        const int o = lane + 64 * k;
+        e[k] = 0.f;
+        if (o < D) {
+            const float* wi = Wimg + o * 4;
+            const float* wc = Wcam + o * 4;
+            const float de = ((wi[0] * d[0] + wi[1] * d[1]) + wi[2] * d[2]) + wi[3] * d[3];
+            const float ce = ((wc[0] * c4[0] + wc[1] * c4[1]) + wc[2] * c4[2]) + wc[3] * c4[3];
+            e[k] = de - ce;
+            ss = fmaf(e[k], e[k], ss);
+        }
+    }
+    const float nrm = sqrtf(wave_sum(ss)) + 1e-7f;
+    float* row = h + pix * D;
+#pragma unroll
+    for (int k = 0; k < NV; ++k) {
+        const int o = lane + 64 * k;
+        if (o < D) row[o] += e[k] / nrm;
+    }
+}
+void launch_vq_geo_embed(float* h, const float* I_inv, const float* E_inv, const float* plane, const float* Wimg, const float* Wcam, int n, int T, int D, hipStream_t s) {
+    BG_REQUIRE(n >= 1 && T >= 1 && D >= 32 && D % 32 == 0 && D <= 1024, "vq_geo_embed: D=%d must be a multiple of 32 (at most 1024)", D);
+    const long pixels = (long)n * T;
+    BG_REQUIRE(pixels <= 0x7FFFFFFFL, "vq_geo_embed: %ld latent pixels", pixels);
+    const dim3 grid((int)((pixels + 3) / 4)), block(256);
+    const int nv = (D + 63) / 64;
+    if (nv <= 1) hipLaunchKernelGGL(vq_geo_embed_kernel<1>, grid, block, 0, s, h, I_inv, E_inv, plane, Wimg, Wcam, pixels, T, D);
+    else if (nv <= 2) hipLaunchKernelGGL(vq_geo_embed_kernel<2>, grid, block, 0, s, h, I_inv, E_inv, plane, Wimg, Wcam, pixels, T, D);
+    else if (nv <= 4) hipLaunchKernelGGL(vq_geo_embed_kernel<4>, grid, block, 0, s, h, I_inv, E_inv, plane, Wimg, Wcam, pixels, T, D);
+    else if (nv <= 8) hipLaunchKernelGGL(vq_geo_embed_kernel<8>, grid, block, 0, s, h, I_inv, E_inv, plane, Wimg, Wcam, pixels, T, D);
+    else hipLaunchKernelGGL(vq_geo_embed_kernel<16>, grid, block, 0, s, h, I_inv, E_inv, plane, Wimg, Wcam, pixels, T, D);
+    LAUNCH_CHECK();
+}
+
+// row_err[r] = sum_c (codebook[ids[r]][c] - z[r][c])^2 as direct fp32 differences (|z|^2 - 2 z.e + |e|^2 cancels); one wave per row.  NaN / inf in z propagate into the
+// row's error (the arg-min has already raised BG_ST_NONFINITE_LATENTS for such a row); the id is clamped into the codebook.
+__global__ __launch_bounds__(256) void vq_row_err_kernel(const float* __restrict__ z, const float* __restrict__ codebook, const int64_t* __restrict__ ids,
+                                                         float* __restrict__ row_err, long rows, int n_e, int D) {
+    const int lane = threadIdx.x & 63;
+    const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= rows) return;
+    long id = ids[row];
+    id = id < 0 ? 0 : (id >= n_e ? n_e - 1 : id);
+    float s = 0.f;
+    for (int i = lane; i < D; i += 64) { const float v = codebook[id * D + i] - z[row * D + i]; s = fmaf(v, v, s); }
+    s = wave_sum(s);
+    if (lane == 0) row_err[row] = s;
+}
+void launch_vq_row_err(const float* z, const float* codebook, const int64_t* ids, float* row_err, long rows, int n_e, int D, hipStream_t s) {
+    hipLaunchKernelGGL(vq_row_err_kernel, dim3((int)((rows + 3) / 4)), dim3(256), 0, s, z, codebook, ids, row_err, rows, n_e, D);
+    LAUNCH_CHECK();
+}
+
+// out[0] = scale * sum(x) in a FIXED order, the pattern of mean_fixed_order_kernel (sampler.hip): thread t adds elements t, t + 256, ... in double, then a binary tree over
+// the 256 partial sums; two calls give the same bits.  The codebook loss: scale = (1 + beta) / (rows D), which is the forward value of both the legacy and the corrected
+// formula (stage1/quantize.py:290-295).  One workgroup.
+__global__ __launch_bounds__(256) void vq_loss_fixed_order_kernel(const float* __restrict__ x, long n, double scale, float* __restrict__ out) {
+    __shared__ double sh[256];
+    double acc = 0.0;
+    for (long i = threadIdx.x; i < n; i += 256) acc += (double)x[i];
+    sh[threadIdx.x] = acc;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if ((int)threadIdx.x < o) sh[threadIdx.x] += sh[threadIdx.x + o];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) out[0] = (float)(sh[0] * scale);
+}
+void launch_vq_loss(const float* row_err, long rows, int D, float beta, float* loss, hipStream_t s) {
+    const double scale = (1.0 + (double)beta) / ((double)rows * (double)D);
+    hipLaunchKernelGGL(vq_loss_fixed_order_kernel, dim3(1), dim3(256), 0, s, row_err, rows, scale, loss);
+    LAUNCH_CHECK();
+}
+
 }  // namespace bevgen

@@ -6,7 +6,8 @@
 
 Parameters carry the reference's ``state_dict`` names (encoder.*, decoder.*, quantize.embedding.weight, quant_conv.*, post_quant_conv.*).
 ``decode`` runs the hand-written HIP decoder (bevgen_vq_decode / bevgen_vq_decode_latents); ``encode`` (the step BEFORE the path)
-runs the HIP encoder + arg-min quantizer (bevgen_vq_encode).
+runs the HIP encoder + arg-min quantizer (bevgen_vq_encode / bevgen_vq_encode_ex: the geometric embedding of ``geometric_embedding=True`` and the codebook loss);
+``forward`` / ``log_images`` are the stage-1 reconstruction (encode, then decode).
 """
 from __future__ import annotations
 
@@ -19,6 +20,37 @@ from ... import weights as W
 from ...runtime import Context
 from ..options import RuntimeOptionsMixin
 from ..params import ParamNode, build_tree, module_device
+
+
+DENORM_MEAN, DENORM_STD = (0.4265, 0.4489, 0.4769), (0.2053, 0.2206, 0.2578)   # bev_utils/util.py:99-100
+
+
+def denormalize_tensor(x: torch.Tensor) -> torch.Tensor:
+    """bev_utils/util.py:97-118 (keep_tensor=True): per-channel x*std+mean, clamp [0,1]; [n, 3, H, W]."""
+    mean = torch.tensor(DENORM_MEAN, device=x.device, dtype=x.dtype).view(1, 3, 1, 1)
+    std = torch.tensor(DENORM_STD, device=x.device, dtype=x.dtype).view(1, 3, 1, 1)
+    return torch.clamp(x * std + mean, 0, 1)
+
+
+def image_plane(cam_latent_res, cam_res) -> torch.Tensor:
+    """vqgan:20-28, 59-66 on the host: [1, 1, 3, h, w] with x = linspace(0, 1, w) * image_width, y = linspace(0, 1, h) * image_height, 1, where
+    (h, w) = cam_latent_res and (image_height, image_width) = cam_res.  (The stage-2 transformers build their plane with the two sides of cam_res the other way round.)"""
+    h, w = int(cam_latent_res[0]), int(cam_latent_res[1])
+    image_height, image_width = cam_res
+    plane = torch.ones(3, h, w)
+    plane[0] = (torch.linspace(0, 1, w) * image_width)[None, :]
+    plane[1] = (torch.linspace(0, 1, h) * image_height)[:, None]
+    return plane[None, None]
+
+
+def geometry_rows(m: torch.Tensor, k: int, n: int) -> torch.Tensor:
+    """batch['intrinsics_inv'] (k = 3) / ['extrinsics_inv'] (k = 4) as one k x k matrix per image row: [B, cam, k, k] -> [(B cam), k, k]; [(B cam), k, k] stays."""
+    if m.dim() not in (3, 4) or tuple(m.shape[-2:]) != (k, k):
+        raise ValueError(f"geometry of shape {tuple(m.shape)}: expected [B, cam, {k}, {k}] or [(B cam), {k}, {k}]")
+    m = m.reshape(-1, k, k)
+    if m.shape[0] != n:
+        raise ValueError(f"{m.shape[0]} {k}x{k} matrices for {n} images: the geometry has one matrix per (batch, camera) row of the input")
+    return m.float()
 
 
 class VectorQuantizer2(ParamNode):
@@ -45,8 +77,7 @@ class VQModel(RuntimeOptionsMixin, nn.Module):
         super().__init__()
         self._ctx: Optional[Context] = None
         self._init_runtime_options(kwargs)    # precision / weights (bevgen_amd/modules/options.py)
-        if geometric_embedding:
-            raise NotImplementedError("geometric_embedding=True is not used by the released checkpoints (configs/model/stage_2_argoverse.yaml:8,11)")
+        self.geometric_embedding = bool(geometric_embedding)
         self.ddconfig = dict(ddconfig)
         self.ddconfig["ch_mult"] = list(self.ddconfig["ch_mult"])
         self.ddconfig["attn_resolutions"] = list(self.ddconfig["attn_resolutions"])
@@ -57,8 +88,22 @@ class VQModel(RuntimeOptionsMixin, nn.Module):
         self.image_key = image_key
         self.denormalize = denormalize
         self.quantize = VectorQuantizer2(n_embed, embed_dim, beta=0.25, remap=remap, sane_index_shape=sane_index_shape, legacy=legacy)
-        shapes = W.vqmodel_shapes(self.ddconfig, n_embed, embed_dim, with_encoder=True)
+        if self.geometric_embedding:
+            # vqgan:59-69.  img_embed / cam_embed map 4 -> cam_emd_dim channels and their output is added to the encoder's z_channels (`h_flat += img_embed`, vqgan:111)
+            if cam_emd_dim != self.ddconfig["z_channels"]:
+                raise ValueError(f"geometric_embedding=True needs cam_emd_dim == ddconfig['z_channels'] (got {cam_emd_dim} and {self.ddconfig['z_channels']}): "
+                                 "the embedding is added to the encoder output")
+            if self.cam_res is None or self.cam_latent_res is None:
+                raise ValueError("geometric_embedding=True needs cam_res and cam_latent_res (the image plane is built from them)")
+            self.register_buffer("image_plane", image_plane(self.cam_latent_res, self.cam_res), persistent=False)
+        shapes = W.vqmodel_shapes(self.ddconfig, n_embed, embed_dim, with_encoder=True, geometric=self.geometric_embedding)
         build_tree(self, shapes)
+        # children in the order the reference constructor creates them (encoder, decoder, [img_embed, cam_embed,] quantize, quant_conv, post_quant_conv): state_dict order
+        order = list(dict.fromkeys(k.split(".")[0] for k in shapes))
+        mods = dict(self._modules)
+        self._modules.clear()
+        for name in order + [m for m in mods if m not in order]:
+            self._modules[name] = mods[name]
         for name, p in self.named_parameters():
             if p.dim() >= 2:
                 nn.init.kaiming_uniform_(p, a=5 ** 0.5)
@@ -107,21 +152,68 @@ class VQModel(RuntimeOptionsMixin, nn.Module):
     def decode_code(self, code_b):
         return self.decode_ids(code_b.reshape(code_b.shape[0], -1))
 
+    def _geometry(self, x, batch):
+        """geometric_embedding=True: (I_inv [n, 3, 3], E_inv [n, 4, 4], plane [3, h*w]) for the n rows of x out of batch['intrinsics_inv'] / ['extrinsics_inv']
+        ([B, cam, ., .] as vqgan:90-91 rearranges them, or already [(B cam), ., .]); else three Nones (the batch is ignored, as in the reference)."""
+        if not self.geometric_embedding:
+            return None, None, None
+        if batch is None or "intrinsics_inv" not in batch or "extrinsics_inv" not in batch:
+            raise ValueError("VQModel(geometric_embedding=True).encode needs batch['intrinsics_inv'] and batch['extrinsics_inv']")
+        n = x.shape[0]
+        I_inv, E_inv = geometry_rows(batch["intrinsics_inv"], 3, n), geometry_rows(batch["extrinsics_inv"], 4, n)
+        f = 2 ** (len(self.ddconfig["ch_mult"]) - 1)
+        if (x.shape[-2] // f, x.shape[-1] // f) != tuple(self.image_plane.shape[-2:]):
+            raise ValueError(f"input {tuple(x.shape[-2:])} does not give the latent grid {tuple(self.image_plane.shape[-2:])} of the image plane (cam_latent_res)")
+        return I_inv, E_inv, self.image_plane.reshape(3, -1)
+
     @torch.no_grad()
-    def encode_ids(self, x):
-        """Encoder -> quant_conv -> arg-min over the codebook: x [n, in_channels, H, W] -> ids [n, h*w]."""
-        return self.context().vq_encode(x)
+    def encode_ids(self, x, batch=None):
+        """Encoder (-> + geometric embedding) -> quant_conv -> arg-min over the codebook: x [n, in_channels, H, W] -> ids [n, h*w]."""
+        if not self.geometric_embedding:
+            return self.context().vq_encode(x)
+        geo = self._geometry(x, batch)
+        return self.context().vq_encode_ex(x, *geo, want_loss=False)[0]
 
     @torch.no_grad()
     def encode(self, x, batch=None):
-        """vqgan:84-116 (geometric_embedding=False) -> (quant [n, e, h, w], emb_loss=None, (None, None, indices [n*h*w]))."""
-        ids = self.encode_ids(x)
+        """vqgan:84-116 -> (quant [n, e, h, w], emb_loss (0-dim, on the device), (None, None, indices [n*h*w])).  emb_loss is the forward value of the quantizer's loss
+        (quant:290-295, the same number with legacy True and False).  quant holds the looked-up codebook rows z_q; the reference returns z + (z_q - z) (its
+        straight-through estimator, quant:298), which differs from z_q by at most an ulp of z."""
+        geo = self._geometry(x, batch)
+        ids, _, emb_loss = self.context().vq_encode_ex(x, *geo, beta=self.quantize.beta)
         f = 2 ** (len(self.ddconfig["ch_mult"]) - 1)
         quant = self.quantize.get_codebook_entry(ids.reshape(-1), (x.shape[0], x.shape[-2] // f, x.shape[-1] // f, self.embed_dim))
-        return quant, None, (None, None, ids.reshape(-1))
+        return quant, emb_loss, (None, None, ids.reshape(-1))
 
+    @torch.no_grad()
     def forward(self, input, batch=None):
-        raise NotImplementedError("stage-1 training/reconstruction forward is outside the stage-2 sampling path")
+        """vqgan:128-131 -> (dec [n, out_ch, H, W], diff = emb_loss): encode, then the fused codebook lookup + decoder on the ids."""
+        _, diff, info = self.encode(input, batch)
+        f = 2 ** (len(self.ddconfig["ch_mult"]) - 1)
+        dec = self.decode_ids(info[2].reshape(input.shape[0], -1), latent_hw=(input.shape[-2] // f, input.shape[-1] // f))
+        return dec, diff
+
+    def get_input(self, batch, k):
+        """vqgan:133-143: channel-last batch[k] -> [n, C, H, W] float; [B, H, W] gains a channel, [B, cam, H, W, C] becomes (B cam) rows (the reference squeezes, which is
+        that for B = 1)."""
+        x = batch[k]
+        if x.dim() == 3:
+            x = x[..., None]
+        elif x.dim() == 5:
+            x = x.reshape(-1, *x.shape[2:])
+        return x.permute(0, 3, 1, 2).contiguous().float()
+
+    @torch.no_grad()
+    def log_images(self, batch, **kwargs):
+        """vqgan:177-199 -> {'inputs', 'reconstructions'} [n, 3, H, W], denormalised to [0, 1] when self.denormalize (the geometric model takes its geometry from
+        `batch`, as forward does: the reference's own geometric branch unpacks three values from get_input and cannot run)."""
+        x = self.get_input(batch, self.image_key).to(module_device(self))
+        if x.shape[1] > 3:
+            raise NotImplementedError("log_images of inputs with more than 3 channels goes through to_rgb (vqgan:201-213), which is visualisation only")
+        xrec, _ = self(x, batch)
+        if self.denormalize:
+            x, xrec = denormalize_tensor(x), denormalize_tensor(xrec)
+        return {"inputs": x, "reconstructions": xrec}
 
 
 class VQSegmentationModel(VQModel):

@@ -85,7 +85,7 @@ class Net2NetTransformer(_Base):
                 z = batch["z_ids"].to(ctx.device)
             else:
                 img = batch[self.first_stage_key].to(ctx.device).float().movedim(-1, -3)
-                z = self.first_stage_model.encode_ids(img.reshape(-1, *img.shape[-3:]))
+                z = self.first_stage_model.encode_ids(img.reshape(-1, *img.shape[-3:]), batch)
             idx = partial_decoding_idx.tolist() if isinstance(partial_decoding_idx, torch.Tensor) else list(partial_decoding_idx)
             forced = partial_forced_ids(cfg, idx, z.reshape(B, cfg.num_cams, cfg.num_cam_tokens))
         if sample and noise_u is None:

@@ -19,7 +19,7 @@ from typing import Optional
 import torch
 import torch.nn as nn
 
-from ...modules.stage1.vqgan import VQModel
+from ...modules.stage1.vqgan import DENORM_MEAN, DENORM_STD, VQModel, denormalize_tensor  # noqa: F401 (one copy of util.denormalize_tensor, re-exported)
 from ..options import pop_runtime_options
 from .muse_maskgit_pytorch import MaskGit
 
@@ -31,16 +31,6 @@ try:  # keep the LightningModule base when Lightning is installed so that `train
     _Base = pl.LightningModule
 except Exception:  # pragma: no cover - Lightning is absent from the build image
     _Base = nn.Module
-
-DENORM_MEAN = (0.4265, 0.4489, 0.4769)
-DENORM_STD = (0.2053, 0.2206, 0.2578)
-
-
-def denormalize_tensor(x: torch.Tensor) -> torch.Tensor:
-    """bev_utils/util.py:97-118 (keep_tensor=True): per-channel x*std+mean, clamp [0,1]; [B,3,H,W]."""
-    mean = torch.tensor(DENORM_MEAN, device=x.device, dtype=x.dtype).view(1, 3, 1, 1)
-    std = torch.tensor(DENORM_STD, device=x.device, dtype=x.dtype).view(1, 3, 1, 1)
-    return torch.clamp(x * std + mean, 0, 1)
 
 
 class Net2NetTransformer(_Base):

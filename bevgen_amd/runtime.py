@@ -408,6 +408,31 @@ class Context:
         self._done(check)
         return ids
 
+    def vq_encode_ex(self, x, I_inv=None, E_inv=None, plane=None, beta=0.25, want_loss=True, check=True):
+        """vq_encode with the geometric embedding of a camera VQGAN and the quantizer's error -> (ids [n, h*w], row_err [n, h*w], loss 0-dim or None).
+        I_inv [n, 3, 3], E_inv [n, 4, 4] (one per image) and plane [3, h*w] go together: a context loaded with img_embed / cam_embed needs them, one without refuses them
+        (BevgenError).  row_err = |codebook[id] - z|^2 per latent row; loss = (1 + beta) mean(row_err) / embed_dim over all rows, accumulated in double in a fixed order."""
+        dd = self.vq_ddconfig
+        x = _req(x, torch.float32, self.device, "x")
+        n, ch, H, W = x.shape
+        f = 1 << self._vq_levels()
+        if ch != dd["in_channels"] or H % f or W % f:
+            raise ValueError(f"vq_encode_ex: input {tuple(x.shape)} needs {dd['in_channels']} channels and sides divisible by {f}")
+        T = (H // f) * (W // f)
+        geo = [I_inv, E_inv, plane]
+        if any(g is not None for g in geo):
+            if any(g is None for g in geo):
+                raise ValueError("vq_encode_ex: I_inv, E_inv and plane go together")
+            I_inv, E_inv, plane = (_req(g, torch.float32, self.device, "geometry") for g in geo)
+            if tuple(I_inv.shape) != (n, 3, 3) or tuple(E_inv.shape) != (n, 4, 4) or plane.numel() != 3 * T:
+                raise ValueError(f"vq_encode_ex: geometry {tuple(I_inv.shape)}, {tuple(E_inv.shape)}, {tuple(plane.shape)} does not fit {n} images of {T} latent pixels")
+        ids = torch.empty((n, T), dtype=torch.int64, device=self.device)
+        row_err = torch.empty((n, T), dtype=torch.float32, device=self.device)
+        loss = torch.empty((), dtype=torch.float32, device=self.device) if want_loss else None
+        self._check(self.lib.bevgen_vq_encode_ex(self._h, _ptr(x), n, H, W, _ptr(I_inv), _ptr(E_inv), _ptr(plane), float(beta), _ptr(ids), _ptr(row_err), _ptr(loss), self._s()))
+        self._done(check)
+        return ids, row_err, loss
+
     def vq_decode_latents(self, zq, denormalize=False, check=True):
         """VQModel.decode(quant): zq [n, embed_dim, h, w] fp32."""
         dd = self.vq_ddconfig
@@ -691,6 +716,20 @@ class Context:
         ee = torch.empty((n_e,), dtype=torch.float32, device=self.device) if want_norms else None
         self._check(self.lib.bevgen_op_vq_quantize(self._h, _ptr(z), _ptr(codebook), _ptr(ids), _ptr(zz), _ptr(ee), rows, n_e, D, self._s()))
         return (ids, zz, ee) if want_norms else ids
+
+    def op_vq_geo_embed(self, h, I_inv, E_inv, plane, wimg, wcam):
+        """h [n, T, D] (in place) += normalize(wimg d - wcam c) per latent pixel: I_inv [n, 3, 3], E_inv [n, 4, 4], plane [3, T], wimg / wcam [D, 4]; D % 32 == 0."""
+        n, T, D = h.shape
+        self._check(self.lib.bevgen_op_vq_geo_embed(self._h, _ptr(h), _ptr(I_inv), _ptr(E_inv), _ptr(plane), _ptr(wimg), _ptr(wcam), n, T, D, self._s()))
+
+    def op_vq_quant_error(self, z, codebook, ids, beta=0.25, want_loss=True):
+        """(row_err [rows] = |codebook[ids] - z|^2, loss 0-dim = (1 + beta) / (rows D) sum(row_err) in a fixed order, or None): z [rows, D], codebook [n_e, D], ids [rows]."""
+        rows, D = z.shape
+        n_e = codebook.shape[0]
+        row_err = torch.empty((rows,), dtype=torch.float32, device=self.device)
+        loss = torch.empty((), dtype=torch.float32, device=self.device) if want_loss else None
+        self._check(self.lib.bevgen_op_vq_quant_error(self._h, _ptr(z), _ptr(codebook), _ptr(ids), float(beta), _ptr(row_err), _ptr(loss), rows, n_e, D, self._s()))
+        return row_err, loss
 
     def op_conv_ranged(self, x_nhwc, w_oihw, bias, kind, check=True):
         """precision='f16x3' / 'f16x3r' contexts: one site of the range-safe mode as vq_decode / vq_encode run it -> (y, e): e (a one-element int32 tensor) is the exponent

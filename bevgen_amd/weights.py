@@ -234,12 +234,16 @@ def vq_encoder_shapes(dd: Mapping) -> "OrderedDict[str, Shape]":
     return s
 
 
-def vqmodel_shapes(dd: Mapping, n_embed: int, embed_dim: int, *, with_encoder: bool = True) -> "OrderedDict[str, Shape]":
-    """Keys of ``VQModel`` (stage1/vqgan.py:31-80): encoder.*, decoder.*, quantize.embedding, quant_conv, post_quant_conv."""
+def vqmodel_shapes(dd: Mapping, n_embed: int, embed_dim: int, *, with_encoder: bool = True, geometric: bool = False) -> "OrderedDict[str, Shape]":
+    """Keys of ``VQModel`` (stage1/vqgan.py:31-80): encoder.*, decoder.*, quantize.embedding, quant_conv, post_quant_conv; geometric (geometric_embedding=True,
+    vqgan.py:62-69): img_embed / cam_embed (1x1 convolutions of 4 -> cam_emd_dim = z_channels channels, no bias) where the constructor creates them, after decoder.*."""
     s: "OrderedDict[str, Shape]" = OrderedDict()
     if with_encoder:
         s.update(vq_encoder_shapes(dd))
     s.update(vq_decoder_shapes(dd))
+    if geometric:
+        s["img_embed.weight"] = (dd["z_channels"], 4, 1, 1)
+        s["cam_embed.weight"] = (dd["z_channels"], 4, 1, 1)
     s["quantize.embedding.weight"] = (n_embed, embed_dim)
     if with_encoder:
         s["quant_conv.weight"] = (embed_dim, dd["z_channels"], 1, 1)

@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define BEVGEN_ABI_VERSION 10   /* 10: bevgen_cfg.vq_range covers bevgen_vq_encode (bevgen_vq_range_exponents reports the most recent decode OR encode call), bevgen_op_conv_ranged.  9: operator entries of the VQGAN building blocks (bevgen_op_conv3x3_down, _vq_attn_block, _vq_out_tail, _vq_quantize, _conv3x3_gn_stats), BEVGEN_STATUS_NONFINITE_LATENTS.  8: bevgen_cfg.vq_range (taken out of reserved[]: the struct size is unchanged), bevgen_vq_range_exponents, bevgen_op_range_split.  7: operator entries of the token samplers (bevgen_op_remask, _maskgit_pick, _critic_scores, _ar_pick, _ar_score_rows, _mean_fixed_order).  6: device status word (bevgen_synchronize, bevgen_status, BEVGEN_ERR_NUMERIC, BEVGEN_STATUS_*).  5: bevgen_op_mlp_fused; a context without max_batch <= 4 packs the split decode layer lazily (see Conventions).  4: 4: BEVGEN_PROFILE_KINDS 5 -> 6 (bevgen_profile_end writes 18 doubles), bevgen_cfg.decode_chains, decode_path values 2 / 3 */
+#define BEVGEN_ABI_VERSION 10   /* 10 (additive, same version and struct): bevgen_vq_encode_ex, bevgen_op_vq_geo_embed, bevgen_op_vq_quant_error; a library without them is told apart by the missing symbols.  10: bevgen_cfg.vq_range covers bevgen_vq_encode (bevgen_vq_range_exponents reports the most recent decode OR encode call), bevgen_op_conv_ranged.  9: operator entries of the VQGAN building blocks (bevgen_op_conv3x3_down, _vq_attn_block, _vq_out_tail, _vq_quantize, _conv3x3_gn_stats), BEVGEN_STATUS_NONFINITE_LATENTS.  8: bevgen_cfg.vq_range (taken out of reserved[]: the struct size is unchanged), bevgen_vq_range_exponents, bevgen_op_range_split.  7: operator entries of the token samplers (bevgen_op_remask, _maskgit_pick, _critic_scores, _ar_pick, _ar_score_rows, _mean_fixed_order).  6: device status word (bevgen_synchronize, bevgen_status, BEVGEN_ERR_NUMERIC, BEVGEN_STATUS_*).  5: bevgen_op_mlp_fused; a context without max_batch <= 4 packs the split decode layer lazily (see Conventions).  4: 4: BEVGEN_PROFILE_KINDS 5 -> 6 (bevgen_profile_end writes 18 doubles), bevgen_cfg.decode_chains, decode_path values 2 / 3 */
 
 enum { BEVGEN_ROUTE_MASKGIT = 0, BEVGEN_ROUTE_AR = 1 };
 /* FP32  : every product and accumulation in exact fp32 on the matrix cores (v_mfma_f32_32x32x2_f32) - bit-exact greedy tokens vs the CPU reference.
@@ -286,6 +286,19 @@ int bevgen_vq_decode(bevgen_ctx* ctx, const int64_t* d_ids, int n, int lat_h, in
  * This is encode_to_c (BEV segmentation -> condition tokens) and encode_to_z (muse_lm:142-155). */
 int bevgen_vq_encode(bevgen_ctx* ctx, const float* d_x, int n, int H, int W, int64_t* d_ids, void* stream);
 
+/* bevgen_vq_encode with the two things a stage-1 checkpoint is judged by (bevgen_vq_encode forwards here with NULLs):
+ *  - the geometric embedding of a camera VQGAN (stage1/vqgan.py:87-112, geometric_embedding=True): a context loaded with img_embed.weight and cam_embed.weight
+ *    ([z_channels, 4, 1, 1], no bias; exactly one of the two, or another shape, fails bevgen_finalize) adds normalize(Wimg d - Wcam c) (d = E_inv [I_inv pix; 1],
+ *    c = E_inv[:, 3], norm + 1e-7) to the encoder output in front of quant_conv (and of quant_conv's range-safe site, whose exponent is chosen from the sum).
+ *    d_I_inv [n, 3, 3], d_E_inv [n, 4, 4] per image, d_plane [3, h*w] (x = linspace(0,1,w) image_width, y = linspace(0,1,h) image_height, 1).  Such a context REQUIRES
+ *    the three pointers and a context without the two weights REFUSES them (BEVGEN_ERR_INVALID): the embedding is never skipped silently.
+ *  - the quantizer's error: d_row_err [n, h*w] (or NULL) = |codebook[id] - z|^2 per latent row as direct fp32 differences, and d_loss (one float, or NULL; needs
+ *    d_row_err, which belongs to the caller because the workspace is reset per pass of 48 images) = (1 + beta) / (n h w embed_dim) * sum(row_err), the forward value
+ *    of VectorQuantizer2's loss in both its legacy and corrected form (stage1/quantize.py:290-295), accumulated in double in a fixed order once over all rows of the call
+ *    (bit-reproducible).  NaN / inf latents propagate into row_err and the loss; BEVGEN_STATUS_NONFINITE_LATENTS is raised by the arg-min as before. */
+int bevgen_vq_encode_ex(bevgen_ctx* ctx, const float* d_x, int n, int H, int W, const float* d_I_inv /* or NULL */, const float* d_E_inv /* or NULL */,
+                        const float* d_plane /* or NULL */, float beta, int64_t* d_ids, float* d_row_err /* or NULL */, float* d_loss /* or NULL */, void* stream);
+
 /* VQModel.decode(quant) (stage1/vqgan.py:118-121) for already looked-up latents: d_zq [n, embed_dim, lat_h, lat_w] (NCHW, like the reference). */
 int bevgen_vq_decode_latents(bevgen_ctx* ctx, const float* d_zq, int n, int lat_h, int lat_w, int out_mode, void* d_out, void* stream);
 
@@ -415,6 +428,15 @@ int bevgen_op_vq_out_tail(bevgen_ctx* ctx, const float* d_x_nhwc, const float* d
  * D % 32 == 0; d_zz [rows] / d_ee [n_e] (or NULL) receive the squared norms.  A row without a finite distance gets id 0 and raises BEVGEN_STATUS_NONFINITE_LATENTS. */
 int bevgen_op_vq_quantize(bevgen_ctx* ctx, const float* d_z, const float* d_codebook, int64_t* d_ids, float* d_zz /* or NULL */, float* d_ee /* or NULL */, long rows, int n_e,
                           int D, void* stream);
+/* vq_geo_embed: the geometric embedding of bevgen_vq_encode_ex on a caller tensor, in place: d_h [n, T, D] += normalize(Wimg d - Wcam c) per latent pixel; d_I_inv [n, 3, 3],
+ * d_E_inv [n, 4, 4], d_plane [3, T], d_wimg / d_wcam [D, 4]; D % 32 == 0, D <= 1024.  fp32 in every precision mode.  One wave per pixel: h is read and written once. */
+int bevgen_op_vq_geo_embed(bevgen_ctx* ctx, float* d_h, const float* d_I_inv, const float* d_E_inv, const float* d_plane, const float* d_wimg, const float* d_wcam, int n, int T,
+                           int D, void* stream);
+/* vq_quant_error: d_row_err[r] = sum_c (d_codebook[d_ids[r]][c] - d_z[r][c])^2 (direct fp32 differences, ids clamped into [0, n_e)) and, with d_loss non-NULL,
+ * d_loss[0] = (1 + beta) / (rows D) * sum(row_err) in double, fixed order.  D % 32 == 0.  Reads z once and the gathered codebook rows.  A NaN in z gives a NaN row_err
+ * of that row only. */
+int bevgen_op_vq_quant_error(bevgen_ctx* ctx, const float* d_z, const float* d_codebook, const int64_t* d_ids, float beta, float* d_row_err, float* d_loss /* or NULL */,
+                             long rows, int n_e, int D, void* stream);
 /* conv3x3_gn_stats (precision = F16X3 contexts): the LDS-DMA 3x3 convolution (stride 1, padding 1) on (hi, lo) planes of d_x whose epilogue leaves the GroupNorm(32) partial sums
  * of its output, d_part [n H W / 32][Cout / 4][2] fp32 (sum, sum of squares), and the statistics made of them, d_stats [n, 32, 2] = (mean, rstd) at eps 1e-6.
  * range_route != 0: the form of the range-safe mode instead (convolution without the bias, then the bias + statistics pass at exponent 0).  H W % 256 == 0 and
