@@ -101,6 +101,9 @@ SIGNATURES = {
     "bevgen_op_conv3x3_down": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _p]),
     "bevgen_op_vq_attn_block": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p]),
     "bevgen_op_vq_out_tail": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _p, _i, _i, _i, _i, _p]),
+    "bevgen_op_vq_out_tail_ex": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _p, _i, _i, _i, _i, _i, _p]),
+    "bevgen_op_bce_logits": (_i, [_p, _p, _p, _l, _p, _f, _p, _p]),
+    "bevgen_op_seg_colorize": (_i, [_p, _p, _p, _i, _p, _i, _i, _i, _i, _p]),
     "bevgen_op_vq_quantize": (_i, [_p, _p, _p, _p, _p, _p, _l, _i, _i, _p]),
     "bevgen_op_vq_geo_embed": (_i, [_p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _p]),
     "bevgen_op_vq_quant_error": (_i, [_p, _p, _p, _p, _f, _p, _p, _l, _i, _i, _p]),

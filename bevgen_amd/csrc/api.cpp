@@ -824,7 +824,33 @@ int bevgen_op_vq_out_tail(bevgen_ctx* ctx, const float* x, const float* norm_w, 
                           int out_mode, int three_kernels, void* out, int n, int H, int W, int C, void* stream) {
     return guarded(ctx, [&] {
         BG_REQUIRE(x && norm_w && norm_b && w && out, "op_vq_out_tail: null argument");
-        vq_op_out_tail(*ctx, x, norm_w, norm_b, w, bias, mean, stdv, out_mode, three_kernels, out, n, H, W, C, (hipStream_t)stream);
+        vq_op_out_tail(*ctx, x, norm_w, norm_b, w, bias, mean, stdv, out_mode, three_kernels, out, n, H, W, C, 3, (hipStream_t)stream);
+    });
+}
+
+int bevgen_op_vq_out_tail_ex(bevgen_ctx* ctx, const float* x, const float* norm_w, const float* norm_b, const float* w, const float* bias, const float* mean, const float* stdv,
+                             int out_mode, int three_kernels, void* out, int n, int H, int W, int C, int cout, void* stream) {
+    return guarded(ctx, [&] {
+        BG_REQUIRE(x && norm_w && norm_b && w && out, "op_vq_out_tail: null argument");
+        vq_op_out_tail(*ctx, x, norm_w, norm_b, w, bias, mean, stdv, out_mode, three_kernels, out, n, H, W, C, cout, (hipStream_t)stream);
+    });
+}
+
+int bevgen_op_bce_logits(bevgen_ctx* ctx, const float* logits, const float* target, long count, const float* qloss, float codebook_weight, float* out, void* stream) {
+    return guarded(ctx, [&] {
+        BG_REQUIRE(logits && target && out && count >= 1, "op_bce_logits: bad arguments");
+        double* partial;
+        ctx->arena.carve([&](Arena& ar) { partial = ar.get<double>((size_t)bce_logits_blocks(count)); });
+        launch_bce_logits(logits, target, count, qloss, codebook_weight, partial, out, (hipStream_t)stream);
+    });
+}
+
+int bevgen_op_seg_colorize(bevgen_ctx* ctx, const float* x, const float* colorize, int threshold, float* rgb, int n, int C, int H, int W, void* stream) {
+    return guarded(ctx, [&] {
+        BG_REQUIRE(x && colorize && rgb && x != rgb, "op_seg_colorize: null argument (or the output aliases the input)");
+        unsigned* minmax;
+        ctx->arena.carve([&](Arena& ar) { minmax = ar.get<unsigned>(2); });
+        launch_seg_colorize(x, colorize, threshold, rgb, n, C, H, W, minmax, (hipStream_t)stream);
     });
 }
 

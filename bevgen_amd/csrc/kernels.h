@@ -435,6 +435,15 @@ void launch_range_unscale_amax(float* y, const float* bias, long rows, int C, co
 void launch_nchw_to_nhwc_pad_amax(const float* x, float* y, int n, int hw, int C, int Cpad /* % 4 == 0 */, unsigned* amax, int* e, hipStream_t s);
 void launch_row_softmax(float* x, int rows, int cols, float scale, hipStream_t s, int ld = 0 /* row stride (0 = cols); columns [cols, ld) are zero-filled */);
 
+// ---------------------------------------------------------------- vqseg_kernels.hip (the stage-1 BEV segmentation model's loss and visualisation)
+// out[0] = mean_i ( max(x,0) - x t + log1p(exp(-|x|)) ): fp32 per element, double sum in a fixed order; qloss non-null: out[1] = out[0] + codebook_weight * qloss[0] (fp32)
+// partial: bce_logits_blocks(count) doubles of workspace
+int bce_logits_blocks(long count);
+void launch_bce_logits(const float* logits, const float* target, long count, const float* qloss /*or null*/, float codebook_weight, double* partial, float* out /*[2]*/,
+                       hipStream_t s);
+// rgb [n, 3, H, W] = minmax-normalised (whole tensor) projection colorize [3, C] of x [n, C, H, W], or of (x > 0) with threshold; minmax: two words of workspace; C <= 32
+void launch_seg_colorize(const float* x, const float* colorize, int threshold, float* rgb, int n, int C, int H, int W, unsigned* minmax, hipStream_t s);
+
 // misc
 void launch_fill(float* p, long n, float v, hipStream_t s);
 void launch_add(const float* a, const float* b, float* c, long n, hipStream_t s);

@@ -232,7 +232,7 @@ void vq_op_conv3x3_down(Ctx& c, const float* x, const float* w, const float* bia
 void vq_op_attn_block(Ctx& c, const float* x, const float* norm_w, const float* norm_b, const float* wq, const float* bq, const float* wk, const float* bk, const float* wv,
                       const float* bv, const float* wp, const float* bp, float* y, int n, int h, int w, int C, hipStream_t s);
 void vq_op_out_tail(Ctx& c, const float* x, const float* norm_w, const float* norm_b, const float* w, const float* bias, const float* mean, const float* stdv, int out_mode,
-                    int three_kernels, void* out, int n, int H, int W, int C, hipStream_t s);
+                    int three_kernels, void* out, int n, int H, int W, int C, int cout, hipStream_t s);   // w [cout][C][3][3]; out_mode 1 / 2 need cout == 3
 void vq_op_quantize(Ctx& c, const float* z, const float* codebook, int64_t* ids, float* zz_out, float* ee_out, long rows, int n_e, int D, hipStream_t s);
 void vq_op_conv3x3_gn_stats(Ctx& c, const float* x, const float* w, const float* bias, int range_route, float* y, float* part, float* stats, int n, int H, int W, int Cin,
                             int Cout, hipStream_t s);

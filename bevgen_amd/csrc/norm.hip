@@ -393,7 +393,9 @@ __global__ void groupnorm_finalize_kernel(const double* __restrict__ part, float
     double var = b / count - mean * mean;
     if (var < 0) var = 0;
     stats[2 * i] = (float)mean;
-    stats[2 * i + 1] = (float)(1.0 / sqrt(var + (double)eps));
+    // A group of ONE value (32 channels at a 1 x 1 image) normalises to beta whatever the value is: x - mean = 0.  rstd = eps^-1/2 = 1000 would multiply the rounding of
+    // the apply pass's shift beta - mean rstd gamma by 1000 (measured 2.8e-5 at the decoder tail against its bound 2.0e-6); rstd = 0 gives beta exactly in every form.
+    stats[2 * i + 1] = count == 1.0 ? 0.f : (float)(1.0 / sqrt(var + (double)eps));
 }
 
 size_t groupnorm_ws_bytes(int n, int hw) { return (size_t)n * cdiv(hw, GN_PIX_PER_BLOCK) * GN_GROUPS * 2 * sizeof(double); }

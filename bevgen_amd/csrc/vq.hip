@@ -125,12 +125,18 @@ __global__ __launch_bounds__(256) void vq_out_conv_kernel(const float* __restric
     }
 }
 
-bool vq_out_conv_supported(int C, int cout) { return cout == 3 && C % 32 == 0 && C >= 32; }
+// COUT is a template argument (the accumulators live in registers, the weight addresses are wave-uniform): 3 = the camera decoder, 7 = the BEV segmentation decoder
+// (stage_1_bev.yaml: out_ch 7).  Compiler's resource report: <3> 57 VGPRs, <7> 81 VGPRs, both 3 waves / SIMD (the 46.6 KB tile is the limit), no scratch and no
+// VGPR spill; <7> parks 73 SGPRs (its 7 x 9 wave-uniform weight rows) in VGPR lanes, <3> 3.  Any other count takes the three-kernel tail.
+bool vq_out_conv_supported(int C, int cout) { return (cout == 3 || cout == 7) && C % 32 == 0 && C >= 32; }
 
 void launch_vq_out_conv(const float* x, const float* stats, const float* gamma, const float* beta, const float* wgt, const float* bias, const float* mean, const float* stdv, int clamp01,
                         float* y, uint8_t* y8, int n, int H, int W, int C, int cout, hipStream_t s) {
     BG_REQUIRE(vq_out_conv_supported(C, cout), "vq_out_conv: C=%d cout=%d", C, cout);
-    hipLaunchKernelGGL((vq_out_conv_kernel<3>), dim3(cdiv(W, OC_T), cdiv(H, OC_T), n), dim3(256), 0, s, x, stats, gamma, beta, wgt, bias, mean, stdv, clamp01, y, y8, H, W, C, status_current());
+    if (cout == 3)
+        hipLaunchKernelGGL((vq_out_conv_kernel<3>), dim3(cdiv(W, OC_T), cdiv(H, OC_T), n), dim3(256), 0, s, x, stats, gamma, beta, wgt, bias, mean, stdv, clamp01, y, y8, H, W, C, status_current());
+    else
+        hipLaunchKernelGGL((vq_out_conv_kernel<7>), dim3(cdiv(W, OC_T), cdiv(H, OC_T), n), dim3(256), 0, s, x, stats, gamma, beta, wgt, bias, mean, stdv, clamp01, y, y8, H, W, C, status_current());
     LAUNCH_CHECK();
 }
 

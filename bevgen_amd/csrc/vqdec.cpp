@@ -146,7 +146,7 @@ struct RangedOpts {
     const int* e = nullptr;       // the exponent, where the caller has one; null: the next slot (range_exponent)
 };
 
-// the decoder's last step: out_mode as in vq_decode; mean / stdv are read for out_mode != 0 only; img: [n, h w, 4] scratch of the three-kernel form
+// the decoder's last step: out_mode as in vq_decode; mean / stdv are read for out_mode != 0 only; img: [n, h w, max(4, cout)] scratch of the three-kernel form
 struct TailOut { void* out; int out_mode; const float *mean, *stdv; float* img; bool fused; };
 
 // the geometric embedding of a pass (launch_vq_geo_embed): the matrices of the pass's images, the latent plane and the two weights [z_channels, 4]
@@ -389,10 +389,11 @@ struct Pass {
 
 // The workspace of a pass over n images (layout functions, arena.h): metered for the largest pass, carved per pass.  Allocation order and sizes are part of the measured
 // arena bytes and stay as they are.
-struct DecBufs { float* img = nullptr; };                    // pixel staging of the three-kernel tail [n, RH RW, 4]
+struct DecBufs { float* img = nullptr; };                    // pixel staging of the three-kernel tail [n, RH RW, max(4, out_ch)]: its convolution writes ldc = out_ch
+inline size_t tail_staging_floats(long pixels, int cout) { return (size_t)pixels * (size_t)std::max(4, cout); }   // (4 for every out_ch <= 4: the measured arena bytes of the camera decoder)
 struct EncBufs { float *dots = nullptr, *zz = nullptr; };   // codebook products [n lat_h lat_w, n_embed] and row norms of the quantizer
 
-DecBufs dec_layout(Arena& a, Pass& p, const VqSizes& z, int embed_dim, int n) {
+DecBufs dec_layout(Arena& a, Pass& p, const VqSizes& z, int embed_dim, int out_ch, int n) {
     DecBufs d;
     if (p.planes) p.part.buf = a.get<float>((size_t)z.per_img * n / 64 + 64);   // GroupNorm partials of one tensor: (pixels / 32) x (channels / 4) x 2
     p.a = a.get<float>((size_t)z.per_img * n);
@@ -405,7 +406,7 @@ DecBufs dec_layout(Arena& a, Pass& p, const VqSizes& z, int embed_dim, int n) {
     p.vT = a.get<float>((size_t)n * z.attn_hwp * z.max_c);
     p.S = a.get<float>((size_t)n * z.attn_hwp * z.attn_hwp);
     p.zq = a.get<float>((size_t)n * z.lat_h * z.lat_w * embed_dim);
-    d.img = a.get<float>((size_t)n * z.RH * z.RW * 4);
+    d.img = a.get<float>(tail_staging_floats((long)n * z.RH * z.RW, out_ch));
     p.o = a.get<float>((size_t)z.per_img * n);
     return d;
 }
@@ -556,20 +557,21 @@ void vq_decode(Ctx& c, const int64_t* ids, const float* latents_nchw, int n_tota
     const auto& g = c.cfg;
     BG_REQUIRE(lat_h >= 1 && lat_w >= 1, "vq_decode: latent grid %d x %d", lat_h, lat_w);
     BG_REQUIRE(out_mode == 0 || g.vq_out_ch == 3, "denormalize needs 3 output channels");
+    BG_REQUIRE(c.conv_out.cout == g.vq_out_ch, "vq_decode: decoder.conv_out has %d output channels, the configuration says out_ch = %d", c.conv_out.cout, g.vq_out_ch);
     Pass proto;
     proto.s = s;
     proto.planes = g.precision == BEVGEN_PRECISION_F16X3;
     const VqSizes z = vq_scan(c.vq_dec_shape, lat_h, lat_w);
     const VqPasses cut = vq_pass_cut(n_total);
     const long lat_hw = (long)lat_h * lat_w;
-    c.arena.reserve(Arena::measure([&](Arena& a) { Pass p = proto; dec_layout(a, p, z, g.vq_embed_dim, cut.chunk); }));
+    c.arena.reserve(Arena::measure([&](Arena& a) { Pass p = proto; dec_layout(a, p, z, g.vq_embed_dim, c.conv_out.cout, cut.chunk); }));
     RangeSites sites = sites_reserve(c, proto.planes && g.vq_range ? vq_sites_per_pass(c.vq_dec_shape) * cut.passes : 0, s);
     if (sites.cap) proto.range = &sites;
     for (int i0 = 0; i0 < n_total; i0 += cut.chunk) {
         const int n = std::min(cut.chunk, n_total - i0);
         c.arena.reset();
         Pass p = proto;
-        const DecBufs d = dec_layout(c.arena, p, z, g.vq_embed_dim, n);
+        const DecBufs d = dec_layout(c.arena, p, z, g.vq_embed_dim, c.conv_out.cout, n);
         if (ids) launch_codebook_gather(ids + (long)i0 * lat_hw, c.codebook, p.zq, (int)(n * lat_hw), g.vq_embed_dim, g.vq_n_embed, s);
         else launch_nchw_to_nhwc(latents_nchw + (long)i0 * g.vq_embed_dim * lat_hw, p.zq, n, (int)lat_hw, g.vq_embed_dim, s);
         p.conv1(p.zq, n * lat_hw, c.post_quant, p.t, nullptr);                       // post_quant_conv
@@ -781,8 +783,9 @@ void vq_op_attn_block(Ctx& c, const float* x, const float* norm_w, const float* 
 }
 
 void vq_op_out_tail(Ctx& c, const float* x, const float* norm_w, const float* norm_b, const float* w, const float* bias, const float* mean, const float* stdv, int out_mode,
-                    int three_kernels, void* out, int n, int H, int W, int C, hipStream_t s) {
-    const int cout = 3;
+                    int three_kernels, void* out, int n, int H, int W, int C, int cout, hipStream_t s) {
+    BG_REQUIRE(cout >= 1 && cout <= 64, "op_vq_out_tail: cout=%d (1 .. 64)", cout);
+    BG_REQUIRE(out_mode == 0 || cout == 3, "op_vq_out_tail: denormalize needs 3 output channels (cout=%d)", cout);
     BG_REQUIRE(n >= 1 && H >= 1 && W >= 1 && C >= 32 && C % 32 == 0 && C <= 1024, "op_vq_out_tail: C=%d must be a multiple of 32 (at most 1024)", C);
     BG_REQUIRE(out_mode >= 0 && out_mode <= 2 && (out_mode == 0 || (mean && stdv)), "op_vq_out_tail: out_mode 0 / 1 / 2; 1 and 2 need mean and std");
     const long hw = (long)H * W;
@@ -794,7 +797,7 @@ void vq_op_out_tail(Ctx& c, const float* x, const float* norm_w, const float* no
         p.t = a.get<float>((size_t)n * hw * C);
         p.stats = a.get<float>((size_t)n * 64);
         p.gn_ws = a.alloc(groupnorm_ws_bytes(n, (int)hw));
-        img = a.get<float>((size_t)n * hw * 4);
+        img = a.get<float>(tail_staging_floats(n * hw, cout));
     });
     OpWeights ow(c, s);
     const ConvW co = ow.conv(wb, w, bias, cout, C, 3);

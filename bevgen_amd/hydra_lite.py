@@ -37,6 +37,7 @@ TARGET_REWRITES: Dict[str, str] = {
     "multi_view_generation.modules.transformer.mingpt_sparse.": "bevgen_amd.modules.transformer.mingpt_sparse.",
     "multi_view_generation.modules.transformer.sparse_self_attention.": "bevgen_amd.modules.transformer.sparse_self_attention.",
     "multi_view_generation.modules.losses.vqperceptual.DummyLoss": "bevgen_amd.modules.losses.DummyLoss",
+    "multi_view_generation.modules.losses.segmentation.": "bevgen_amd.modules.losses.segmentation.",
     "multi_view_generation.utils.GenerateImages": "bevgen_amd.writer.GenerateImages",
     "multi_view_generation.utils.callback.GenerateImages": "bevgen_amd.writer.GenerateImages",
 }

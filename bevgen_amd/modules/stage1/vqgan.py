@@ -7,7 +7,8 @@
 Parameters carry the reference's ``state_dict`` names (encoder.*, decoder.*, quantize.embedding.weight, quant_conv.*, post_quant_conv.*).
 ``decode`` runs the hand-written HIP decoder (bevgen_vq_decode / bevgen_vq_decode_latents); ``encode`` (the step BEFORE the path)
 runs the HIP encoder + arg-min quantizer (bevgen_vq_encode / bevgen_vq_encode_ex: the geometric embedding of ``geometric_embedding=True`` and the codebook loss);
-``forward`` / ``log_images`` are the stage-1 reconstruction (encode, then decode).
+``forward`` / ``log_images`` are the stage-1 reconstruction (encode, then decode).  ``VQSegmentationModel`` (the stage-1 BEV model, configs/model/stage_1_bev.yaml) adds
+``validation_step`` / ``test_step`` with the loss kept in ``self.loss`` (modules/losses/segmentation.py) and its own ``log_images`` through ``to_rgb`` (bevgen_op_seg_colorize).
 """
 from __future__ import annotations
 
@@ -87,6 +88,10 @@ class VQModel(RuntimeOptionsMixin, nn.Module):
         self.cam_latent_res = tuple(cam_latent_res) if cam_latent_res is not None else None
         self.image_key = image_key
         self.denormalize = denormalize
+        # vqgan:57.  The loss classes of this package hold no parameters (the state_dict does not move) and run on this model's device context
+        self.loss = lossconfig
+        if hasattr(lossconfig, "bind"):
+            lossconfig.bind(self)
         self.quantize = VectorQuantizer2(n_embed, embed_dim, beta=0.25, remap=remap, sane_index_shape=sane_index_shape, legacy=legacy)
         if self.geometric_embedding:
             # vqgan:59-69.  img_embed / cam_embed map 4 -> cam_emd_dim channels and their output is added to the encoder's z_channels (`h_flat += img_embed`, vqgan:111)
@@ -113,6 +118,17 @@ class VQModel(RuntimeOptionsMixin, nn.Module):
             from ...checkpoint import init_from_ckpt
 
             init_from_ckpt(self, ckpt_path, ignore_keys=list(ignore_keys), strict=False)
+
+    # ---------------------------------------------------------------------------------- copies (copy.deepcopy, pickle, torch.save of the module)
+    def __getstate__(self):
+        state = self.__dict__.copy()
+        state["_ctx"] = None            # the device context belongs to this object: a copy builds its own on first use
+        return state
+
+    def __setstate__(self, state):
+        super().__setstate__(state)
+        if hasattr(self.loss, "bind"):  # the copied loss runs on the COPY's context
+            self.loss.bind(self)
 
     # ---------------------------------------------------------------------------------- device context
     def load_state_dict(self, *a, **k):
@@ -221,3 +237,49 @@ class VQSegmentationModel(VQModel):
         super().__init__(*args, **kwargs)
         self.n_labels = n_labels
         self.register_buffer("colorize", torch.randn(3, n_labels, 1, 1))  # checkpoint key (vqgan:219); only used by visualisation
+
+    def to_rgb(self, x, threshold=False):
+        """vqgan:201-213: the random projection `colorize` of x [n, C, H, W], min-max normalised over the whole tensor (Context.seg_to_rgb); threshold: of
+        round(sigmoid(x)), evaluated as x > 0 (include/bevgen_hip.h bevgen_op_seg_colorize)."""
+        self._check_rgb(x.shape[1])
+        return self.context().seg_to_rgb(x, self.colorize, threshold)
+
+    def _check_rgb(self, channels):
+        assert self.image_key == "segmentation", "to_rgb colours a segmentation (vqgan:202): image_key must be 'segmentation'"
+        if channels == 12:
+            raise NotImplementedError("12 channels are nuScenes' BEV layers, drawn by a third-party visualiser in the reference (vqgan:203-205)")
+        if channels != self.colorize.shape[1]:
+            raise ValueError(f"{channels} channels do not fit the colorize buffer {tuple(self.colorize.shape)} (n_labels)")
+
+    @torch.no_grad()
+    def log_images(self, batch, **kwargs):
+        """vqgan:245-261 -> {'inputs', 'reconstructions'}.  More than 3 channels: to_rgb(x) and to_rgb(round(sigmoid(xrec))), [n, 3, H, W] in [0, 1]; otherwise the raw
+        input and the raw reconstruction (this class does not denormalise: VQModel.log_images does, with the camera statistics)."""
+        x = self.get_input(batch, self.image_key).to(module_device(self))
+        if x.shape[1] > 3:
+            self._check_rgb(x.shape[1])   # (before the forward: the refusals need no device)
+        xrec, _ = self(x, batch)
+        if x.shape[1] > 3:
+            assert xrec.shape[1] > 3
+            x, xrec = self.to_rgb(x), self.to_rgb(xrec, threshold=True)
+        return {"inputs": x, "reconstructions": xrec}
+
+    @torch.no_grad()
+    def validation_step(self, batch, batch_idx):
+        """vqgan:231-239: {'loss': aeloss} of self.loss(qloss, x, xrec, split='val'), plus the log_images dict on every tenth batch; the logged values go to
+        log_dict where the object has one (a LightningModule does)."""
+        if self.loss is None:
+            raise RuntimeError("validation_step needs a loss: construct the model with lossconfig (modules/losses/segmentation.py BCELossWithQuant)")
+        x = self.get_input(batch, self.image_key).to(module_device(self))
+        xrec, qloss = self(x, batch)
+        aeloss, log_dict_ae = self.loss(qloss, x, xrec, split="val")
+        if hasattr(self, "log_dict"):
+            self.log_dict(log_dict_ae, prog_bar=False, logger=True, on_step=True, on_epoch=True)
+        ret = {"loss": aeloss}
+        if batch_idx % 10 == 0:
+            ret = {**ret, **self.log_images(batch)}
+        return ret
+
+    @torch.no_grad()
+    def test_step(self, batch, batch_idx):
+        return self.log_images(batch)

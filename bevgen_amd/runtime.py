@@ -697,15 +697,61 @@ class Context:
                                                      _ptr(bp), _ptr(y), n, h, w, Cc, self._s()))
         return y
 
-    def op_vq_out_tail(self, x_nhwc, norm_w, norm_b, w_oihw, bias, mode="raw", mean=None, std=None, fused=True):
-        """The decoder's tail conv_out(swish(norm_out(x))) -> NCHW [n, 3, H, W]: mode 'raw' fp32, 'denorm' (x std + mean, clamped to [0, 1]) or 'u8' (round(255 x) of that);
-        fused=False: the three-kernel form."""
+    def op_vq_out_tail(self, x_nhwc, norm_w, norm_b, w_oihw, bias, mode="raw", mean=None, std=None, fused=True, cout=None):
+        """The decoder's tail conv_out(swish(norm_out(x))) -> NCHW [n, cout, H, W]: mode 'raw' fp32, 'denorm' (x std + mean, clamped to [0, 1]) or 'u8' (round(255 x) of that);
+        fused=False: the three-kernel form.  cout=None: the export with three output channels; a number: bevgen_op_vq_out_tail_ex with w_oihw [cout, C, 3, 3] (3 and 7 have
+        the fused kernel, every other count runs as three kernels; 'denorm' / 'u8' need 3)."""
         n, H, W, Cc = x_nhwc.shape
         out_mode = {"raw": _lib.VQ_OUT_RAW, "denorm": _lib.VQ_OUT_DENORM, "u8": _lib.VQ_OUT_U8}[mode]
-        out = torch.empty((n, 3, H, W), dtype=torch.uint8 if mode == "u8" else torch.float32, device=self.device)
-        self._check(self.lib.bevgen_op_vq_out_tail(self._h, _ptr(x_nhwc), _ptr(norm_w), _ptr(norm_b), _ptr(w_oihw), _ptr(bias), _ptr(mean), _ptr(std), out_mode, int(not fused),
-                                                   _ptr(out), n, H, W, Cc, self._s()))
+        if cout is not None and (w_oihw.shape[0] != cout or (bias is not None and bias.numel() != cout)):
+            raise ValueError(f"op_vq_out_tail: weight {tuple(w_oihw.shape)} / bias do not have cout = {cout} output channels")
+        out = torch.empty((n, 3 if cout is None else int(cout), H, W), dtype=torch.uint8 if mode == "u8" else torch.float32, device=self.device)
+        args = (self._h, _ptr(x_nhwc), _ptr(norm_w), _ptr(norm_b), _ptr(w_oihw), _ptr(bias), _ptr(mean), _ptr(std), out_mode, int(not fused), _ptr(out), n, H, W, Cc)
+        if cout is None:
+            self._check(self.lib.bevgen_op_vq_out_tail(*args, self._s()))
+        else:
+            self._check(self.lib.bevgen_op_vq_out_tail_ex(*args, int(cout), self._s()))
         return out
+
+    def op_bce_logits(self, logits, target, qloss=None, codebook_weight=1.0):
+        """out [2] fp32 on the device: out[0] = F.binary_cross_entropy_with_logits(logits, target) (mean; fp32 per element, double sum in a fixed order) and, with qloss
+        (a one-element device tensor), out[1] = out[0] + codebook_weight * qloss in fp32; without qloss out[1] is left as allocated (NaN here)."""
+        if logits.shape != target.shape:
+            raise ValueError(f"op_bce_logits: logits {tuple(logits.shape)} and target {tuple(target.shape)} differ in shape")
+        out = torch.full((2,), float("nan"), dtype=torch.float32, device=self.device)
+        self._check(self.lib.bevgen_op_bce_logits(self._h, _ptr(logits), _ptr(target), logits.numel(), _ptr(qloss), float(codebook_weight), _ptr(out), self._s()))
+        return out
+
+    def op_seg_colorize(self, x, colorize, threshold=False):
+        """VQModel.to_rgb: x [n, C, H, W] (C <= 32), colorize [3, C] -> [n, 3, H, W] = the projection, min-max normalised over the whole tensor; threshold: of (x > 0)
+        instead of x, which stands for torch.round(torch.sigmoid(x)) (include/bevgen_hip.h names the one interval where the two differ)."""
+        n, Cc, H, W = x.shape
+        if colorize.numel() != 3 * Cc:
+            raise ValueError(f"op_seg_colorize: colorize {tuple(colorize.shape)} does not project {Cc} channels to 3")
+        rgb = torch.empty((n, 3, H, W), dtype=torch.float32, device=self.device)
+        self._check(self.lib.bevgen_op_seg_colorize(self._h, _ptr(x), _ptr(colorize), int(bool(threshold)), _ptr(rgb), n, Cc, H, W, self._s()))
+        return rgb
+
+    # the stage-1 BEV segmentation model's loss and visualisation (modules/losses/segmentation.py, VQSegmentationModel.log_images): tensors are brought to this context's
+    # device as fp32; results stay on the device
+    def bce_logits(self, pred, target, qloss=None, codebook_weight=1.0, check=True):
+        """(bce, total): 0-dim device tensors; total = bce + codebook_weight * qloss (fp32, as torch evaluates it), or None without qloss."""
+        pred, target = _req(pred, torch.float32, self.device, "pred"), _req(target, torch.float32, self.device, "target")
+        if qloss is not None:
+            qloss = _req(qloss, torch.float32, self.device, "qloss").reshape(-1)
+            if qloss.numel() != 1:
+                raise ValueError("bce_logits: qloss is one number (the quantizer's loss)")
+        out = self.op_bce_logits(pred, target, qloss, codebook_weight)
+        self._done(check)
+        return out[0], (out[1] if qloss is not None else None)
+
+    def seg_to_rgb(self, x, colorize, threshold=False, check=True):
+        """to_rgb(x) (threshold=False) or to_rgb(round(sigmoid(x))) (threshold=True) with the model's `colorize` buffer [3, C, 1, 1]: [n, C, H, W] -> [n, 3, H, W] in [0, 1]."""
+        x = _req(x, torch.float32, self.device, "x")
+        colorize = _req(colorize, torch.float32, self.device, "colorize").reshape(3, -1)
+        rgb = self.op_seg_colorize(x, colorize, threshold)
+        self._done(check)
+        return rgb
 
     def op_vq_quantize(self, z, codebook, want_norms=False):
         """ids [rows] = argmin_j |z - e_j|^2 as the quantizer forms it ((|z|^2 + |e_j|^2) - 2 z.e_j, lowest index on ties); want_norms: also (|z|^2 [rows], |e|^2 [n_e])."""

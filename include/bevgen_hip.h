@@ -424,6 +424,26 @@ int bevgen_op_vq_attn_block(bevgen_ctx* ctx, const float* d_x_nhwc, const float*
 int bevgen_op_vq_out_tail(bevgen_ctx* ctx, const float* d_x_nhwc, const float* d_norm_w, const float* d_norm_b, const float* d_w_oihw, const float* d_bias /* or NULL */,
                           const float* d_mean /* [3], or NULL with out_mode 0 */, const float* d_std, int out_mode, int three_kernels, void* d_out, int n, int H, int W, int C,
                           void* stream);
+/* vq_out_tail_ex: vq_out_tail with `cout` output channels (d_w [cout][C][3][3], d_bias [cout], d_out [n, cout, H, W]); bevgen_op_vq_out_tail is this with cout = 3.
+ * cout 3 and 7 (the BEV segmentation decoder, out_ch 7) have the fused kernel, any other count runs the three-kernel form whatever three_kernels says; the pixel staging
+ * of that form is max(4, cout) floats per pixel.  out_mode 1 / 2 need cout == 3. */
+int bevgen_op_vq_out_tail_ex(bevgen_ctx* ctx, const float* d_x_nhwc, const float* d_norm_w, const float* d_norm_b, const float* d_w_oihw, const float* d_bias /* or NULL */,
+                             const float* d_mean /* [3], or NULL with out_mode 0 */, const float* d_std, int out_mode, int three_kernels, void* d_out, int n, int H, int W, int C,
+                             int cout, void* stream);
+/* bce_logits: F.binary_cross_entropy_with_logits(logits, target) with mean reduction (losses/segmentation.py:7,17): per element max(x, 0) - x t + log1p(exp(-|x|)) in fp32
+ * (|x| up to 1e4 and beyond without overflow, soft targets allowed, NaN propagates), summed in double in a fixed order (two calls give the same bits), times 1 / count in
+ * double, rounded to float once -> d_out[0].  d_qloss non-NULL: also d_out[1] = d_out[0] + codebook_weight * d_qloss[0] in fp32, the product rounded and then the sum, as
+ * torch evaluates BCELossWithQuant's `bce_loss + self.codebook_weight*qloss`; d_qloss NULL leaves d_out[1] untouched.  fp32 in every precision mode. */
+int bevgen_op_bce_logits(bevgen_ctx* ctx, const float* d_logits, const float* d_target, long count, const float* d_qloss /* or NULL */, float codebook_weight,
+                         float* d_out /* [2]: bce, total */, void* stream);
+/* seg_colorize: VQModel.to_rgb's random projection (stage1/vqgan.py:207-212): d_rgb [n, 3, H, W] = (y - min y) / (max y - min y) with y_k = sum_c d_colorize[k][c] v_c in
+ * channel order (fmaf), d_x [n, C, H, W] (NCHW), C <= 32; d_rgb must not alias d_x.  threshold = 0: v = x.  threshold = 1: v = (x > 0 ? 1 : 0), which stands for the
+ * reference's torch.round(torch.sigmoid(x)) (vqgan:253-256): the two agree (ties to even) everywhere except 0 < x <~ 6e-8, where fp32 sigmoid rounds to 0.5 and the
+ * reference therefore gives 0 (on the CPU, torch.round(torch.sigmoid(1e-9)) = 0).  round(sigmoid(.)) of a logit near 0 is a step: no bound on the logit carries over.
+ * min and max are taken over the WHOLE tensor (all n images), on the device, through an order-preserving integer encoding and atomicMin / atomicMax: one moved extreme
+ * rescales every pixel, the order of the atomics does not matter, so the result is bit-reproducible.  IEEE fp32 subtraction and a true division; max == min gives 0 / 0
+ * as in the reference; a NaN makes every pixel NaN.  (The reference's model decodes z + (z_q - z), this library z_q: at most an ulp of z apart in front of the decoder.) */
+int bevgen_op_seg_colorize(bevgen_ctx* ctx, const float* d_x, const float* d_colorize /* [3, C] */, int threshold, float* d_rgb, int n, int C, int H, int W, void* stream);
 /* vq_quantize: VectorQuantizer2.forward's arg-min, d_ids[r] = argmin_j (|z_r|^2 + |e_j|^2) - 2 z_r . e_j with the lowest index on ties; d_z [rows, D], d_codebook [n_e, D],
  * D % 32 == 0; d_zz [rows] / d_ee [n_e] (or NULL) receive the squared norms.  A row without a finite distance gets id 0 and raises BEVGEN_STATUS_NONFINITE_LATENTS. */
 int bevgen_op_vq_quantize(bevgen_ctx* ctx, const float* d_z, const float* d_codebook, int64_t* d_ids, float* d_zz /* or NULL */, float* d_ee /* or NULL */, long rows, int n_e,
