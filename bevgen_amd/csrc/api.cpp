@@ -163,6 +163,44 @@ int bevgen_maskgit_generate_ex(bevgen_ctx* ctx, const int64_t* cond, const float
     });
 }
 
+int bevgen_maskgit_loss(bevgen_ctx* ctx, const int64_t* ids, const int64_t* cond, const float* I_inv, const float* E_inv, int B, const int32_t* h_num_masked,
+                        const float* perm_u, const float* gumbel_u, float temperature, unsigned long long noise_seed, int with_critic, float critic_loss_weight, float* out,
+                        uint8_t* mask_out, int64_t* x_out, int64_t* critic_input_out, void* stream) {
+    return guarded(ctx, [&] {
+        need_final(ctx);
+        BG_REQUIRE(ids && cond && I_inv && E_inv && h_num_masked && out, "maskgit_loss: null argument");
+        BG_REQUIRE(B >= 1 && (ctx->cfg.max_batch <= 0 || B <= ctx->cfg.max_batch), "maskgit_loss: batch %d exceeds max_batch %d", B, ctx->cfg.max_batch);
+        const MaskgitLoss lp{h_num_masked, perm_u, gumbel_u, temperature, noise_seed, with_critic != 0, critic_loss_weight, out, mask_out, x_out, critic_input_out};
+        maskgit_loss(*ctx, MuseBatch{cond, I_inv, E_inv, B}, ids, lp, (hipStream_t)stream);
+    });
+}
+
+int bevgen_op_maskgit_train_mask(bevgen_ctx* ctx, const int64_t* ids, const float* perm_u, const int32_t* num_masked, int rows, int T, int64_t mask_id,
+                                 unsigned long long seed, int64_t* x, uint8_t* mask, void* stream) {
+    return guarded(ctx, [&] {
+        BG_REQUIRE(ids && num_masked && x && mask && rows >= 1 && T >= 1, "op_maskgit_train_mask: bad arguments");
+        launch_maskgit_train_mask(ids, perm_u, num_masked, x, mask, rows, T, mask_id, seed, (hipStream_t)stream);
+    });
+}
+
+int bevgen_op_masked_ce(bevgen_ctx* ctx, const float* logits, int ldl, const int64_t* ids, const uint8_t* mask, long rows, int V, long denom, float* nll, float* out,
+                        void* stream) {
+    return guarded(ctx, [&] {
+        BG_REQUIRE(logits && ids && mask && nll && rows >= 1 && V >= 1 && ldl >= V && (!out || denom >= 1), "op_masked_ce: bad arguments");
+        launch_maskgit_ce_rows(logits, ldl, ids, mask, nll, rows, V, (hipStream_t)stream);
+        if (out) launch_mean_fixed_order(nll, rows, out, (hipStream_t)stream, denom);
+    });
+}
+
+int bevgen_op_critic_bce(bevgen_ctx* ctx, const float* embed, int lde, const float* w, const float* b, const int64_t* ids, const int64_t* critic_input, long rows, int D,
+                         float* loss_rows, float* out, void* stream) {
+    return guarded(ctx, [&] {
+        BG_REQUIRE(embed && w && b && ids && critic_input && loss_rows && rows >= 1 && D >= 1 && lde >= D, "op_critic_bce: bad arguments");
+        launch_critic_bce_rows(embed, lde, w, b, ids, critic_input, loss_rows, rows, D, (hipStream_t)stream);
+        if (out) launch_mean_fixed_order(loss_rows, rows, out, (hipStream_t)stream);
+    });
+}
+
 int bevgen_op_philox_uniform(bevgen_ctx* ctx, unsigned long long seed, unsigned iter, unsigned stream_id, int V, long n, float* out, void* stream) {
     return guarded(ctx, [&] {
         BG_REQUIRE(out && n >= 0, "op_philox_uniform: bad arguments");

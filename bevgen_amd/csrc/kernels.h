@@ -413,7 +413,18 @@ void launch_ar_pick(const float* logits, int ldl, const float* u /*[steps, rows]
 // (nll may be null), wnll[r] = weight[b, fwd_idx[s0 + r]] * nll[r] (weight null = 1); target null: only the NaN / inf check of the rows (BG_ST_NONFINITE_LOGITS)
 void launch_ar_score_rows(const float* logits, int ldl, const int64_t* target /*[B, N] camera-major*/, const float* weight, const int64_t* fwd_idx, int b, int s0, int rows,
                           int N, int V, float* nll, float* wnll, hipStream_t s);
-void launch_mean_fixed_order(const float* x, long n, float* out, hipStream_t s);   // out[0] = sum(x) / n, double accumulation in a fixed order (bit-reproducible)
+// out[0] = sum(x) / (denom > 0 ? denom : n), double accumulation in a fixed order (bit-reproducible)
+void launch_mean_fixed_order(const float* x, long n, float* out, hipStream_t s, long denom = 0);
+// MaskGit.forward (muse_net:629-729, eval mode).  train_mask: mask = argsort(u) < n per row of [rows, T] (ties: lower index first), u = perm_u or Philox stream 2 of `seed`
+// at iteration 0 (element = row * T + i); n_mask [rows] int32 on the device; x = mask_id where masked
+void launch_maskgit_train_mask(const int64_t* ids, const float* perm_u /*or null*/, const int* n_mask, int64_t* x, uint8_t* mask, int rows, int T, int64_t mask_id,
+                               unsigned long long seed, hipStream_t s);
+// nll[p] = logsumexp(logits[p]) - logits[p, ids[p]] at masked positions, 0 elsewhere; logits [rows, ldl >= V], V <= 1024
+void launch_maskgit_ce_rows(const float* logits, int ldl, const int64_t* ids, const uint8_t* mask, float* nll, long rows, int V, hipStream_t s);
+// loss[p] = BCE-with-logits(embed[p, :D] . w + b, ids[p] != critic_input[p])
+void launch_critic_bce_rows(const float* embed, int lde, const float* w, const float* b, const int64_t* ids, const int64_t* critic_input, float* loss, long rows, int D,
+                            hipStream_t s);
+void launch_maskgit_loss_combine(float* out /*[3]: in ce, bce at [1], [2]*/, float weight, int with_critic, hipStream_t s);
 
 // ---------------------------------------------------------------- vq.hip
 void launch_codebook_gather(const int64_t* ids, const float* codebook, float* out, int rows, int dim, int n_embed, hipStream_t s);

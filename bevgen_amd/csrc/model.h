@@ -205,6 +205,11 @@ struct MaskgitSampling {   // bevgen_maskgit_generate_ex's sampling arguments (b
 };
 void muse_forward(Ctx& c, const MuseBatch& in, const int64_t* ids, float* logits, float* embed, hipStream_t s);
 void maskgit_generate(Ctx& c, const MuseBatch& in, const MaskgitSampling& sp, int64_t* out, hipStream_t s);
+struct MaskgitLoss {   // bevgen_maskgit_loss's arguments behind the batch (bevgen_hip.h)
+    const int32_t* h_num_masked; const float *perm_u, *gumbel_u; float temperature; unsigned long long noise_seed; int with_critic; float critic_loss_weight;
+    float* out; uint8_t* mask_out; int64_t *x_out, *critic_input_out;
+};
+void maskgit_loss(Ctx& c, const MuseBatch& in, const int64_t* ids, const MaskgitLoss& lp, hipStream_t s);
 // ar.cpp
 void sparse_self_attention_op(Ctx& c, const float* q, const float* k, const float* v, const int64_t* layout, const float* mask, const float* add, int B, int H,
                               int L, int block, float* out, hipStream_t s);

@@ -23,12 +23,14 @@ struct MuseWs {
     int B = 0;
     int S = 1;   // samples per BEV layout: consecutive groups of S scenes share their condition, whose cross-attention K / V exist once per layout
     bool generate = false;   // the call also needs logits and scores
+    bool loss = false;       // MaskGit.forward's losses: logits, the masked ids / mask / counts and one value per token row
 
     long rows = 0;
     float *img = nullptr, *c_embed = nullptr, *context = nullptr;
     int64_t* cond_g = nullptr; float* c_embed_g = nullptr;   // S > 1: the first scene of every group as contiguous [G, ...] inputs of the condition side
     std::vector<float*> crossK, crossV;
-    float *logits = nullptr, *scores = nullptr;   // generate only
+    float *logits = nullptr, *scores = nullptr;   // generate only (logits: loss too)
+    int64_t* loss_x = nullptr; uint8_t* loss_mask = nullptr; int* loss_n = nullptr; float* loss_rows = nullptr;   // loss only: x [rows], mask [rows], n [B * cams], nll / bce [rows]
     float *x = nullptr, *xn = nullptr, *qraw = nullptr, *kvraw = nullptr, *Q = nullptr, *Ks = nullptr, *Vs = nullptr, *att = nullptr, *h = nullptr, *g = nullptr;
     size_t kvS = 0, kvC = 0;   // elements of one self- / cross-attention K (or V) buffer: B (or B / S) x H x Nk_pad x 64
     float* attn_ws = nullptr; int attn_ks = 1;   // key-split self-attention of the low-latency path (pick_attn_ksplit): partial rows of the key ranges
@@ -340,12 +342,16 @@ void muse_layout(const Ctx& c, MuseWs& w, Arena& a) {
         w.crossK[i] = a.get<float>(w.kvC);
         w.crossV[i] = a.get<float>(w.kvC);
     }
-    w.logits = w.generate ? a.get<float>((size_t)w.rows * c.V) : nullptr;
+    w.logits = w.generate || w.loss ? a.get<float>((size_t)w.rows * c.V) : nullptr;
     w.scores = w.generate ? a.get<float>((size_t)w.rows) : nullptr;
+    w.loss_x = w.loss ? a.get<int64_t>((size_t)w.rows) : nullptr;
+    w.loss_mask = w.loss ? a.get<uint8_t>((size_t)w.rows) : nullptr;
+    w.loss_n = w.loss ? a.get<int>((size_t)B * g.num_cams) : nullptr;
+    w.loss_rows = w.loss ? a.get<float>((size_t)w.rows) : nullptr;
 }
 
 // per-batch constants: the workspace, the tensors used by name, embeddings + cross-attention K/V
-void muse_prepare(Ctx& c, MuseWs& w, const MuseBatch& in, bool generate, hipStream_t s) {
+void muse_prepare(Ctx& c, MuseWs& w, const MuseBatch& in, bool generate, hipStream_t s, bool loss = false) {
     const auto& g = c.cfg;
     const std::string p = "transformer.";
     const int B = in.B, S = in.samples_per_layout < 1 ? 1 : in.samples_per_layout;
@@ -354,6 +360,7 @@ void muse_prepare(Ctx& c, MuseWs& w, const MuseBatch& in, bool generate, hipStre
     w.S = S;
     w.B = B;
     w.generate = generate;
+    w.loss = loss;
     w.rows = (long)B * c.N;
     c.arena.carve([&](Arena& a) { muse_layout(c, w, a); });
     w.token_emb = c.pf(p + "token_emb.weight"); w.pos_emb = c.pf(p + "pos_emb.weight");
@@ -452,6 +459,43 @@ void maskgit_generate(Ctx& c, const MuseBatch& in, const MaskgitSampling& sp, in
                                  sp.noise_seed, (unsigned)step);
         }
     }
+}
+
+// MaskGit.forward in eval mode (muse_net:629-729): mask, forward, masked cross-entropy; with the self critic the gumbel pick at the masked positions, a second forward
+// (embed only: the head is not run) and the critic's BCE.  Every reduction is a fixed-order double sum: two calls give the same bits.
+void maskgit_loss(Ctx& c, const MuseBatch& in, const int64_t* ids, const MaskgitLoss& lp, hipStream_t s) {
+    BG_REQUIRE(c.cfg.route == BEVGEN_ROUTE_MASKGIT, "context was not created for the MaskGit route");
+    BG_REQUIRE(in.B >= 1 && ids && lp.h_num_masked && lp.out, "bad maskgit_loss arguments");
+    BG_REQUIRE(lp.perm_u || lp.noise_seed, "maskgit_loss: neither d_perm_u nor a noise_seed: a mask needs randomness");
+    BG_REQUIRE(!lp.with_critic || lp.gumbel_u || lp.noise_seed, "maskgit_loss: the critic input is a gumbel sample: neither d_gumbel_u nor a noise_seed");
+    BG_REQUIRE(!lp.with_critic || c.find("token_critic.to_pred.weight"), "maskgit_loss: the context holds no token critic (token_critic.to_pred.*): call with with_critic = 0");
+    const int seqs = in.B * c.cfg.num_cams, T = c.T, V = c.V, D = c.D;
+    long masked = 0;
+    for (int r = 0; r < seqs; ++r) {
+        BG_REQUIRE(lp.h_num_masked[r] >= 1 && lp.h_num_masked[r] <= T, "maskgit_loss: h_num_masked[%d]=%d outside [1, %d]", r, lp.h_num_masked[r], T);
+        masked += lp.h_num_masked[r];
+    }
+    MuseWs w;
+    muse_prepare(c, w, in, false, s, true);
+    const long rows = w.rows;
+    const int64_t mask_id = c.cfg.vocab_size;
+    HIP_CHECK(hipMemcpyAsync(w.loss_n, lp.h_num_masked, (size_t)seqs * sizeof(int), hipMemcpyHostToDevice, s));   // (a few hundred bytes of pageable memory: the runtime copies them to its staging buffer before the call returns)
+    launch_maskgit_train_mask(ids, lp.perm_u, w.loss_n, w.loss_x, w.loss_mask, seqs, T, mask_id, lp.noise_seed, s);
+    if (lp.mask_out) HIP_CHECK(hipMemcpyAsync(lp.mask_out, w.loss_mask, (size_t)rows, hipMemcpyDeviceToDevice, s));
+    if (lp.x_out) HIP_CHECK(hipMemcpyAsync(lp.x_out, w.loss_x, (size_t)rows * sizeof(int64_t), hipMemcpyDeviceToDevice, s));
+    muse_blocks(c, w, w.loss_x, s);
+    gemm({w.xn, D}, gemm_args(c, {w.to_logits, D}, {w.logits, V}, (int)rows, V, D), s);
+    launch_maskgit_ce_rows(w.logits, V, ids, w.loss_mask, w.loss_rows, rows, V, s);
+    launch_mean_fixed_order(w.loss_rows, rows, lp.out + 1, s, masked);
+    if (lp.with_critic) {
+        // gumbel_sample over all V logits (no top-k, muse_net:713) replaces exactly the masked positions of x: critic_input = where(mask, sampled, x) (:718)
+        launch_maskgit_pick(w.loss_x, w.logits, V, lp.gumbel_u, (int)rows, V, V, lp.temperature, mask_id, s, lp.noise_seed, 0u, nullptr, 0);
+        if (lp.critic_input_out) HIP_CHECK(hipMemcpyAsync(lp.critic_input_out, w.loss_x, (size_t)rows * sizeof(int64_t), hipMemcpyDeviceToDevice, s));
+        muse_blocks(c, w, w.loss_x, s);
+        launch_critic_bce_rows(w.xn, D, w.critic_w, w.critic_b, ids, w.loss_x, w.loss_rows, rows, D, s);
+        launch_mean_fixed_order(w.loss_rows, rows, lp.out + 2, s);
+    }
+    launch_maskgit_loss_combine(lp.out, lp.critic_loss_weight, lp.with_critic, s);
 }
 
 }  // namespace bevgen

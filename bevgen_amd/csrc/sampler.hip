@@ -375,7 +375,8 @@ void launch_ar_score_rows(const float* logits, int ldl, const int64_t* target, c
 
 // loss = sum(x) / n in a FIXED order (thread t adds elements t, t + 256, ... in double, then a binary tree over the 256 partial sums): two calls give the same bits,
 // no float atomics.  One workgroup: n = B * n_steps <= a few 10^4.
-__global__ __launch_bounds__(256) void mean_fixed_order_kernel(const float* __restrict__ x, long n, float* __restrict__ out) {
+// `denom`: what the sum is divided by (n for a mean; the masked count for the masked cross-entropy, whose unmasked rows hold 0)
+__global__ __launch_bounds__(256) void mean_fixed_order_kernel(const float* __restrict__ x, long n, double denom, float* __restrict__ out) {
     __shared__ double sh[256];
     double acc = 0.0;
     for (long i = threadIdx.x; i < n; i += 256) acc += (double)x[i];
@@ -385,10 +386,133 @@ __global__ __launch_bounds__(256) void mean_fixed_order_kernel(const float* __re
         if ((int)threadIdx.x < o) sh[threadIdx.x] += sh[threadIdx.x + o];
         __syncthreads();
     }
-    if (threadIdx.x == 0) out[0] = (float)(sh[0] / (double)n);
+    if (threadIdx.x == 0) out[0] = (float)(sh[0] / denom);
 }
-void launch_mean_fixed_order(const float* x, long n, float* out, hipStream_t s) {
-    hipLaunchKernelGGL(mean_fixed_order_kernel, dim3(1), dim3(256), 0, s, x, n, out);
+void launch_mean_fixed_order(const float* x, long n, float* out, hipStream_t s, long denom) {
+    hipLaunchKernelGGL(mean_fixed_order_kernel, dim3(1), dim3(256), 0, s, x, n, (double)(denom > 0 ? denom : n), out);
+    LAUNCH_CHECK();
+}
+
+// ---------------------------------------------------------------------------------------------- MaskGit.forward: validation losses (muse_net:629-729, eval mode)
+// The training mask (muse_net:660-675): mask = rand(rows, T).argsort(-1) < n[:, None], i.e. position i is masked iff the index of the i-th smallest uniform of its row
+// is below n.  One workgroup per row: the row's uniforms in LDS, then for each j < n the rank of u[j] (ties: the lower index first - one of the orders an unstable argsort
+// may return) marks position rank(j).  The ranks are a permutation, so no two threads mark the same byte.  x = mask_id where masked, else the id.
+__global__ __launch_bounds__(256) void maskgit_train_mask_kernel(const int64_t* __restrict__ ids, const float* __restrict__ perm_u, const int* __restrict__ n_mask,
+                                                                 int64_t* __restrict__ x, uint8_t* __restrict__ mask, int T, int64_t mask_id, unsigned long long seed) {
+    extern __shared__ float su[];
+    uint8_t* flag = reinterpret_cast<uint8_t*>(su + T);
+    const long row = blockIdx.x;
+    for (int i = threadIdx.x; i < T; i += blockDim.x) {
+        su[i] = perm_u ? perm_u[row * T + i] : philox_uniform(seed, (unsigned long long)(row * T + i), 0u, 2u);
+        flag[i] = 0;
+    }
+    __syncthreads();
+    const int n = min(max(n_mask[row], 0), T);
+    for (int j = threadIdx.x; j < n; j += blockDim.x) {
+        const float u = su[j];
+        int rank = 0;
+        for (int k = 0; k < T; ++k) rank += (su[k] < u || (su[k] == u && k < j)) ? 1 : 0;
+        flag[rank] = 1;
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < T; i += blockDim.x) {
+        const uint8_t m = flag[i];
+        mask[row * T + i] = m;
+        x[row * T + i] = m ? mask_id : ids[row * T + i];
+    }
+}
+void launch_maskgit_train_mask(const int64_t* ids, const float* perm_u, const int* n_mask, int64_t* x, uint8_t* mask, int rows, int T, int64_t mask_id,
+                               unsigned long long seed, hipStream_t s) {
+    BG_REQUIRE(rows >= 1 && T >= 1 && (size_t)T * 5 <= 64 * 1024, "maskgit_train_mask: %d uniforms and flags per row do not fit the 64 KiB of dynamic LDS", T);
+    BG_REQUIRE(perm_u || seed, "maskgit_train_mask: neither explicit uniforms nor a seed (a mask needs randomness)");
+    hipLaunchKernelGGL(maskgit_train_mask_kernel, dim3(rows), dim3(256), (size_t)T * 5, s, ids, perm_u, n_mask, x, mask, T, mask_id, seed);
+    LAUNCH_CHECK();
+}
+
+// Masked cross-entropy per position (muse_net:379 with labels = where(mask, ids, ignore_index)): nll = logsumexp(logits) - logits[id] where masked, 0 elsewhere.  One wave
+// per position, the V <= 64 * VPL_MAX logits in registers (the layout of maskgit_pick_kernel); an id outside [0, V) gives a NaN nll.  Like the pick, only the masked
+// positions' logits are read and checked (BG_ST_NONFINITE_LOGITS).
+__global__ __launch_bounds__(256) void maskgit_ce_rows_kernel(const float* __restrict__ logits, int ldl, const int64_t* __restrict__ ids, const uint8_t* __restrict__ mask,
+                                                              float* __restrict__ nll, long rows, int V, unsigned* __restrict__ status) {
+    const int lane = threadIdx.x & 63;
+    const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= rows) return;   // (whole waves)
+    if (!mask[row]) {
+        if (lane == 0) nll[row] = 0.f;
+        return;
+    }
+    const float* lr = logits + row * ldl;
+    const int64_t t = ids[row];
+    float x[VPL_MAX];
+    float mx = -INFINITY, xt = 0.f;
+    bool nf = false;
+#pragma unroll
+    for (int j = 0; j < VPL_MAX; ++j) {
+        const int i = lane + 64 * j;
+        x[j] = i < V ? lr[i] : -INFINITY;
+        if (i < V) {
+            nf |= nonfinite(x[j]);
+            mx = fmaxf(mx, x[j]);
+            if (i == t) xt = x[j];
+        }
+    }
+    if (nf) status_raise(status, BG_ST_NONFINITE_LOGITS);
+    mx = wave_max(mx);
+    float sum = 0.f;
+#pragma unroll
+    for (int j = 0; j < VPL_MAX; ++j)
+        if (lane + 64 * j < V) sum += expf(x[j] - mx);
+    sum = wave_sum(sum);
+    xt = wave_sum(xt);   // exactly one lane holds the label's logit
+    if (lane == 0) nll[row] = (t >= 0 && t < V) ? (mx + logf(sum)) - xt : __uint_as_float(0x7fc00000u);
+}
+void launch_maskgit_ce_rows(const float* logits, int ldl, const int64_t* ids, const uint8_t* mask, float* nll, long rows, int V, hipStream_t s) {
+    BG_REQUIRE(V >= 1 && V <= 64 * VPL_MAX, "maskgit_ce_rows: vocabulary %d > %d", V, 64 * VPL_MAX);
+    BG_REQUIRE(rows >= 1 && ldl >= V, "maskgit_ce_rows: %ld positions, row pitch %d < V = %d", rows, ldl, V);
+    hipLaunchKernelGGL(maskgit_ce_rows_kernel, dim3(cdiv(rows, 4)), dim3(256), 0, s, logits, ldl, ids, mask, nll, rows, V, status_current());
+    LAUNCH_CHECK();
+}
+
+// Self-critic loss per position (muse_net:402-414, 718-719): z = embed . w + b accumulated as critic_scores_kernel does, label y = (id != critic input),
+// loss = max(z, 0) - z y + log1p(exp(-|z|)) (F.binary_cross_entropy_with_logits, no overflow for any finite z).  A non-finite z raises BG_ST_NONFINITE_LOGITS.
+__global__ __launch_bounds__(256) void critic_bce_rows_kernel(const float* __restrict__ embed, int lde, const float* __restrict__ w, const float* __restrict__ b,
+                                                              const int64_t* __restrict__ ids, const int64_t* __restrict__ critic_input, float* __restrict__ loss, long rows,
+                                                              int D, unsigned* __restrict__ status) {
+    const int lane = threadIdx.x & 63;
+    const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= rows) return;
+    const float* e = embed + row * lde;
+    float acc = 0.f;
+    for (int i = lane * 4; i < D; i += 256) {
+        const float4 ev = *reinterpret_cast<const float4*>(e + i);
+        const float4 wv = *reinterpret_cast<const float4*>(w + i);
+        acc = fmaf(ev.x, wv.x, acc); acc = fmaf(ev.y, wv.y, acc); acc = fmaf(ev.z, wv.z, acc); acc = fmaf(ev.w, wv.w, acc);
+    }
+    acc = wave_sum(acc);
+    if (lane == 0) {
+        const float z = acc + b[0];
+        if (nonfinite(z)) status_raise(status, BG_ST_NONFINITE_LOGITS);
+        const float y = ids[row] != critic_input[row] ? 1.f : 0.f;
+        loss[row] = (fmaxf(z, 0.f) - z * y) + log1pf(expf(-fabsf(z)));
+    }
+}
+void launch_critic_bce_rows(const float* embed, int lde, const float* w, const float* b, const int64_t* ids, const int64_t* critic_input, float* loss, long rows, int D,
+                            hipStream_t s) {
+    BG_REQUIRE(rows >= 1 && D >= 4 && D % 4 == 0 && lde >= D, "critic_bce_rows: D = %d must be a positive multiple of 4 and lde = %d >= D", D, lde);
+    BG_REQUIRE(lde % 4 == 0 && ((reinterpret_cast<uintptr_t>(embed) | reinterpret_cast<uintptr_t>(w)) & 15) == 0,
+               "critic_bce_rows: 16-byte loads need lde %% 4 == 0 (got %d) and 16-byte aligned embed / w", lde);
+    hipLaunchKernelGGL(critic_bce_rows_kernel, dim3(cdiv(rows, 4)), dim3(256), 0, s, embed, lde, w, b, ids, critic_input, loss, rows, D, status_current());
+    LAUNCH_CHECK();
+}
+
+// out = {ce + weight * bce, ce, bce} from out[1], out[2] (muse_net:729: the product rounded, then the sum, as torch evaluates it); without a critic {ce, ce, 0}
+__global__ void maskgit_loss_combine_kernel(float* __restrict__ out, float weight, int with_critic) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    if (!with_critic) out[2] = 0.f;
+    out[0] = with_critic ? __fadd_rn(out[1], __fmul_rn(weight, out[2])) : out[1];
+}
+void launch_maskgit_loss_combine(float* out, float weight, int with_critic, hipStream_t s) {
+    hipLaunchKernelGGL(maskgit_loss_combine_kernel, dim3(1), dim3(64), 0, s, out, weight, with_critic);
     LAUNCH_CHECK();
 }
 

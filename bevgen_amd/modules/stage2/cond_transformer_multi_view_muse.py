@@ -169,6 +169,46 @@ class Net2NetTransformer(_Base):
         log.info("Generating images took %.3f s", time.time() - start)
         return {"gen": gen, "rec": rec, "gt": gt}
 
+    # ---- validation losses (muse_lm:181-218)
+    def get_xc(self, batch, N=None):
+        """muse_lm:181-188."""
+        x = self.get_input(self.first_stage_key, batch)
+        c = self.get_input(self.cond_stage_key, batch)
+        if N is not None:
+            x, c = x[:N], c[:N]
+        return x, c
+
+    @torch.no_grad()
+    def shared_step(self, batch, batch_idx, inference=False, noise=None):
+        """muse_lm:190-202: MaskGit.forward on the encoded images given the encoded condition -> (loss, ce, bce), or (loss, loss, 0) without a critic.  Precomputed
+        batch['z_ids'] / batch['cond_ids'] short-circuit the encoders."""
+        dev = next(self.maskgit.parameters()).device
+        _, c = self.encode_to_c(None if "cond_ids" in batch else self.get_input(self.cond_stage_key, batch).to(dev), batch)
+        c = c.to(dev)
+        if "z_ids" in batch:
+            z = batch["z_ids"].to(dev)
+        else:
+            _, z = self.encode_to_z(self.get_input(self.first_stage_key, batch).to(dev), batch)
+        z = z.reshape(c.shape[0] * self.cfg.num_cams, -1)
+        geo = {**batch, "intrinsics_inv": batch["intrinsics_inv"].to(dev), "extrinsics_inv": batch["extrinsics_inv"].to(dev)}
+        loss = self.maskgit.forward(z, cond_images=c, batch=geo, weights=None, noise=noise)
+        return loss if isinstance(loss, tuple) else (loss, loss, 0)
+
+    def validation_step(self, batch, batch_idx):
+        """muse_lm:204-218."""
+        loss, ce_loss, bce_critic_loss = self.shared_step(batch, batch_idx)
+        if hasattr(self, "log"):
+            self.log("val/loss", loss, prog_bar=True, on_step=False, on_epoch=True)
+            self.log("val/ce_loss", ce_loss, prog_bar=True, on_step=False, on_epoch=True)
+            self.log("val/critic_loss", bce_critic_loss, prog_bar=True, on_step=False, on_epoch=True)
+        ret = {"loss": loss}
+        if batch_idx == 0:
+            try:   # (the reference: "Viz code has a lot of side effects so we catch and continue")
+                ret = {**self.log_images(batch), **ret}
+            except Exception as ex:
+                log.error("log_images failed", exc_info=ex)
+        return ret
+
     def test_step(self, batch, batch_idx):
         return self.log_images(batch, generate_only=True)
 

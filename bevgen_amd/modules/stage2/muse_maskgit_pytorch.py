@@ -5,7 +5,7 @@ Same class names, constructor kwargs, method signatures and ``state_dict`` keys 
   SelfCritic                    muse_net:388-396
   MaskGit                       muse_net:467-627              (``_target_`` at muse_stage_two_multi_view.yaml:26)
 The modules hold parameters only; ``forward`` / ``generate`` run inside libbevgen_hip (bevgen_muse_forward,
-bevgen_maskgit_generate).  Inference only (the surveyed branch has no training, README.md:20).
+bevgen_maskgit_generate, bevgen_maskgit_loss).  Inference and validation losses only: no gradients (the surveyed branch has no training, README.md:20).
 """
 from __future__ import annotations
 
@@ -175,5 +175,62 @@ class MaskGit(RuntimeOptionsMixin, nn.Module):
         logits, embed = self.context().muse_forward(x, conditioning_token_ids, batch["intrinsics_inv"], batch["extrinsics_inv"])
         return (logits, embed) if return_embed else logits
 
-    def forward(self, *a, **k):
-        raise NotImplementedError("training losses are outside the inference path this library accelerates (README.md:20: no training in the released branch)")
+    PHILOX_HOST_STREAM = 3   # noise=int: the mask times (elements 0 .. rows-1) and the temperature (element rows) come from this Philox stream at iteration 0
+
+    def _forward_refusals(self, ignore_index, cond_images, cond_token_ids, cond_drop_prob, weights):
+        """What MaskGit.forward cannot evaluate, refused before anything touches the device."""
+        V = self.transformer.num_tokens
+        if weights is not None:
+            raise NotImplementedError("weights (muse_net:375-377: the bounding-box weighting of the cross-entropy, training only) is not implemented; refusing rather than ignoring it")
+        if self.no_mask_token_prob > 0.:
+            raise NotImplementedError("no_mask_token_prob > 0 (muse_net:671-673: part of the masked tokens keep their id) is set by no shipped configuration and is not implemented")
+        assert not (cond_images is not None and cond_token_ids is not None), 'if conditioning on low resolution, cannot pass in both images and token ids'   # muse_net:654
+        if 0 <= int(ignore_index) <= V:
+            raise ValueError(f"ignore_index = {ignore_index} is a token id of this model (0 .. {V}, the mask id included): labels = where(mask, ids, ignore_index) "
+                             "(muse_net:669) would drop real tokens from the cross-entropy")
+        drop = self.cond_drop_prob if cond_drop_prob is None else cond_drop_prob
+        if self.transformer.training and drop > 0:
+            raise NotImplementedError(f"the transformer is in training mode with cond_drop_prob = {drop} (muse_net:310-313 would drop conditions at random): this library "
+                                      "evaluates the eval-mode arithmetic only; call .eval() first (Lightning's validate loop does)")
+
+    @torch.no_grad()
+    def forward(self, images_or_ids: torch.Tensor, ignore_index=-1, cond_images: Optional[torch.Tensor] = None, cond_token_ids: Optional[torch.Tensor] = None,
+                cond_drop_prob=None, train_only_generator=False, sample_temperature=None, batch=None, weights=None, noise=None):
+        """muse_net:629-729 in eval mode, on the device (bevgen_maskgit_loss): the masked-token cross-entropy and, with a token critic, the critic's BCE ->
+        (ce + critic_loss_weight * bce, ce, bce), or ce alone without a critic / with train_only_generator, as 0-dim device tensors.  ``noise``: None -> the reference's
+        own sources (mask times from torch's CPU generator, a Philox seed for the permutation and the gumbel noise from it as in ``generate``, the temperature from
+        Python's ``random()``: ``seed_everything`` reproduces a run); an int -> everything from that Philox seed; or explicit {'time_u' [rows], 'perm_u' [rows, T],
+        'gumbel_u' [rows, T, V], 'temperature'}.  Equal uniforms within a perm_u row rank by index."""
+        import random
+
+        self._forward_refusals(ignore_index, cond_images, cond_token_ids, cond_drop_prob, weights)
+        cond = cond_images if cond_images is not None else cond_token_ids
+        if cond is None or batch is None:
+            raise ValueError("MaskGit.forward needs the condition token ids (cond_images) and the batch with intrinsics_inv / extrinsics_inv")
+        ids = images_or_ids.reshape(images_or_ids.shape[0], -1)   # 'b ... -> b (...)', muse_net:648
+        rows, T = ids.shape
+        with_critic = self.token_critic is not None and not train_only_generator   # muse_net:708
+        ctx = self.context()
+        perm_u = gumbel_u = None
+        seed = 0
+        if noise is None:
+            time_u = torch.zeros(rows).float().uniform_(0, 1)   # muse_net:430-431, 660
+            seed = int(torch.randint(1, 2 ** 62, (), dtype=torch.int64).item())
+            temperature = sample_temperature if sample_temperature is not None else random.random()   # muse_net:713
+        elif isinstance(noise, int):
+            seed = noise
+            host = ctx.philox_uniform(seed, 0, self.PHILOX_HOST_STREAM, rows + 1).cpu()
+            time_u = host[:rows]
+            temperature = sample_temperature if sample_temperature is not None else float(host[rows])
+        else:
+            time_u, perm_u, gumbel_u = noise["time_u"], noise["perm_u"], noise.get("gumbel_u")
+            temperature = noise["temperature"] if noise.get("temperature") is not None else sample_temperature
+            if with_critic and (gumbel_u is None or temperature is None):
+                raise ValueError("explicit noise needs 'gumbel_u' and a temperature for the critic loss")
+        # the masked count per row with the reference's own fp32 CPU operations (muse_net:661-662): no device cos can move a count by one
+        time_u = torch.as_tensor(time_u, dtype=torch.float32).cpu().reshape(rows)
+        num_masked = (T * self.noise_schedule(time_u)).round().clamp(min=1)
+        out = ctx.maskgit_loss(ids, cond, batch["intrinsics_inv"], batch["extrinsics_inv"], num_masked.to(torch.int64), perm_u=perm_u, gumbel_u=gumbel_u,
+                               temperature=0.0 if temperature is None else float(temperature), noise_seed=seed, with_critic=with_critic,
+                               critic_loss_weight=float(self.critic_loss_weight))
+        return (out[0], out[1], out[2]) if with_critic else out[1]

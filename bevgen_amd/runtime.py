@@ -267,8 +267,53 @@ class Context:
         self._done(check)
         return out.reshape(rows, cfg.cam_latent_h, cfg.cam_latent_w)
 
+    def maskgit_loss(self, ids, cond_ids, I_inv, E_inv, num_masked, *, perm_u=None, gumbel_u=None, temperature=1.0, noise_seed=0, with_critic=True,
+                     critic_loss_weight=1.0, return_aux=False, check=True):
+        """MaskGit.forward in eval mode (``bevgen_maskgit_loss``): ids [(B C), T] ground-truth tokens, num_masked [(B C)] host integers in [1, T] (the reference's
+        clamp(round(T cos(pi/2 t)), 1), evaluated by the caller).  perm_u [(B C), T] / gumbel_u [(B C), T, V]: explicit uniforms, else Philox streams 2 / 0 of noise_seed.
+        Returns out [3] = (ce + critic_loss_weight * bce, ce, bce) - (ce, ce, 0) with with_critic=False - on the device; with return_aux also
+        {'mask' bool, 'x', 'critic_input' (None without a critic)}, each [(B C), T]."""
+        cfg = self.cfg
+        d = self.device
+        cond_ids = _req(cond_ids, torch.int64, d, "cond_ids")
+        I_inv = _req(I_inv, torch.float32, d, "I_inv")
+        E_inv = _req(E_inv, torch.float32, d, "E_inv")
+        B = cond_ids.shape[0]
+        rows, T, V = B * cfg.num_cams, cfg.num_cam_tokens, cfg.vocab_size
+        ids = _req(ids, torch.int64, d, "ids").reshape(ids.shape[0], -1)
+        if tuple(ids.shape) != (rows, T):
+            raise ValueError(f"ids must be [{rows}, {T}] ((batch x cameras) rows of camera tokens), got {tuple(ids.shape)}")
+        n = [int(v) for v in (num_masked.tolist() if hasattr(num_masked, "tolist") else num_masked)]
+        if len(n) != rows or min(n) < 1 or max(n) > T:
+            raise ValueError(f"num_masked must hold {rows} counts in [1, {T}], got {n}")
+        if perm_u is not None:
+            perm_u = _req(perm_u, torch.float32, d, "perm_u")
+            if tuple(perm_u.shape) != (rows, T):
+                raise ValueError(f"perm_u must be [{rows}, {T}], got {tuple(perm_u.shape)}")
+        if gumbel_u is not None and with_critic:
+            gumbel_u = _req(gumbel_u, torch.float32, d, "gumbel_u")
+            if gumbel_u.numel() != rows * T * V:
+                raise ValueError(f"gumbel_u must hold [{rows}, {T}, {V}] uniforms, got {tuple(gumbel_u.shape)}")
+        else:
+            gumbel_u = None
+        seed = int(noise_seed) & 0xFFFFFFFFFFFFFFFF
+        if seed == 0 and (perm_u is None or (with_critic and gumbel_u is None)):
+            raise ValueError("maskgit_loss: noise_seed = 0 without explicit uniforms (a mask needs randomness)")
+        out = torch.empty((3,), dtype=torch.float32, device=d)
+        mask = torch.empty((rows, T), dtype=torch.uint8, device=d) if return_aux else None
+        x = torch.empty((rows, T), dtype=torch.int64, device=d) if return_aux else None
+        ci = torch.empty((rows, T), dtype=torch.int64, device=d) if return_aux and with_critic else None
+        self._check(self.lib.bevgen_maskgit_loss(self._h, _ptr(ids), _ptr(cond_ids), _ptr(I_inv), _ptr(E_inv), B, (C.c_int32 * rows)(*n), _ptr(perm_u), _ptr(gumbel_u),
+                                                 float(temperature), C.c_uint64(seed), int(bool(with_critic)), float(critic_loss_weight), _ptr(out), _ptr(mask), _ptr(x),
+                                                 _ptr(ci), self._s()))
+        self._done(check)
+        if return_aux:
+            return out, {"mask": mask.bool(), "x": x, "critic_input": ci}
+        return out
+
     def philox_uniform(self, seed, it, stream_id, n, V=0):
-        """The uniforms maskgit_generate(noise_seed=seed) draws at iteration `it` (stream 0: gumbel [rows*V], 1: critic [rows])."""
+        """The uniforms maskgit_generate(noise_seed=seed) draws at iteration `it` (stream 0: gumbel [rows*V], 1: critic [rows]); of maskgit_loss: stream 2 = the
+        mask permutation's [rows*T] at iteration 0 (stream 3 is MaskGit.forward's own: the mask times and the temperature of an integer seed)."""
         out = torch.empty((n,), dtype=torch.float32, device=self.device)
         self._check(self.lib.bevgen_op_philox_uniform(self._h, C.c_uint64(int(seed)), int(it), int(stream_id), int(V), int(n), _ptr(out), self._s()))
         return out
@@ -579,6 +624,36 @@ class Context:
         self._check(self.lib.bevgen_op_critic_scores(self._h, _ptr(embed), self._ld(embed, lde), _ptr(w), _ptr(b), _ptr(u), float(noise_scale), float(frac),
                                                      C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), int(it), _ptr(scores), rows, D, self._s()))
         return scores
+
+    def op_maskgit_train_mask(self, ids, num_masked, mask_id, *, perm_u=None, seed=0, x=None, mask=None):
+        """(x int64, mask uint8), each [rows, T] (written in place where given): mask = argsort(u) < num_masked[row], ties by index; u = perm_u [rows, T], else Philox
+        stream 2 of `seed`; num_masked [rows] int32 on the device."""
+        rows, T = ids.shape
+        x = torch.empty_like(ids) if x is None else x
+        mask = torch.empty((rows, T), dtype=torch.uint8, device=self.device) if mask is None else mask
+        self._check(self.lib.bevgen_op_maskgit_train_mask(self._h, _ptr(ids), _ptr(perm_u), _ptr(num_masked), rows, T, int(mask_id), C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF),
+                                                          _ptr(x), _ptr(mask), self._s()))
+        return x, mask
+
+    def op_masked_ce(self, logits, V, ids, mask, *, denom=None, nll=None, out=None, ldl=None):
+        """(nll [rows], mean) of logits [rows, ldl >= V]: nll = logsumexp - logit[id] where mask (uint8), 0 elsewhere; mean = sum(nll) / denom (None: not computed)."""
+        rows = ids.numel()
+        nll = torch.empty((rows,), dtype=torch.float32, device=self.device) if nll is None else nll
+        if denom is not None and out is None:
+            out = torch.empty((), dtype=torch.float32, device=self.device)
+        self._check(self.lib.bevgen_op_masked_ce(self._h, _ptr(logits), self._ld(logits, ldl), _ptr(ids), _ptr(mask), rows, int(V), int(denom or 0), _ptr(nll),
+                                                 _ptr(out if denom is not None else None), self._s()))
+        return nll, out
+
+    def op_critic_bce(self, embed, w, b, ids, critic_input, D=None, *, loss_rows=None, want_mean=True, lde=None):
+        """(loss [rows], mean): BCE-with-logits of z = embed[:, :D] . w + b against the label (ids != critic_input)."""
+        rows = ids.numel()
+        D = embed.shape[1] if D is None else int(D)
+        loss_rows = torch.empty((rows,), dtype=torch.float32, device=self.device) if loss_rows is None else loss_rows
+        out = torch.empty((), dtype=torch.float32, device=self.device) if want_mean else None
+        self._check(self.lib.bevgen_op_critic_bce(self._h, _ptr(embed), self._ld(embed, lde), _ptr(w), _ptr(b), _ptr(ids), _ptr(critic_input), rows, D, _ptr(loss_rows),
+                                                  _ptr(out), self._s()))
+        return loss_rows, out
 
     def op_ar_pick(self, logits, V, *, top_k=0, temperature=1.0, u=None, step=None, forced=None, ldl=None, out_all=None, fwd_idx=None, tok_emb=None, img_embed=None,
                    pos_emb=None, x=None, C_=0, T=0):

@@ -212,6 +212,37 @@ int bevgen_maskgit_generate_ex(bevgen_ctx* ctx, const int64_t* d_cond_ids, const
                                const float* d_gumbel_u, const float* d_critic_u, const int64_t* d_init_ids, int64_t* d_out_ids,
                                unsigned long long noise_seed, int score_mode, int samples_per_layout, void* stream);
 
+/* MaskGit.forward in eval mode (stage2/muse_maskgit_pytorch.py:629-729; no condition drop, no self conditioning): the validation losses.
+ *   d_ids [B*C, T]              the ground-truth token ids
+ *   h_num_masked[B*C]           tokens masked per row, clamp(round(T cos(pi/2 t)), min = 1) (:660-662) - host-computed with the reference's own fp32 operations, in [1, T]
+ *   d_perm_u [B*C, T] or NULL   the uniforms whose argsort is the reference's batch_randperm (:665): position i of a row is masked iff the index of the row's i-th smallest
+ *                               uniform is below the row's count; equal uniforms rank by index (one of the orders an unstable argsort may return)
+ *   d_gumbel_u [B*C, T, V] or NULL   uniforms of gumbel_sample (:713, no top-k); read with with_critic only
+ *   noise_seed                  used where an explicit tensor is NULL: d_perm_u = Philox stream 2 (element = plain index), d_gumbel_u = stream 0 (the layout of
+ *                               bevgen_maskgit_generate), both at iteration 0 and reproducible through bevgen_op_philox_uniform.  0 with a NULL tensor is refused.
+ *   temperature                 sample_temperature (the reference's default is Python's random())
+ *   with_critic                 0: the masked cross-entropy alone, d_out = {ce, ce, 0}; else d_out = {ce + critic_loss_weight * bce, ce, bce} (:729), which needs
+ *                               token_critic.to_pred.* in the context
+ *   d_mask_out [B*C, T] u8, d_x_out, d_critic_input_out [B*C, T] i64, each or NULL: the mask, the masked ids and where(mask, sampled, x) (:718; with_critic only)
+ * ce = mean over the masked positions of logsumexp(logits) - logits[id]; bce = mean over all positions of BCE-with-logits(to_pred(embed(critic_input)), id != critic_input).
+ * Both are fixed-order double sums rounded to float once: two calls give the same bits.  The two transformer forwards are bevgen_muse_forward's, in the context's precision. */
+int bevgen_maskgit_loss(bevgen_ctx* ctx, const int64_t* d_ids, const int64_t* d_cond_ids, const float* d_I_inv, const float* d_E_inv, int B,
+                        const int32_t* h_num_masked, const float* d_perm_u, const float* d_gumbel_u, float temperature, unsigned long long noise_seed,
+                        int with_critic, float critic_loss_weight, float* d_out /* [3] */, uint8_t* d_mask_out, int64_t* d_x_out, int64_t* d_critic_input_out,
+                        void* stream);
+/* The three kernels of bevgen_maskgit_loss, one entry each (sampler.hip).
+ * maskgit_train_mask: d_mask [rows, T] = argsort(u) < d_num_masked[row] with u = d_perm_u, else Philox stream 2 of `seed`; d_x = mask_id where masked, else d_ids.  T <= 13107. */
+int bevgen_op_maskgit_train_mask(bevgen_ctx* ctx, const int64_t* d_ids, const float* d_perm_u /* or NULL */, const int32_t* d_num_masked, int rows, int T, int64_t mask_id,
+                                 unsigned long long seed, int64_t* d_x, uint8_t* d_mask, void* stream);
+/* masked_ce: d_nll[p] = logsumexp(d_logits[p, :V]) - d_logits[p, d_ids[p]] where d_mask[p], 0 elsewhere (an id outside [0, V): NaN); V <= 1024, ldl >= V.  Non-finite logits of a
+ * masked position raise BEVGEN_STATUS_NONFINITE_LOGITS.  d_out non-NULL: d_out[0] = sum(d_nll) / denom in a fixed order. */
+int bevgen_op_masked_ce(bevgen_ctx* ctx, const float* d_logits, int ldl, const int64_t* d_ids, const uint8_t* d_mask, long rows, int V, long denom, float* d_nll,
+                        float* d_out /* or NULL */, void* stream);
+/* critic_bce: z = d_embed[p, :D] . d_w + d_b[0], y = (d_ids[p] != d_critic_input[p]), d_loss_rows[p] = max(z, 0) - z y + log1p(exp(-|z|)); D % 4 == 0, lde % 4 == 0, d_embed
+ * and d_w 16-byte aligned.  d_out non-NULL: d_out[0] = the mean over the rows in a fixed order. */
+int bevgen_op_critic_bce(bevgen_ctx* ctx, const float* d_embed, int lde, const float* d_w, const float* d_b, const int64_t* d_ids, const int64_t* d_critic_input, long rows,
+                         int D, float* d_loss_rows, float* d_out /* or NULL */, void* stream);
+
 /* ---------------------------------------------------------------------------------------------------------------
  * Route A - autoregressive sparse-causal transformer with camera bias (prefill + KV-cache decode)                 */
 
