@@ -108,6 +108,8 @@ SIGNATURES = {
     "bevgen_op_vq_out_tail_ex": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _p, _i, _i, _i, _i, _i, _p]),
     "bevgen_op_bce_logits": (_i, [_p, _p, _p, _l, _p, _f, _p, _p]),
     "bevgen_op_seg_colorize": (_i, [_p, _p, _p, _i, _p, _i, _i, _i, _i, _p]),
+    "bevgen_op_image_sqerr": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _p, _p, _p, _p]),
+    "bevgen_op_ssim": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _i, C.c_double, C.c_double, C.c_double, C.c_double, _p, _p, _p, _p]),
     "bevgen_op_vq_quantize": (_i, [_p, _p, _p, _p, _p, _p, _l, _i, _i, _p]),
     "bevgen_op_vq_geo_embed": (_i, [_p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _p]),
     "bevgen_op_vq_quant_error": (_i, [_p, _p, _p, _p, _f, _p, _p, _l, _i, _i, _p]),
@@ -121,6 +123,7 @@ SIGNATURES = {
     "bevgen_op_attn_tables": (_i, [_p, _i, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _l, _l, _f, _p]),
     "bevgen_op_attention_tiles": (_i, [_p, _p, _p, _p, _p, _i, _p, _i, _i, _i, _i, _f, _i, _i, _i, _p, _p]),
     "bevgen_decode_attention_splits": (_i, [_i, _i, _i]),
+    "bevgen_metrics_workspace_bytes": (_l, [_i, _i, _i, _i, _i, _i]),
     "bevgen_profile_begin": (_i, [_p]),
     "bevgen_profile_end": (_i, [_p, C.POINTER(C.c_double)]),
     "bevgen_ar_step_timing": (_i, [_p, _i]),

@@ -892,6 +892,21 @@ int bevgen_op_seg_colorize(bevgen_ctx* ctx, const float* x, const float* coloriz
     });
 }
 
+int bevgen_op_image_sqerr(bevgen_ctx* ctx, const void* a, const void* b, int dtype, int n, int C, int H, int W, double* sse, float* minmax, void* work, void* stream) {
+    return guarded(ctx, [&] {
+        BG_REQUIRE(a && b && sse && minmax && work, "op_image_sqerr: null argument");
+        launch_image_sqerr(a, b, dtype, n, C, H, W, sse, minmax, work, (hipStream_t)stream);
+    });
+}
+
+int bevgen_op_ssim(bevgen_ctx* ctx, const void* a, const void* b, int dtype, int n, int C, int H, int W, int kernel_size, double sigma, double data_range, double k1, double k2,
+                   double* sums, float* map, void* work, void* stream) {
+    return guarded(ctx, [&] {
+        BG_REQUIRE(a && b && sums && work, "op_ssim: null argument");
+        launch_ssim(a, b, dtype, n, C, H, W, kernel_size, sigma, data_range, k1, k2, sums, map, work, (hipStream_t)stream);
+    });
+}
+
 int bevgen_op_vq_quantize(bevgen_ctx* ctx, const float* z, const float* codebook, int64_t* ids, float* zz, float* ee, long rows, int n_e, int D, void* stream) {
     return guarded(ctx, [&] {
         BG_REQUIRE(z && codebook && ids, "op_vq_quantize: null argument");
@@ -1065,6 +1080,10 @@ int bevgen_op_attention_tiles(bevgen_ctx* ctx, const float* q, const float* k, c
 }
 
 int bevgen_decode_attention_splits(int B, int H, int n) { return decode_attention_splits(B, H, n); }
+
+long bevgen_metrics_workspace_bytes(int op, int n, int C, int H, int W, int kernel_size) {
+    return op == 0 ? image_sqerr_workspace_bytes(n, C, H, W) : op == 1 ? ssim_workspace_bytes(n, C, H, W, kernel_size) : -1;
+}
 
 int bevgen_profile_begin(bevgen_ctx* ctx) {
     return guarded(ctx, [&] { ctx->prof.begin(); });

@@ -455,6 +455,16 @@ void launch_bce_logits(const float* logits, const float* target, long count, con
 // rgb [n, 3, H, W] = minmax-normalised (whole tensor) projection colorize [3, C] of x [n, C, H, W], or of (x > 0) with threshold; minmax: two words of workspace; C <= 32
 void launch_seg_colorize(const float* x, const float* colorize, int threshold, float* rgb, int n, int C, int H, int W, unsigned* minmax, hipStream_t s);
 
+// ---------------------------------------------------------------- metrics.hip (PSNR / SSIM states of images on the device; a, b [n, C, H, W] fp32 or uint8 = v / 255)
+// bytes of caller workspace a call needs (a pure function of the shapes; -1: the call would be refused)
+long image_sqerr_workspace_bytes(int n, int C, int H, int W);
+long ssim_workspace_bytes(int n, int C, int H, int W, int k);
+// sse [n] (double) = sum (a - b)^2 per image in a fixed order; minmax [2] = (min(minmax[0], min b), max(minmax[1], max b)): the caller initialises it to (+inf, -inf)
+void launch_image_sqerr(const void* a, const void* b, int dtype, int n, int C, int H, int W, double* sse, float* minmax, void* work, hipStream_t s);
+// sums [n] (double) = per-image sum of the SSIM map [n, C, H - k + 1, W - k + 1] over the valid k x k Gaussian windows, moments about a per-tile shift; map (or null): the map
+void launch_ssim(const void* a, const void* b, int dtype, int n, int C, int H, int W, int k, double sigma, double data_range, double k1, double k2, double* sums, float* map,
+                 void* work, hipStream_t s);
+
 // misc
 void launch_fill(float* p, long n, float v, hipStream_t s);
 void launch_add(const float* a, const float* b, float* c, long n, hipStream_t s);

@@ -10,18 +10,22 @@ is the README's inference command with ``python generate.py`` replaced.  Differe
   (what the reference's DDP + DistributedSampler does, configs/modes/generate.yaml:17-18);
 * the dataset classes (nuScenes / Argoverse 2 devkits + data) are out of scope: batches come from ``--batches file.pt`` (a list of collated batch
   dicts saved with torch.save - exactly what the reference DataLoader yields) or ``--synthetic N`` (seeded BEV token ids + ring cameras);
-* ``--random-weights`` nulls every ``ckpt_path`` (deterministic generated weights) for smoke runs without the released checkpoints.
+* ``--random-weights`` nulls every ``ckpt_path`` (deterministic generated weights) for smoke runs without the released checkpoints;
+* ``--metrics`` (off by default) accumulates PSNR / SSIM of gen-vs-gt and rec-vs-gt on the device over the batches that carry images (bevgen_amd/metrics.py, the
+  PSNR / SSIM step of scripts/metrics_eval.py), prints the reference's lines at the end and writes ``<save_dir>/metrics_rank<r>.json``; with ``--synthetic`` it also
+  gives every synthetic scene seeded camera images, so that the run has a ground truth.
 """
 from __future__ import annotations
 
 import argparse
+import json
 import os
 import sys
 from typing import Any, Dict, Iterable, List
 
 import torch
 
-from . import hydra_lite, synthetic
+from . import hydra_lite, metrics, synthetic
 
 
 def _null_ckpts(node: Any) -> None:
@@ -50,7 +54,7 @@ def _cfg_nodes(node: Any, target: Any) -> List[dict]:
     return out
 
 
-def _synthetic_batches(cfg, n_scenes: int, batch_size: int, seed: int) -> Iterable[Dict[str, Any]]:
+def _synthetic_batches(cfg, n_scenes: int, batch_size: int, seed: int, images: bool = False) -> Iterable[Dict[str, Any]]:
     done = 0
     while done < n_scenes:
         b = min(batch_size, n_scenes - done)
@@ -59,6 +63,8 @@ def _synthetic_batches(cfg, n_scenes: int, batch_size: int, seed: int) -> Iterab
         batch["cam_name"] = [[name] * b for name in cfg.cam_names.value]
         H, W = cfg.bev_latent_res[0] * 16, cfg.bev_latent_res[1] * 16
         batch["segmentation"] = torch.zeros(b, H, W, 1, dtype=torch.uint8)   # placeholder condition image for bev.npz (the ids are given directly)
+        if images:   # seeded camera images in the normalised units of the data loader ([B, cams, H, W, 3]): a ground truth for --metrics
+            batch["image"] = synthetic.uniform_noise((b, cfg.num_cams, int(cfg.cam_res[0]), int(cfg.cam_res[1]), 3), seed + done, stream=5) * 2.0 - 1.0
         yield batch
         done += b
 
@@ -107,6 +113,8 @@ def main(argv: List[str] = None) -> int:
                     help="legacy_prob_matrix=false needs pretrained/cam_data_<dataset>.pt (the rig calibration the reference's dataset class writes); "
                          "use a synthetic ring rig instead when that file is absent (smoke runs)")
     ap.add_argument("--seed", type=int, default=None)
+    ap.add_argument("--metrics", action="store_true",
+                    help="accumulate PSNR / SSIM of gen and rec against gt on the device and write <save_dir>/metrics_rank<r>.json (bevgen_amd/metrics.py)")
     ap.add_argument("--print-config", action="store_true", help="print the composed configuration and exit")
     ap.add_argument("overrides", nargs="*")
     args = ap.parse_args(argv)
@@ -154,7 +162,7 @@ def main(argv: List[str] = None) -> int:
     if args.batches:
         batches: Iterable[Dict[str, Any]] = torch.load(args.batches)
     elif args.synthetic > 0:
-        batches = _synthetic_batches(model.cfg, args.synthetic, batch_size, int(seed or 0))
+        batches = _synthetic_batches(model.cfg, args.synthetic, batch_size, int(seed or 0), images=args.metrics)
     else:
         raise hydra_lite.ConfigError("pass --batches FILE or --synthetic N: the dataset classes of the reference are not part of this package")
 
@@ -162,6 +170,7 @@ def main(argv: List[str] = None) -> int:
         log_dir = cfg.get("paths", {}).get("output_dir", ".") if isinstance(cfg.get("paths"), dict) else "."
         global_rank = rank
 
+    run_metrics = metrics.make_run_metrics() if args.metrics else None
     n = 0
     with torch.no_grad():
         for i, batch in enumerate(batches):
@@ -170,9 +179,18 @@ def main(argv: List[str] = None) -> int:
             outputs = model(_to_device(batch, device))
             for cb in callbacks:
                 cb.on_test_batch_end(_Trainer, model, outputs, batch, i)
+            if run_metrics is not None:
+                metrics.accumulate_metrics(run_metrics, outputs)
             n += outputs["gen"].shape[0]
     for cb in callbacks:
         cb.on_test_end(_Trainer, model)
+    if run_metrics is not None:
+        metrics.report_metrics(run_metrics)
+        out_dir = str(callbacks[0].save_dir or _Trainer.log_dir)
+        os.makedirs(out_dir, exist_ok=True)
+        with open(os.path.join(out_dir, f"metrics_rank{rank}.json"), "w") as f:
+            json.dump(metrics.metrics_state(run_metrics), f, indent=1)
+        run_metrics["gen_psnr"].close()
     print(f"[bevgen_amd.generate] rank {rank}/{world}: wrote {n} scenes to {callbacks[0].save_dir or _Trainer.log_dir}")
     return 0
 

@@ -807,6 +807,44 @@ class Context:
         self._check(self.lib.bevgen_op_seg_colorize(self._h, _ptr(x), _ptr(colorize), int(bool(threshold)), _ptr(rgb), n, Cc, H, W, self._s()))
         return rgb
 
+    # image metrics (csrc/metrics.hip; bevgen_amd/metrics.py builds PSNR / SSIM on them): a, b [n, C, H, W] on this context's device, both fp32 (values in [0, 1]) or both
+    # uint8 (v / 255); results stay on the device.  The workspace is a tensor of this call, sized by the library's pure function.
+    _METRIC_DTYPES = {torch.float32: _lib.DTYPE_F32, torch.uint8: _lib.DTYPE_U8, torch.int64: _lib.DTYPE_I64, torch.float64: _lib.DTYPE_F64}
+
+    def _metric_args(self, name, a, b, kernel_size=0):
+        if a.shape != b.shape or a.dtype != b.dtype:
+            raise ValueError(f"{name}: preds {tuple(a.shape)} {a.dtype} and target {tuple(b.shape)} {b.dtype} differ in shape or dtype")
+        if a.dim() != 4:
+            raise ValueError(f"{name}: images are [n, C, H, W], got {tuple(a.shape)}")
+        a, b = _req(a, a.dtype, self.device, "preds"), _req(b, b.dtype, self.device, "target")
+        n, Cc, H, W = a.shape
+        dt = self._METRIC_DTYPES.get(a.dtype, -1)   # (any other number: the library refuses the dtype)
+        nbytes = self.lib.bevgen_metrics_workspace_bytes(0 if name == "op_image_sqerr" else 1, n, Cc, H, W, int(kernel_size))
+        work = torch.empty((max(int(nbytes), 8) // 8,), dtype=torch.float64, device=self.device)
+        return a, b, dt, (n, Cc, H, W), work
+
+    def op_image_sqerr(self, a, b, minmax=None):
+        """(sse [n] float64, minmax [2] float32): sse[i] = sum (a - b)^2 over image i (fp32: one fp32 subtraction and product per element, double sum in a fixed order;
+        uint8: the exact integer sum, in units of 1 / 255^2); minmax = (min, max) of the target b (uint8: of v / 255) merged INTO the buffer passed in (default: a fresh
+        (+inf, -inf)), which is how PeakSignalNoiseRatio(data_range=None) follows the range over many updates."""
+        a, b, dt, (n, Cc, H, W), work = self._metric_args("op_image_sqerr", a, b)
+        sse = torch.empty((n,), dtype=torch.float64, device=self.device)
+        if minmax is None:
+            minmax = torch.tensor([float("inf"), float("-inf")], dtype=torch.float32, device=self.device)
+        self._check(self.lib.bevgen_op_image_sqerr(self._h, _ptr(a), _ptr(b), dt, n, Cc, H, W, _ptr(sse), _ptr(minmax), _ptr(work), self._s()))
+        return sse, minmax
+
+    def op_ssim(self, a, b, kernel_size=11, sigma=1.5, data_range=1.0, k1=0.01, k2=0.03, return_map=False):
+        """sums [n] float64 = per-image sum of the SSIM map [n, C, H - k + 1, W - k + 1] (Gaussian window over the valid positions, no clamp; second moments about a
+        per-tile shift, include/bevgen_hip.h); return_map: (sums, map fp32)."""
+        a, b, dt, (n, Cc, H, W), work = self._metric_args("op_ssim", a, b, kernel_size)
+        k = int(kernel_size)
+        sums = torch.empty((max(n, 1),), dtype=torch.float64, device=self.device)[:n]
+        smap = torch.empty((n, Cc, max(H - k + 1, 0), max(W - k + 1, 0)), dtype=torch.float32, device=self.device) if return_map else None
+        self._check(self.lib.bevgen_op_ssim(self._h, _ptr(a), _ptr(b), dt, n, Cc, H, W, k, float(sigma), float(data_range), float(k1), float(k2), _ptr(sums), _ptr(smap),
+                                            _ptr(work), self._s()))
+        return (sums, smap) if return_map else sums
+
     # the stage-1 BEV segmentation model's loss and visualisation (modules/losses/segmentation.py, VQSegmentationModel.log_images): tensors are brought to this context's
     # device as fp32; results stay on the device
     def bce_logits(self, pred, target, qloss=None, codebook_weight=1.0, check=True):

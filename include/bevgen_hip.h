@@ -475,6 +475,22 @@ int bevgen_op_bce_logits(bevgen_ctx* ctx, const float* d_logits, const float* d_
  * rescales every pixel, the order of the atomics does not matter, so the result is bit-reproducible.  IEEE fp32 subtraction and a true division; max == min gives 0 / 0
  * as in the reference; a NaN makes every pixel NaN.  (The reference's model decodes z + (z_q - z), this library z_q: at most an ulp of z apart in front of the decoder.) */
 int bevgen_op_seg_colorize(bevgen_ctx* ctx, const float* d_x, const float* d_colorize /* [3, C] */, int threshold, float* d_rgb, int n, int C, int H, int W, void* stream);
+/* Image metrics on planes that are already on the device (the PSNR / SSIM step of scripts/metrics_eval.py:115-132).  d_a, d_b [n, C, H, W], contiguous, of ONE dtype:
+ * BEVGEN_DTYPE_F32 (values nominally in [0, 1]) or BEVGEN_DTYPE_U8 (0 .. 255, meaning v / 255).  fp32 / fp64 kernels in every precision mode, on any context.  Sums are
+ * taken in double in a fixed order without floating atomics: two calls give the same bits and image i's result does not depend on the rest of the batch.  A NaN pixel
+ * gives a NaN for its image only and raises no status bit.  d_work: bevgen_metrics_workspace_bytes(op, ...) bytes of caller memory (8-byte aligned), not kept between calls.
+ * Refused with BEVGEN_ERR_INVALID before any launch: another dtype, an empty batch, C H W >= 2^31, and for ssim an even kernel_size, kernel_size > 33, H or W < kernel_size.
+ * image_sqerr: d_sse[i] = sum over image i of (a - b)^2 - fp32: the difference and the square one fp32 operation each, the sum in double; uint8: the exact integer sum of
+ * (a - b)^2 in units of 1 / 255^2 - and d_minmax[0] = min(d_minmax[0], min b), d_minmax[1] = max(d_minmax[1], max b) (uint8: of v / 255): the caller initialises d_minmax to
+ * (+inf, -inf) once and every call merges into it, which is what PeakSignalNoiseRatio(data_range=None) tracks. */
+int bevgen_op_image_sqerr(bevgen_ctx* ctx, const void* d_a, const void* d_b, int dtype, int n, int C, int H, int W, double* d_sse /* [n] */, float* d_minmax /* [2] */,
+                          void* d_work, void* stream);
+/* ssim: d_sums[i] = sum over the map [C, H - k + 1, W - k + 1] of image i of ((2 mx my + c1)(2 sxy + c2)) / ((mx^2 + my^2 + c1)(sxx + syy + c2)), c1 = (k1 R)^2, c2 = (k2 R)^2,
+ * no clamp; the moments are taken with the normalised Gaussian window g g^T, g_j = exp(-d_j^2 / 2 sigma^2), over the VALID windows only (equal to reflect-padding by
+ * (k - 1) / 2, filtering and cropping the pad).  fp32 per pixel; the second moments are accumulated about a per-tile shift (the target's pixel in the middle of the tile's
+ * halo), which is added back to the means only: E[x^2] - mu^2 then cancels on the local contrast, not on the level.  d_map (or NULL): the fp32 map [n, C, H-k+1, W-k+1]. */
+int bevgen_op_ssim(bevgen_ctx* ctx, const void* d_a, const void* d_b, int dtype, int n, int C, int H, int W, int kernel_size, double sigma, double data_range, double k1,
+                   double k2, double* d_sums /* [n] */, float* d_map /* or NULL */, void* d_work, void* stream);
 /* vq_quantize: VectorQuantizer2.forward's arg-min, d_ids[r] = argmin_j (|z_r|^2 + |e_j|^2) - 2 z_r . e_j with the lowest index on ties; d_z [rows, D], d_codebook [n_e, D],
  * D % 32 == 0; d_zz [rows] / d_ee [n_e] (or NULL) receive the squared norms.  A row without a finite distance gets id 0 and raises BEVGEN_STATUS_NONFINITE_LATENTS. */
 int bevgen_op_vq_quantize(bevgen_ctx* ctx, const float* d_z, const float* d_codebook, int64_t* d_ids, float* d_zz /* or NULL */, float* d_ee /* or NULL */, long rows, int n_e,
@@ -551,6 +567,8 @@ int bevgen_op_attention_tiles(bevgen_ctx* ctx, const float* d_q, const float* d_
 
 /* Per-kernel timing support for bench.py's roofline leg: number of workgroup splits the decode-attention kernel uses. */
 int bevgen_decode_attention_splits(int B, int H, int n);
+/* Bytes of workspace bevgen_op_image_sqerr (op 0; kernel_size ignored) / bevgen_op_ssim (op 1) need for these shapes: a pure function, no context.  -1: the call would be refused. */
+long bevgen_metrics_workspace_bytes(int op, int n, int C, int H, int W, int kernel_size);
 
 /* HIP-event timing of the hot kernels on their launch stream.  Between begin and end every launch of
  *   0 gemm (fp32 MFMA)   1 conv3x3 (implicit GEMM)   2 flash attention   3 decode attention   4 skinny GEMM
