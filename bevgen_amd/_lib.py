@@ -110,6 +110,11 @@ SIGNATURES = {
     "bevgen_op_seg_colorize": (_i, [_p, _p, _p, _i, _p, _i, _i, _i, _i, _p]),
     "bevgen_op_image_sqerr": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _p, _p, _p, _p]),
     "bevgen_op_ssim": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _i, C.c_double, C.c_double, C.c_double, C.c_double, _p, _p, _p, _p]),
+    "bevgen_lpips_prepare": (_i, [_p, _p, _p, _p, _p, _p, _p, _p]),
+    "bevgen_lpips": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _p, _p, _p, _p]),
+    "bevgen_op_conv3x3_act": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p]),
+    "bevgen_op_maxpool2x2": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _p]),
+    "bevgen_op_lpips_tap": (_i, [_p, _p, _p, _p, _i, _i, _i, _p, _p]),
     "bevgen_op_vq_quantize": (_i, [_p, _p, _p, _p, _p, _p, _l, _i, _i, _p]),
     "bevgen_op_vq_geo_embed": (_i, [_p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _p]),
     "bevgen_op_vq_quant_error": (_i, [_p, _p, _p, _p, _f, _p, _p, _l, _i, _i, _p]),
@@ -124,6 +129,8 @@ SIGNATURES = {
     "bevgen_op_attention_tiles": (_i, [_p, _p, _p, _p, _p, _i, _p, _i, _i, _i, _i, _f, _i, _i, _i, _p, _p]),
     "bevgen_decode_attention_splits": (_i, [_i, _i, _i]),
     "bevgen_metrics_workspace_bytes": (_l, [_i, _i, _i, _i, _i, _i]),
+    "bevgen_lpips_prepared_bytes": (_l, [_i]),
+    "bevgen_lpips_workspace_bytes": (_l, [_i, _i, _i, _i]),
     "bevgen_profile_begin": (_i, [_p]),
     "bevgen_profile_end": (_i, [_p, C.POINTER(C.c_double)]),
     "bevgen_ar_step_timing": (_i, [_p, _i]),

@@ -790,10 +790,12 @@ int bevgen_op_ar_attn_fused(bevgen_ctx* ctx, const float* x, const float* partia
     });
 }
 
-int bevgen_op_conv3x3(bevgen_ctx* ctx, const float* x, const float* w, const float* bias, const float* residual, float* y, int n, int H, int W, int Cin, int Cout,
-                      int up, void* stream) {
+static int op_conv3x3_act(bevgen_ctx* ctx, const float* x, const float* w, const float* bias, const float* residual, float* y, int n, int H, int W, int Cin, int Cout,
+                          int up, int act, void* stream) {
     return guarded(ctx, [&] {
+        BG_REQUIRE(act == 0 || act == 1, "op_conv3x3_act: act %d (0 = none, 1 = ReLU)", act);
         GemmArgs g;
+        g.act = act ? ACT_RELU : ACT_NONE;
         const int flags = up;   // bit 0: nearest-2x upsample fused into the gather; bit 1: the LDS-DMA kernel on operand planes split here (tests / probes: the model hands it
         up &= 1;                // planes its GroupNorm wrote); bit 2 (with bit 1): the general convolution variant also where the stride-1 one (MODE_CONV3S) applies
         const int oh = up ? 2 * H : H, ow = up ? 2 * W : W;
@@ -816,6 +818,43 @@ int bevgen_op_conv3x3(bevgen_ctx* ctx, const float* x, const float* w, const flo
         }
         launch_gemm(g, (hipStream_t)stream);
     });
+}
+
+int bevgen_op_conv3x3(bevgen_ctx* ctx, const float* x, const float* w, const float* bias, const float* residual, float* y, int n, int H, int W, int Cin, int Cout,
+                      int up, void* stream) {
+    return op_conv3x3_act(ctx, x, w, bias, residual, y, n, H, W, Cin, Cout, up, 0, stream);
+}
+
+int bevgen_op_conv3x3_act(bevgen_ctx* ctx, const float* x, const float* w, const float* bias, const float* residual, float* y, int n, int H, int W, int Cin, int Cout,
+                          int up, int act, void* stream) {
+    return op_conv3x3_act(ctx, x, w, bias, residual, y, n, H, W, Cin, Cout, up, act, stream);
+}
+
+int bevgen_op_maxpool2x2(bevgen_ctx* ctx, const float* x, float* y, void* planes, int n, int H, int W, int C, void* stream) {
+    return guarded(ctx, [&] {
+        BG_REQUIRE(x && y, "op_maxpool2x2: null argument");
+        launch_maxpool2x2(x, y, planes, n, H, W, C, (hipStream_t)stream);
+    });
+}
+
+int bevgen_op_lpips_tap(bevgen_ctx* ctx, const float* fa, const float* fb, const float* w, int n, int pixels, int C, double* out, void* stream) {
+    return guarded(ctx, [&] {
+        BG_REQUIRE(fa && fb && w && out && n >= 1 && pixels >= 1, "op_lpips_tap: bad arguments");
+        BG_REQUIRE(C == 64 || C == 128 || C == 256 || C == 512, "op_lpips_tap: C=%d (the VGG16 taps have 64, 128, 256 or 512 channels)", C);
+        double* partial;
+        ctx->arena.carve([&](Arena& ar) { partial = ar.get<double>((size_t)n * lpips_tap_blocks(pixels, C)); });
+        launch_lpips_tap(fa, fb, w, n, pixels, C, partial, out, 1, (hipStream_t)stream);
+    });
+}
+
+int bevgen_lpips_prepare(bevgen_ctx* ctx, const float* const* w, const float* const* bias, const float* const* lin, const float* shift, const float* scale, void* prepared,
+                         void* stream) {
+    return guarded(ctx, [&] { lpips_prepare(ctx->cfg.precision != BEVGEN_PRECISION_FP32, w, bias, lin, shift, scale, prepared, (hipStream_t)stream); });
+}
+
+int bevgen_lpips(bevgen_ctx* ctx, const void* prepared, const void* a, const void* b, int dtype, int n, int H, int W, int normalize, double* out, double* layers, void* work,
+                 void* stream) {
+    return guarded(ctx, [&] { lpips_run(ctx->cfg.precision != BEVGEN_PRECISION_FP32, prepared, a, b, dtype, n, H, W, normalize, out, layers, work, (hipStream_t)stream); });
 }
 
 int bevgen_op_groupnorm(bevgen_ctx* ctx, const float* x, const float* gamma, const float* beta, float* y, int n, int hw, int C, int swish, void* stream) {
@@ -1080,6 +1119,9 @@ int bevgen_op_attention_tiles(bevgen_ctx* ctx, const float* q, const float* k, c
 }
 
 int bevgen_decode_attention_splits(int B, int H, int n) { return decode_attention_splits(B, H, n); }
+
+long bevgen_lpips_prepared_bytes(int precision) { return lpips_prepared_bytes(precision); }
+long bevgen_lpips_workspace_bytes(int n, int H, int W, int precision) { return lpips_workspace_bytes(n, H, W, precision); }
 
 long bevgen_metrics_workspace_bytes(int op, int n, int C, int H, int W, int kernel_size) {
     return op == 0 ? image_sqerr_workspace_bytes(n, C, H, W) : op == 1 ? ssim_workspace_bytes(n, C, H, W, kernel_size) : -1;

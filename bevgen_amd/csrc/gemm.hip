@@ -77,7 +77,13 @@ __device__ __forceinline__ void store_tile(float* __restrict__ S, int tid, const
     }
 }
 
-template <int MODE>
+// FLUSH (GemmArgs::acc_flush, the LPIPS convolutions): the MFMA accumulator is a chain of K / 2 fp32 additions per output - 2304 at K = 9 x 512, a random walk of ~sqrt(2304)
+// roundings.  Every kAccFlush k-tiles (64 chain links) the chain is cut: the tile sums move into a second accumulator and the chain restarts from zero, a two-level sum of
+// 64 + K / 128 links.  Measured need: with the single chain the deep LPIPS taps missed 4 x the fp32 error of a blocked CPU convolution (experiments/r17.md).
+// Instantiations without FLUSH compile to the code they had.
+constexpr int kAccFlush = 4;
+
+template <int MODE, bool FLUSH = false>
 __global__ __launch_bounds__(256, 2) void gemm_f32_kernel(GemmArgs g) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float* As = smem;                    // [2][BM][LDSS]
@@ -116,6 +122,15 @@ __global__ __launch_bounds__(256, 2) void gemm_f32_kernel(GemmArgs g) {
         for (int j = 0; j < 2; ++j)
 #pragma unroll
             for (int q = 0; q < 16; ++q) acc[i][j][q] = 0.f;
+    f32x16 tot[FLUSH ? 2 : 1][FLUSH ? 2 : 1];
+    if constexpr (FLUSH) {
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+            for (int j = 0; j < 2; ++j)
+#pragma unroll
+                for (int q = 0; q < 16; ++q) tot[i][j][q] = 0.f;
+    }
 
     const int nk = g.K / BK;
     Frag4 ra, rb;
@@ -154,8 +169,27 @@ __global__ __launch_bounds__(256, 2) void gemm_f32_kernel(GemmArgs g) {
             store_tile(As + (cur ^ 1) * BM * LDSS, tid, ra);
             store_tile(Bs + (cur ^ 1) * BN * LDSS, tid, rb);
         }
+        if constexpr (FLUSH) {
+            if ((kt + 1) % kAccFlush == 0 || !more) {
+#pragma unroll
+                for (int i = 0; i < 2; ++i)
+#pragma unroll
+                    for (int j = 0; j < 2; ++j)
+#pragma unroll
+                        for (int q = 0; q < 16; ++q) {
+                            tot[i][j][q] += acc[i][j][q];
+                            acc[i][j][q] = 0.f;
+                        }
+            }
+        }
         __syncthreads();
         cur ^= 1;
+    }
+    if constexpr (FLUSH) {
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+            for (int j = 0; j < 2; ++j) acc[i][j] = tot[i][j];
     }
 
     // epilogue.  C/D layout of the 32x32 MFMA: col = lane&31, row = (reg&3) + 8*(reg>>2) + 4*(lane>>5)
@@ -175,6 +209,7 @@ __global__ __launch_bounds__(256, 2) void gemm_f32_kernel(GemmArgs g) {
                 float v = acc[i][j][q] * g.alpha + bn;
                 if (g.bias_m) v += g.bias_m[m];
                 if (g.act == ACT_GELU) v = gelu_erf(v);
+                else if (MODE != MODE_PLAIN && g.act == ACT_RELU) v = v < 0.f ? 0.f : v;   // (convolution instantiations only: the plain GEMMs keep their code)
                 if (R) v += R[(long)m * g.ldr + n];
                 C[(long)m * g.ldc + n] = v;
             }
@@ -187,6 +222,7 @@ void split_registry_set(const void* table) { g_split_table = reinterpret_cast<co
 
 void launch_gemm(const GemmArgs& g_in, hipStream_t stream) {
     const GemmArgs g = conv_defaults(g_in);
+    BG_REQUIRE(g.act != ACT_RELU || g.mode == MODE_CONV3, "gemm: the ReLU epilogue belongs to the convolution form");
     if (g.B_hi) return g.A_hi ? launch_gemm_split_glds(g, stream) : launch_gemm_split(g, stream);
     if (g_split_table && g.strideB == 0) {  // the executing context runs in split-precision mode and B is one of its (pre-split) weights
         auto it = g_split_table->find(g.B);
@@ -211,10 +247,14 @@ void launch_gemm(const GemmArgs& g_in, hipStream_t stream) {
     if (!attr_set[dslot].load(std::memory_order_acquire)) {
         HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_f32_kernel<MODE_PLAIN>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_f32_kernel<MODE_CONV3>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_f32_kernel<MODE_CONV3, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         attr_set[dslot].store(true, std::memory_order_release);
     }
     ProfScope prof(g.mode == MODE_CONV3 ? PROF_CONV3 : PROF_GEMM, 2.0 * g.M * (double)g.N * g.K * g.batch, stream);
-    if (g.mode == MODE_CONV3)
+    BG_REQUIRE(!g.acc_flush || g.mode == MODE_CONV3, "gemm: the two-level accumulation belongs to the convolution form");
+    if (g.mode == MODE_CONV3 && g.acc_flush)
+        hipLaunchKernelGGL((gemm_f32_kernel<MODE_CONV3, true>), grid, dim3(256), lds, stream, g);
+    else if (g.mode == MODE_CONV3)
         hipLaunchKernelGGL(gemm_f32_kernel<MODE_CONV3>, grid, dim3(256), lds, stream, g);
     else
         hipLaunchKernelGGL(gemm_f32_kernel<MODE_PLAIN>, grid, dim3(256), lds, stream, g);

@@ -225,6 +225,7 @@ __global__ __launch_bounds__(256, 2) void gemm_split_kernel(GemmArgs g) {
                 float v = (accM[i][j][q] + accC[i][j][q] * kLoInv) * g.alpha + bn;
                 if (g.bias_m) v += g.bias_m[m];
                 if (g.act == ACT_GELU) v = gelu_erf(v);
+                else if (MODE != MODE_PLAIN && g.act == ACT_RELU) v = v < 0.f ? 0.f : v;   // (convolution instantiations only: the plain GEMMs keep their code)
                 if (R) v += R[(long)m * g.ldr + n];
                 C[(long)m * g.ldc + n] = v;
             }

@@ -1217,6 +1217,7 @@ __device__ __forceinline__ void gemm_tile(const GemmArgs& g, const int tx, const
                     float t = a[e] * g.alpha + bmr[s2];
                     t += b4[e];
                     if (g.act == ACT_GELU) t = gelu_erf(t);
+                    else if (MODE != MODE_PLAIN && g.act == ACT_RELU) t = t < 0.f ? 0.f : t;   // (convolution instantiations only: the plain GEMMs keep their code)
                     o[e] = t + rres[s2][e];
                 }
                 if (m < g.M && n < g.N) *reinterpret_cast<f32x4*>(C + (long)m * g.ldc + n) = o;
@@ -1275,6 +1276,7 @@ __device__ __forceinline__ void gemm_tile(const GemmArgs& g, const int tx, const
                     float t = (accM[i][j][q] + accC[i][j][q] * kGLoInv) * g.alpha + bm[i];
                     t += bias4[j][qq][e];
                     if (g.act == ACT_GELU) t = gelu_erf(t);
+                    else if (MODE != MODE_PLAIN && g.act == ACT_RELU) t = t < 0.f ? 0.f : t;   // (convolution instantiations only: the plain GEMMs keep their code)
                     v[e] = t + rv[i][j][qq][e];
                 }
                 float* cp = C + (long)m * g.ldc + n;

@@ -7,7 +7,7 @@ namespace bevgen {
 
 // ---------------------------------------------------------------- gemm.hip
 enum { MODE_PLAIN = 0, MODE_CONV3 = 1, MODE_CONV3S = 2 };   // (MODE_CONV3S: kernel-template value only - launch_gemm_split_glds picks it for stride-1 / pad-1 / no-upsample convolutions; callers pass MODE_CONV3)
-enum { ACT_NONE = 0, ACT_GELU = 1 };
+enum { ACT_NONE = 0, ACT_GELU = 1, ACT_RELU = 2 };   // (ACT_RELU: max(0, acc + bias), NaN kept, MODE_CONV3 only - the VGG16 convolutions of lpips.cpp; the launchers refuse it on a plain GEMM)
 enum { EPI_PLAIN = 0, EPI_MUSE_Q = 1, EPI_GEGLU = 2, EPI_MUSE_KV = 3, EPI_MUSE_QKV = 4 };
 
 struct GemmArgs {
@@ -102,6 +102,7 @@ struct GemmArgs {
     unsigned sk_epoch = 0;
     int sk_tiles = 0;                 // filled in by the launcher
     bool sk_force = false;            // take the stream-K form whatever glds_sk_pays says (operator tests)
+    bool acc_flush = false;           // MODE_CONV3 on the exact-fp32 kernel (gemm.hip): two-level accumulation, the MFMA chain restarts every 4 k-tiles (the LPIPS convolutions)
     int ln_rows = 0;                  // row stride of the producer's statistics array (the whole problem's rows: a row-split launch keeps indexing by absolute row)
 };
 // (sum, sum of squares) per (32 columns, row) [groups][rows][2] -> (mean, rstd) per row [rows][2]; `count` real columns (the zero padding of a padded row adds nothing to either sum)
@@ -464,6 +465,28 @@ void launch_image_sqerr(const void* a, const void* b, int dtype, int n, int C, i
 // sums [n] (double) = per-image sum of the SSIM map [n, C, H - k + 1, W - k + 1] over the valid k x k Gaussian windows, moments about a per-tile shift; map (or null): the map
 void launch_ssim(const void* a, const void* b, int dtype, int n, int C, int H, int W, int k, double sigma, double data_range, double k1, double k2, double* sums, float* map,
                  void* work, hipStream_t s);
+
+// ---------------------------------------------------------------- lpips_kernels.hip / lpips.cpp (LPIPS with the VGG16 feature stack: losses/lpips.py:41-54, 57-64, 116-122)
+// a, b [m, 3, hw] (NCHW, fp32 or uint8 = v / 255) -> ONE batch of 2 m images (a's first), NHWC with the channels padded to 32 with zeros: (normalize: 2 x - 1, then)
+// (x - shift) / scale, fp32, one operation each.  shift_scale: 8 device floats (shift 0 .. 2, scale 4 .. 6).  y (fp32) and / or planes (the (hi, lo) image) may be null
+void launch_lpips_prep(const void* a, const void* b, int dtype, int m, int hw, int normalize, const float* shift_scale, float* y, void* planes, hipStream_t s);
+// MaxPool2d(2, 2) over NHWC [n, H, W, C] -> [n, H / 2, W / 2, C] (odd sizes floor; a NaN stays); y (fp32) and / or planes may be null.  planes = the (hi, lo) image of the
+// pooled tensor, bit for bit what launch_range_split writes for it at exponent 0.  C % 32 == 0
+void launch_maxpool2x2(const float* x, float* y, void* planes, int n, int H, int W, int C, hipStream_t s);
+// distance of one tap: fa, fb [n, pix, C] (C = 64, 128, 256 or 512), w [C] -> out[i * out_stride] = mean_p sum_c w_c (fa^ - fb^)^2, f^ = f / (sqrt(sum_c f^2) + 1e-10).
+// partial: n * lpips_tap_blocks(pix, C) doubles of workspace.  No atomics, a fixed order: the same bits on every run
+int lpips_tap_blocks(int pix, int C);
+void launch_lpips_tap(const float* fa, const float* fb, const float* w, int n, int pix, int C, double* partial, double* out, int out_stride, hipStream_t s);
+void launch_lpips_total(const double* layers /*[n, 5]*/, double* out /*[n]*/, int n, hipStream_t s);   // ((((d0 + d1) + d2) + d3) + d4)
+void launch_conv_weight_relayout(const float* w_oihw, float* w_ohwi, int Cout, int Cin, int Cin_pad, hipStream_t s);   // [Cout][Cin][3][3] -> [Cout][3][3][Cin_pad], zero padded
+// the whole metric (lpips.cpp).  split: the convolutions run the three-product f16 arithmetic on (hi, lo) planes (any split-precision context), else the exact-fp32 kernel
+int lpips_chunk(int H, int W, int precision);                        // image pairs per pass: a pure function of the image size and the precision
+long lpips_prepared_bytes(int precision);                            // -1: unknown precision
+long lpips_workspace_bytes(int n, int H, int W, int precision);      // -1: the call would be refused
+void lpips_prepare(bool split, const float* const* w_oihw /*[13]*/, const float* const* bias /*[13]*/, const float* const* lin /*[5]*/, const float* shift, const float* scale,
+                   void* prepared, hipStream_t s);
+void lpips_run(bool split, const void* prepared, const void* a, const void* b, int dtype, int n, int H, int W, int normalize, double* out, double* layers, void* work,
+               hipStream_t s);
 
 // misc
 void launch_fill(float* p, long n, float v, hipStream_t s);

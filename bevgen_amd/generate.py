@@ -13,7 +13,8 @@ is the README's inference command with ``python generate.py`` replaced.  Differe
 * ``--random-weights`` nulls every ``ckpt_path`` (deterministic generated weights) for smoke runs without the released checkpoints;
 * ``--metrics`` (off by default) accumulates PSNR / SSIM of gen-vs-gt and rec-vs-gt on the device over the batches that carry images (bevgen_amd/metrics.py, the
   PSNR / SSIM step of scripts/metrics_eval.py), prints the reference's lines at the end and writes ``<save_dir>/metrics_rank<r>.json``; with ``--synthetic`` it also
-  gives every synthetic scene seeded camera images, so that the run has a ground truth.
+  gives every synthetic scene seeded camera images, so that the run has a ground truth.  ``--lpips-weights FILE [FILE]`` (state dicts with the VGG16 features and the
+  LPIPS lin layers) adds LPIPS: the "PSIM/LPIPS" line in front of the other two and the states ``gen_lpips`` / ``rec_lpips`` in the JSON file.
 """
 from __future__ import annotations
 
@@ -115,6 +116,8 @@ def main(argv: List[str] = None) -> int:
     ap.add_argument("--seed", type=int, default=None)
     ap.add_argument("--metrics", action="store_true",
                     help="accumulate PSNR / SSIM of gen and rec against gt on the device and write <save_dir>/metrics_rank<r>.json (bevgen_amd/metrics.py)")
+    ap.add_argument("--lpips-weights", nargs="+", default=None, metavar="FILE",
+                    help="with --metrics: state dict file(s) holding the VGG16 features and the LPIPS lin layers; also accumulates LPIPS (gen_lpips / rec_lpips)")
     ap.add_argument("--print-config", action="store_true", help="print the composed configuration and exit")
     ap.add_argument("overrides", nargs="*")
     args = ap.parse_args(argv)
@@ -170,7 +173,7 @@ def main(argv: List[str] = None) -> int:
         log_dir = cfg.get("paths", {}).get("output_dir", ".") if isinstance(cfg.get("paths"), dict) else "."
         global_rank = rank
 
-    run_metrics = metrics.make_run_metrics() if args.metrics else None
+    run_metrics = metrics.make_run_metrics(lpips_weights=list(args.lpips_weights) if args.lpips_weights else None) if args.metrics else None
     n = 0
     with torch.no_grad():
         for i, batch in enumerate(batches):
@@ -191,6 +194,8 @@ def main(argv: List[str] = None) -> int:
         with open(os.path.join(out_dir, f"metrics_rank{rank}.json"), "w") as f:
             json.dump(metrics.metrics_state(run_metrics), f, indent=1)
         run_metrics["gen_psnr"].close()
+        if "gen_lpips" in run_metrics:
+            run_metrics["gen_lpips"].close()
     print(f"[bevgen_amd.generate] rank {rank}/{world}: wrote {n} scenes to {callbacks[0].save_dir or _Trainer.log_dir}")
     return 0
 

@@ -1,4 +1,4 @@
-"""PSNR and SSIM of generated / reconstructed views against ground truth, where the pixels already are (reference scripts/metrics_eval.py:29-132).
+"""PSNR, SSIM and LPIPS of generated / reconstructed views against ground truth, where the pixels already are (reference scripts/metrics_eval.py:29-132).
 
 ``PeakSignalNoiseRatio`` and ``StructuralSimilarityIndexMeasure`` take the constructor arguments ``metrics_eval.compute_metrics`` gives torchmetrics' classes of the
 same names; ``compute_metrics(pairs)`` is that function, ``python -m bevgen_amd.metrics DIR`` its directory form.  The sums run in libbevgen_hip's kernels
@@ -13,7 +13,16 @@ The contract is this definition, not a third-party implementation:
         a normalised Gaussian window (kernel_size, sigma) over the VALID window positions - which equals reflect-padding by (kernel_size - 1) / 2, filtering and cropping
         the pad - no clamp.
 That is what metrics_eval.py asks for through its constructor arguments.  torchmetrics' own arithmetic is not part of the reference tree and the package is not installed
-where this library is built, so parity with torchmetrics is UNPINNED ("Evaluation").  LPIPS and FID need pretrained networks and are out of scope.
+where this library is built, so parity with torchmetrics is UNPINNED ("Evaluation").
+
+  LPIPS ``LearnedPerceptualImagePatchSimilarity(net_type='vgg')``: the reference's modules/losses/lpips.py (41-54, 57-64, 116-122) in eval mode - (x - shift) / scale, the
+        thirteen 3x3 convolution + ReLU layers of VGG16 features[0:30] with their four 2x2 max-pools, and at relu1_2 .. relu5_3
+        d_k = mean_{h,w} sum_c lin_k[c] (fa^ - fb^)^2, f^ = f / (sqrt(sum_c f^2) + 1e-10); LPIPS = sum_k d_k per image pair (``Context.lpips``, csrc/lpips.cpp).
+        The network is a fixed description; its weights are an ordinary state_dict the user of the reference has on disk (``load_lpips_state``), like the VQGAN and
+        stage-2 checkpoints.  Inputs are [0, 1] images with normalize=False, as metrics_eval.py feeds them.  torchmetrics' host-side check that the inputs lie in the
+        expected range (scripts/lpip.py:40-43, 136) would need a synchronising device-to-host min / max per update and is NOT reproduced.  Parity with the `lpips` /
+        torchmetrics packages is unpinned like the other two.
+FID needs an Inception network plus a matrix square root and stays out of scope.
 """
 from __future__ import annotations
 
@@ -104,6 +113,70 @@ class _Metric:
         return self
 
 
+# ---- LPIPS weights ----------------------------------------------------------------------------------------------------------------------------------------------------
+LPIPS_CONV_INDEX = (0, 2, 5, 7, 10, 12, 14, 17, 19, 21, 24, 26, 28)      # torchvision's vgg16().features indices of the thirteen convolutions
+LPIPS_CONV_SHAPES = ((64, 3), (64, 64), (128, 64), (128, 128), (256, 128), (256, 256), (256, 256), (512, 256), (512, 512), (512, 512), (512, 512), (512, 512), (512, 512))
+LPIPS_TAP_CHANNELS = (64, 128, 256, 512, 512)
+LPIPS_SHIFT, LPIPS_SCALE = (-0.030, -0.088, -0.188), (0.458, 0.448, 0.450)
+LPIPS_WEIGHT_FILES = ("vgg.pth (the lin layers, taming's vgg_lpips checkpoint)", "the VGG16 features state_dict (torchvision's vgg16, IMAGENET1K_V1)")
+
+
+def _lpips_slice(index: int) -> int:
+    return 1 if index < 4 else 2 if index < 9 else 3 if index < 16 else 4 if index < 23 else 5
+
+
+def load_lpips_state(*sources) -> Dict[str, Any]:
+    """Merges state dicts (mappings, or paths given to torch.load) into {'conv_w': 13 x [Cout, Cin, 3, 3], 'conv_b': 13 x [Cout], 'lin': 5 x [C_k], 'shift': [3],
+    'scale': [3]} (float32, CPU).  Three key spellings are accepted: the reference's (net.slice{1..5}.{N}.{weight,bias}, lin{k}.model.1.weight, optional
+    scaling_layer.{shift,scale}), torchvision's features.{N}.{weight,bias} for the same N, and lin{k}.model.0.weight (a NetLinLayer built without dropout).  Every shape
+    is checked and whatever is missing is named."""
+    merged: Dict[str, Any] = {}
+    for src in sources:
+        if not isinstance(src, Mapping):
+            src = torch.load(src, map_location="cpu")
+        if isinstance(src, Mapping) and "state_dict" in src and isinstance(src["state_dict"], Mapping):
+            src = src["state_dict"]
+        merged.update(src)
+
+    def pick(names):
+        for nm in names:
+            if nm in merged:
+                return nm, torch.as_tensor(merged[nm]).detach().to("cpu", torch.float32)
+        return None, None
+
+    missing: List[str] = []
+    out: Dict[str, Any] = {"conv_w": [], "conv_b": [], "lin": []}
+    for idx, (co, ci) in zip(LPIPS_CONV_INDEX, LPIPS_CONV_SHAPES):
+        for kind, shape, dst in (("weight", (co, ci, 3, 3), "conv_w"), ("bias", (co,), "conv_b")):
+            names = (f"net.slice{_lpips_slice(idx)}.{idx}.{kind}", f"features.{idx}.{kind}")
+            nm, t = pick(names)
+            if t is None:
+                missing.append(" or ".join(names))
+                continue
+            if tuple(t.shape) != shape:
+                raise ValueError(f"load_lpips_state: {nm} has shape {tuple(t.shape)}, VGG16 needs {shape}")
+            out[dst].append(t.contiguous())
+    for k, c in enumerate(LPIPS_TAP_CHANNELS):
+        names = (f"lin{k}.model.1.weight", f"lin{k}.model.0.weight")
+        nm, t = pick(names)
+        if t is None:
+            missing.append(" or ".join(names))
+            continue
+        if t.numel() != c or tuple(t.shape) not in ((1, c, 1, 1), (c,), (1, c)):
+            raise ValueError(f"load_lpips_state: {nm} has shape {tuple(t.shape)}, lin{k} needs (1, {c}, 1, 1)")
+        out["lin"].append(t.reshape(c).contiguous())
+    if missing:
+        raise ValueError("load_lpips_state: missing " + "; ".join(missing) + " - LPIPS needs " + " and ".join(LPIPS_WEIGHT_FILES))
+    for key, default in (("shift", LPIPS_SHIFT), ("scale", LPIPS_SCALE)):
+        nm, t = pick((f"scaling_layer.{key}",))
+        if t is None:
+            t = torch.tensor(default, dtype=torch.float32)
+        if t.numel() != 3:
+            raise ValueError(f"load_lpips_state: {nm} has shape {tuple(t.shape)}, the scaling layer has 3 channels")
+        out[key] = t.reshape(3).contiguous()
+    return out
+
+
 class PeakSignalNoiseRatio(_Metric):
     """10 log10(R^2 / mse) over everything seen; R = data_range, or (None) max - min of the targets seen."""
     _STATES = (("sse", torch.float64, 0.0), ("count", torch.int64, 0), ("min", torch.float32, float("inf")), ("max", torch.float32, float("-inf")))
@@ -158,31 +231,109 @@ class StructuralSimilarityIndexMeasure(_Metric):
         return self.sum / self.images.double()
 
 
-def _report(ssim_value: float, psnr_value: float, label: str = "") -> None:
+class LearnedPerceptualImagePatchSimilarity(_Metric):
+    """LPIPS (VGG16) of preds against target: mean / sum over every image pair seen, or (reduction='none') the per-image scores of the last update - what
+    filter_generated.py reads.  weights: what load_lpips_state takes (a path, a state dict, or a sequence of them) or its result.  Without `ctx` the metric makes its own
+    context with precision='f16x3' (the drop-in modules' default); a passed context is used as it is.  The input range is not checked (module docstring)."""
+    _STATES = (("sum_scores", torch.float64, 0.0), ("total", torch.int64, 0))
+
+    def __init__(self, net_type: str = "vgg", reduction: str = "mean", normalize: bool = False, weights=None, ctx=None):
+        if net_type != "vgg":
+            raise NotImplementedError(f"net_type {net_type!r}: only the VGG16 LPIPS ('vgg'), the one the reference uses, is implemented")
+        if reduction not in ("mean", "sum", "none"):
+            raise ValueError(f"reduction must be 'mean', 'sum' or 'none', got {reduction!r}")
+        if weights is None:
+            raise ValueError("LearnedPerceptualImagePatchSimilarity needs weights=: " + " and ".join(LPIPS_WEIGHT_FILES))
+        if isinstance(weights, Mapping) and "conv_w" in weights:
+            self.weights = weights
+        else:
+            self.weights = load_lpips_state(*(weights if isinstance(weights, (list, tuple)) else (weights,)))
+        self.net_type, self.reduction, self.normalize = net_type, reduction, bool(normalize)
+        self._prepared, self._prepared_for, self.last_scores = None, None, None
+        super().__init__(ctx)
+
+    def context(self):
+        if self._ctx is None:
+            from .runtime import Context
+
+            self._ctx, self._own_ctx = Context(None, precision="f16x3"), True   # (raises "no CPU path in the product" without a GPU)
+        return self._ctx
+
+    def _fresh(self):
+        one = LearnedPerceptualImagePatchSimilarity(self.net_type, self.reduction, self.normalize, self.weights)
+        one._prepared, one._prepared_for = self._prepared, self._prepared_for
+        return one
+
+    def _ensure_prepared(self, ctx):
+        """the weights in the form this context's kernels read, made once per context"""
+        if self._prepared is None or self._prepared_for is not ctx:
+            self._prepared, self._prepared_for = ctx.lpips_prepare(self.weights), ctx
+        return self._prepared
+
+    def __call__(self, preds, target):
+        self._ensure_prepared(self.context())   # (so that the one-batch metric of _Metric.__call__ shares them)
+        return super().__call__(preds, target)
+
+    def update(self, preds, target):
+        ctx, a, b = self._pair(preds, target)
+        scores = ctx.lpips(self._ensure_prepared(ctx), a, b, normalize=self.normalize)
+        self.last_scores = scores
+        self.sum_scores = self.sum_scores + scores.sum()
+        self.total = self.total + scores.numel()
+
+    def merge_state(self, other):
+        super().merge_state(other)
+        if isinstance(other, LearnedPerceptualImagePatchSimilarity) and other.last_scores is not None:
+            self.last_scores = other.last_scores
+        return self
+
+    def compute(self) -> torch.Tensor:
+        if int(self.total.item()) == 0:
+            raise RuntimeError("LearnedPerceptualImagePatchSimilarity.compute() before any update()")
+        if self.reduction == "none":
+            if self.last_scores is None:
+                raise RuntimeError("reduction='none' returns the last update's per-image scores; a merged or loaded state has none")
+            return self.last_scores
+        return self.sum_scores / self.total.double() if self.reduction == "mean" else self.sum_scores
+
+
+def _report(ssim_value: float, psnr_value: float, label: str = "", lpips_value: Optional[float] = None) -> None:
+    if lpips_value is not None:
+        print(f"{label}PSIM/LPIPS Score for dataset is: {lpips_value:.2f}")
     print(f"{label}SSIM Score for dataset is: {ssim_value:.2f}")
     print(f"{label}PSNR Score for dataset is: {psnr_value:.2f}")
 
 
-def compute_metrics(pairs: Iterable, ctx=None) -> Dict[str, float]:
-    """metrics_eval.compute_metrics without LPIPS: `pairs` yields (gt, gen) batches; prints the reference's two lines and returns {'ssim', 'psnr'}."""
+def compute_metrics(pairs: Iterable, ctx=None, lpips_weights=None) -> Dict[str, float]:
+    """metrics_eval.compute_metrics: `pairs` yields (gt, gen) batches; prints the reference's lines and returns {'ssim', 'psnr'}.  With lpips_weights (what
+    LearnedPerceptualImagePatchSimilarity takes as weights=) the "PSIM/LPIPS" line comes first, as in the reference, and the result also holds 'lpips'; without them
+    the output and the result are the two-metric ones."""
     psnr, ssim = PeakSignalNoiseRatio(ctx=ctx), StructuralSimilarityIndexMeasure(data_range=1.0, ctx=ctx)
+    lp = LearnedPerceptualImagePatchSimilarity(weights=lpips_weights, ctx=ctx) if lpips_weights is not None else None
     if ctx is None:
         ssim._ctx = psnr.context()
     for gt, gen in pairs:
+        if lp is not None:
+            lp.update(gen, gt)
         ssim.update(gen, gt)
         psnr.update(gen, gt)
     out = {"ssim": float(ssim.compute().item()), "psnr": float(psnr.compute().item())}
+    if lp is not None:
+        out["lpips"] = float(lp.compute().item())
+        lp.close()
     psnr.close()
-    _report(out["ssim"], out["psnr"])
+    _report(out["ssim"], out["psnr"], lpips_value=out.get("lpips"))
     return out
 
 
 # ---- generate.py --metrics --------------------------------------------------------------------------------------------------------------------------------------------
 METRIC_KEYS = ("gen_psnr", "gen_ssim", "rec_psnr", "rec_ssim")
+LPIPS_KEYS = ("gen_lpips", "rec_lpips")   # present only in a run with --lpips-weights
 
 
-def make_run_metrics(ctx=None) -> Dict[str, _Metric]:
-    """the four states a generate run accumulates: gen-vs-gt and rec-vs-gt, on ONE context"""
+def make_run_metrics(ctx=None, lpips_weights=None) -> Dict[str, _Metric]:
+    """the four states a generate run accumulates: gen-vs-gt and rec-vs-gt, on ONE context; with lpips_weights also LPIPS_KEYS (their two metrics share one context
+    of their own, precision f16x3, unless `ctx` is given)"""
     first = PeakSignalNoiseRatio(ctx=ctx)
     out: Dict[str, _Metric] = {"gen_psnr": first, "gen_ssim": StructuralSimilarityIndexMeasure(ctx=ctx), "rec_psnr": PeakSignalNoiseRatio(ctx=ctx),
                                "rec_ssim": StructuralSimilarityIndexMeasure(ctx=ctx)}
@@ -190,6 +341,14 @@ def make_run_metrics(ctx=None) -> Dict[str, _Metric]:
         shared = first.context()
         for m in out.values():
             m._ctx = shared
+    if lpips_weights is not None:
+        state = lpips_weights if isinstance(lpips_weights, Mapping) and "conv_w" in lpips_weights else load_lpips_state(
+            *(lpips_weights if isinstance(lpips_weights, (list, tuple)) else (lpips_weights,)))
+        gen = LearnedPerceptualImagePatchSimilarity(weights=state, ctx=ctx)
+        rec = LearnedPerceptualImagePatchSimilarity(weights=state, ctx=ctx)
+        if ctx is None and torch.cuda.is_available():
+            rec._ctx = gen.context()
+        out["gen_lpips"], out["rec_lpips"] = gen, rec
     return out
 
 
@@ -204,11 +363,13 @@ def accumulate_metrics(metrics: Mapping[str, _Metric], outputs: Mapping[str, Any
         if x is not None:
             metrics[f"{split}_psnr"].update(x, gt)
             metrics[f"{split}_ssim"].update(x, gt)
+            if f"{split}_lpips" in metrics:
+                metrics[f"{split}_lpips"].update(x, gt)
     return _planes(gt, "gt").shape[0]
 
 
 def metrics_state(metrics: Mapping[str, _Metric]) -> Dict[str, Dict[str, Any]]:
-    return {k: metrics[k].state() for k in METRIC_KEYS}
+    return {k: metrics[k].state() for k in METRIC_KEYS + tuple(k for k in LPIPS_KEYS if k in metrics)}
 
 
 def report_metrics(metrics: Mapping[str, _Metric]) -> Dict[str, Optional[float]]:
@@ -220,7 +381,10 @@ def report_metrics(metrics: Mapping[str, _Metric]) -> Dict[str, Optional[float]]
             out[f"{split}_ssim"] = out[f"{split}_psnr"] = None
             continue
         out[f"{split}_ssim"], out[f"{split}_psnr"] = float(s.compute().item()), float(p.compute().item())
-        _report(out[f"{split}_ssim"], out[f"{split}_psnr"], label=f"[{split}] ")
+        lp = metrics.get(f"{split}_lpips")
+        if lp is not None:
+            out[f"{split}_lpips"] = float(lp.compute().item())
+        _report(out[f"{split}_ssim"], out[f"{split}_psnr"], label=f"[{split}] ", lpips_value=out.get(f"{split}_lpips"))
     return out
 
 
@@ -260,8 +424,9 @@ def _load_u8(path: str) -> torch.Tensor:
     return torch.from_numpy(a.copy()).permute(2, 0, 1)
 
 
-def evaluate_directory(dataset_dir: str, argoverse: bool = False, rec: bool = False, batch_size: int = 20, ctx=None) -> Tuple[PeakSignalNoiseRatio, StructuralSimilarityIndexMeasure]:
-    """PIL decode on the host, uint8 upload, the uint8 kernels; images of one size are batched."""
+def evaluate_directory(dataset_dir: str, argoverse: bool = False, rec: bool = False, batch_size: int = 20, ctx=None, lpips=None):
+    """PIL decode on the host, uint8 upload, the uint8 kernels; images of one size are batched.  -> (psnr, ssim); `lpips` (a LearnedPerceptualImagePatchSimilarity)
+    is updated with the same batches."""
     gt_tree, other_tree, rel, dropped = directory_pairs(dataset_dir, argoverse, rec)
     if dropped:
         print(f"Removed at least {dropped}")
@@ -274,6 +439,8 @@ def evaluate_directory(dataset_dir: str, argoverse: bool = False, rec: bool = Fa
     def flush():
         if gts:
             g, o = torch.stack(gts), torch.stack(others)
+            if lpips is not None:
+                lpips.update(o, g)
             ssim.update(o, g)
             psnr.update(o, g)
             gts.clear()
@@ -290,29 +457,42 @@ def evaluate_directory(dataset_dir: str, argoverse: bool = False, rec: bool = Fa
 
 
 def main(argv: Optional[List[str]] = None) -> int:
-    ap = argparse.ArgumentParser(prog="python -m bevgen_amd.metrics", description="PSNR / SSIM of a generated tree against its ground truth (metrics_eval.py without LPIPS / FID)")
+    ap = argparse.ArgumentParser(prog="python -m bevgen_amd.metrics", description="PSNR / SSIM (and, with --lpips-weights, LPIPS) of a generated tree against its ground truth "
+                                 "(metrics_eval.py without FID)")
     ap.add_argument("dataset_dir", nargs="?", default=None, help="directory holding gt/ and gen/ (rec/), or with --argoverse sample_gt/ and sample/")
     ap.add_argument("--argoverse", action="store_true")
     ap.add_argument("--rec", action="store_true", help="compare rec/ instead of gen/")
     ap.add_argument("--merge", nargs="*", default=[], metavar="STATE.json", help="metrics_rank<r>.json files of a generate --metrics run (or files written by --save) to add")
     ap.add_argument("--save", default=None, metavar="STATE.json", help="write the merged states here")
+    ap.add_argument("--lpips-weights", nargs="+", default=None, metavar="FILE", help="state dict file(s) holding the VGG16 features and the LPIPS lin layers: also report PSIM/LPIPS")
     args = ap.parse_args(argv)
     if args.dataset_dir is None and not args.merge:
         ap.error("pass a dataset directory, --merge files, or both")
     split = "rec" if args.rec else "gen"
+    lp = LearnedPerceptualImagePatchSimilarity(weights=list(args.lpips_weights)) if args.lpips_weights else None
     if args.dataset_dir is not None:
-        psnr, ssim = evaluate_directory(args.dataset_dir, args.argoverse, args.rec)
+        psnr, ssim = evaluate_directory(args.dataset_dir, args.argoverse, args.rec, lpips=lp)
     else:
         psnr, ssim = PeakSignalNoiseRatio(), StructuralSimilarityIndexMeasure(data_range=1.0)
+    lp_state: Optional[Dict[str, Any]] = lp.state() if lp is not None else None   # (--merge adds LPIPS states where the files carry them, with or without weights here)
     for path in args.merge:
         with open(path) as f:
             d = json.load(f)
         psnr.merge_state(d[f"{split}_psnr"])
         ssim.merge_state(d[f"{split}_ssim"])
-    _report(float(ssim.compute().item()), float(psnr.compute().item()))
+        if f"{split}_lpips" in d:
+            theirs = d[f"{split}_lpips"]
+            lp_state = dict(theirs) if lp_state is None else {"sum_scores": lp_state["sum_scores"] + theirs["sum_scores"], "total": lp_state["total"] + theirs["total"]}
+    lp_value = lp_state["sum_scores"] / lp_state["total"] if lp_state is not None and lp_state["total"] > 0 else None
+    _report(float(ssim.compute().item()), float(psnr.compute().item()), lpips_value=lp_value)
     if args.save:
+        saved = {f"{split}_psnr": psnr.state(), f"{split}_ssim": ssim.state()}
+        if lp_state is not None:
+            saved[f"{split}_lpips"] = lp_state
         with open(args.save, "w") as f:
-            json.dump({f"{split}_psnr": psnr.state(), f"{split}_ssim": ssim.state()}, f)
+            json.dump(saved, f)
+    if lp is not None:
+        lp.close()
     psnr.close()
     return 0
 

@@ -726,16 +726,88 @@ class Context:
                                                      _ptr(layout), int(block), B, int(G), H, int(n), Lmax, int(prefix), int(split), _ptr(out), self._s()))
         return out
 
-    def op_conv3x3(self, x_nhwc, w_ohwi, bias, residual=None, upsample=False, kernel="auto"):
+    def op_conv3x3(self, x_nhwc, w_ohwi, bias, residual=None, upsample=False, kernel="auto", act=None):
         """kernel: 'auto' (fp32 input: the register-staged kernel), 'dma' (the LDS-DMA kernel on planes split inside the call), 'dma_general' (its general variant
-        also where the stride-1 variant applies)."""
+        also where the stride-1 variant applies).  act: None, or 'relu' = max(0, acc + bias) in the epilogue (bevgen_op_conv3x3_act)."""
+        if act not in (None, "relu"):
+            raise ValueError(f"op_conv3x3: act must be None or 'relu', got {act!r}")
         n, H, W, Cin = x_nhwc.shape
         Cout = w_ohwi.shape[0]
         oh, ow = (2 * H, 2 * W) if upsample else (H, W)
         y = torch.empty((n, oh, ow, Cout), dtype=torch.float32, device=self.device)
         flags = int(upsample) | {"auto": 0, "dma": 2, "dma_general": 6}[kernel]
-        self._check(self.lib.bevgen_op_conv3x3(self._h, _ptr(x_nhwc), _ptr(w_ohwi), _ptr(bias), _ptr(residual), _ptr(y), n, H, W, Cin, Cout, flags, self._s()))
+        if act is None:
+            self._check(self.lib.bevgen_op_conv3x3(self._h, _ptr(x_nhwc), _ptr(w_ohwi), _ptr(bias), _ptr(residual), _ptr(y), n, H, W, Cin, Cout, flags, self._s()))
+        else:
+            self._check(self.lib.bevgen_op_conv3x3_act(self._h, _ptr(x_nhwc), _ptr(w_ohwi), _ptr(bias), _ptr(residual), _ptr(y), n, H, W, Cin, Cout, flags, 1, self._s()))
         return y
+
+    # LPIPS (csrc/lpips.cpp, lpips_kernels.hip; bevgen_amd/metrics.py builds LearnedPerceptualImagePatchSimilarity on it)
+    def op_maxpool2x2(self, x_nhwc, planes=False):
+        """MaxPool2d(2, 2) over NHWC fp32 [n, H, W, C] (C % 32 == 0; odd sizes floor) -> y [n, H // 2, W // 2, C]; planes=True: (y, planes) with planes
+        [n (H // 2) (W // 2), C / 32, 2, 32] float16 = the (hi, lo) image of y written by the same pass (op_range_split's layout at exponent 0)."""
+        n, H, W, Cc = x_nhwc.shape
+        y = torch.empty((n, H // 2, W // 2, Cc), dtype=torch.float32, device=self.device)
+        pl = torch.empty((n * (H // 2) * (W // 2), Cc // 32, 2, 32), dtype=torch.float16, device=self.device) if planes else None
+        self._check(self.lib.bevgen_op_maxpool2x2(self._h, _ptr(x_nhwc), _ptr(y), _ptr(pl), n, H, W, Cc, self._s()))
+        return (y, pl) if planes else y
+
+    def op_lpips_tap(self, fa, fb, w):
+        """d [n] float64 = mean over the pixels of sum_c w_c (fa^ - fb^)^2, f^ = f / (sqrt(sum_c f^2) + 1e-10): fa, fb [n, pixels, C] fp32 (C = 64, 128, 256 or 512)."""
+        if fa.shape != fb.shape or fa.dim() != 3:
+            raise ValueError(f"op_lpips_tap: features are two [n, pixels, C] tensors, got {tuple(fa.shape)} and {tuple(fb.shape)}")
+        n, pix, Cc = fa.shape
+        out = torch.empty((n,), dtype=torch.float64, device=self.device)
+        self._check(self.lib.bevgen_op_lpips_tap(self._h, _ptr(fa), _ptr(fb), _ptr(w), n, pix, Cc, _ptr(out), self._s()))
+        return out
+
+    def _precision_code(self):
+        return int(self._c.precision)
+
+    def lpips_prepare(self, state):
+        """state: what metrics.load_lpips_state returns ({'conv_w': 13 tensors [Cout, Cin, 3, 3], 'conv_b': 13, 'lin': 5 vectors, 'shift', 'scale'}) -> the prepared
+        weight image, a uint8 device tensor this context's lpips() reads (it belongs to this context's precision)."""
+        dev = self.device
+        ws = [_req(t, torch.float32, dev, "conv weight") for t in state["conv_w"]]
+        bs = [_req(t, torch.float32, dev, "conv bias") for t in state["conv_b"]]
+        lins = [_req(t.reshape(-1), torch.float32, dev, "lin") for t in state["lin"]]
+        if len(ws) != 13 or len(bs) != 13 or len(lins) != 5:
+            raise ValueError("lpips_prepare: needs 13 convolution weights, 13 biases and 5 lin vectors (metrics.load_lpips_state)")
+        shift, scale = _req(state["shift"].reshape(-1), torch.float32, dev, "shift"), _req(state["scale"].reshape(-1), torch.float32, dev, "scale")
+        nbytes = int(self.lib.bevgen_lpips_prepared_bytes(self._precision_code()))
+        if nbytes < 0:
+            raise ValueError("lpips_prepare: this context's precision has no LPIPS path")
+        prepared = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+        arr = lambda ts: (C.c_void_p * len(ts))(*[t.data_ptr() for t in ts])
+        self._check(self.lib.bevgen_lpips_prepare(self._h, arr(ws), arr(bs), arr(lins), _ptr(shift), _ptr(scale), _ptr(prepared), self._s()))
+        self.synchronize()   # (the sources may be freed when this returns; a weight outside the f16 range is reported here)
+        return prepared
+
+    def lpips(self, prepared, a, b, normalize=False, return_layers=False, check=True):
+        """LPIPS (VGG16) per image pair -> scores [n] float64 on the device (return_layers: (scores, layers [n, 5])).  a, b [n, 3, H, W] or [B, cams, 3, H, W], both fp32
+        (nominally in [0, 1]; normalize=True maps x -> 2 x - 1 first, as the reference's metric class does for [0, 1] inputs it rescales - metrics_eval.py feeds [0, 1]
+        images with normalize=False, the default here) or both uint8 (v / 255).  H, W >= 16.  torchmetrics' host-side check that the inputs lie in the expected range
+        is not reproduced: it would need a synchronising min / max per call."""
+        if a.shape != b.shape or a.dtype != b.dtype:
+            raise ValueError(f"lpips: preds {tuple(a.shape)} {a.dtype} and target {tuple(b.shape)} {b.dtype} differ in shape or dtype")
+        if a.dim() == 5:
+            a, b = a.reshape(-1, *a.shape[2:]), b.reshape(-1, *b.shape[2:])
+        if a.dim() != 4 or a.shape[1] != 3:
+            raise ValueError(f"lpips: images are [n, 3, H, W] or [B, cams, 3, H, W], got {tuple(a.shape)}")
+        if a.dtype not in (torch.float32, torch.uint8):
+            raise ValueError(f"lpips: images are float32 or uint8, got {a.dtype}")
+        a, b = _req(a, a.dtype, self.device, "preds"), _req(b, b.dtype, self.device, "target")
+        n, _, H, W = a.shape
+        nbytes = int(self.lib.bevgen_lpips_workspace_bytes(n, H, W, self._precision_code()))
+        if nbytes < 0:
+            raise ValueError(f"lpips: images [{n}, 3, {H}, {W}] are refused (needs n >= 1, H and W >= 16 so that relu5_3 has a pixel, H W <= 2^21)")
+        work = torch.empty((nbytes,), dtype=torch.uint8, device=self.device)
+        out = torch.empty((n,), dtype=torch.float64, device=self.device)
+        layers = torch.empty((n, 5), dtype=torch.float64, device=self.device) if return_layers else None
+        self._check(self.lib.bevgen_lpips(self._h, _ptr(prepared), _ptr(a), _ptr(b), self._METRIC_DTYPES[a.dtype], n, H, W, int(bool(normalize)), _ptr(out), _ptr(layers),
+                                          _ptr(work), self._s()))
+        self._done(check)
+        return (out, layers) if return_layers else out
 
     def op_groupnorm(self, x_nhwc, gamma, beta, swish=True):
         n, H, W, Cc = x_nhwc.shape

@@ -491,6 +491,36 @@ int bevgen_op_image_sqerr(bevgen_ctx* ctx, const void* d_a, const void* d_b, int
  * halo), which is added back to the means only: E[x^2] - mu^2 then cancels on the local contrast, not on the level.  d_map (or NULL): the fp32 map [n, C, H-k+1, W-k+1]. */
 int bevgen_op_ssim(bevgen_ctx* ctx, const void* d_a, const void* d_b, int dtype, int n, int C, int H, int W, int kernel_size, double sigma, double data_range, double k1,
                    double k2, double* d_sums /* [n] */, float* d_map /* or NULL */, void* d_work, void* stream);
+/* LPIPS with the VGG16 feature stack (the reference's modules/losses/lpips.py:41-54, 57-64, 116-122; the "PSIM/LPIPS" line of scripts/metrics_eval.py), eval mode.
+ *   x' = (x - shift) / scale per channel (after 2 x - 1 with normalize != 0), fp32, one operation each; uint8 pixels are v / 255 (one fp32 division)
+ *   VGG16 features[0:30]: thirteen 3x3 convolutions (stride 1, zero padding 1) with bias and ReLU, MaxPool2d(2, 2) (odd sizes floor) in front of convolutions 2, 4, 7, 10;
+ *   taps relu1_2, relu2_2, relu3_3, relu4_3, relu5_3 (64, 128, 256, 512, 512 channels)
+ *   d_k = mean_{h,w} sum_c lin_k[c] (fa^ - fb^)^2, f^ = f / (sqrt(sum_c f^2) + 1e-10): fp32 per element in that order, the spatial sum in double in a fixed order, no
+ *   atomics (two calls give the same bits; image i's value does not depend on the batch); LPIPS = (((d_0 + d_1) + d_2) + d_3) + d_4 per image pair.
+ * A context of precision FP32 runs the convolutions on the exact-fp32 kernel, every other precision on the three-product f16 kernel ((hi, lo) operand planes: a NaN or
+ * |v| >= 65520 activation or weight raises BEVGEN_STATUS_F16_RANGE).  Parity with the `lpips` / torchmetrics packages is unpinned (neither is part of the reference tree);
+ * torchmetrics' host-side range check of the inputs is not reproduced.
+ * bevgen_lpips_prepare: the thirteen weights d_w[l] [Cout][Cin][3][3] and biases d_bias[l] [Cout] (h_w, h_bias: HOST arrays of 13 device pointers, in network order),
+ * h_lin: 5 device pointers to the non-negative lin vectors [C_k], d_shift / d_scale [3] -> d_prepared (bevgen_lpips_prepared_bytes(precision) bytes of caller memory,
+ * 256-byte aligned): weights re-laid to [Cout][3][3][Cin] (the first layer's Cin padded to 32 with zeros) and, on a split-precision context, their (hi, lo) planes.  Once per
+ * checkpoint; d_prepared belongs to the precision of the context that wrote it.
+ * bevgen_lpips: d_a, d_b [n, 3, H, W] contiguous, of ONE dtype (BEVGEN_DTYPE_F32 or _U8) -> d_out [n] and, with d_layers non-NULL, the five d_k per pair [n, 5].  Pairs run
+ * in chunks whose size depends on (H, W, precision) only, a and b of a chunk as one batch.  d_work: bevgen_lpips_workspace_bytes(n, H, W, precision) bytes, 256-byte aligned,
+ * not kept between calls.  Refused with BEVGEN_ERR_INVALID before any launch: H or W < 16 (relu5_3 would have no pixel), n < 1, H W > 2^21, another dtype. */
+int bevgen_lpips_prepare(bevgen_ctx* ctx, const float* const* h_w, const float* const* h_bias, const float* const* h_lin, const float* d_shift, const float* d_scale,
+                         void* d_prepared, void* stream);
+int bevgen_lpips(bevgen_ctx* ctx, const void* d_prepared, const void* d_a, const void* d_b, int dtype, int n, int H, int W, int normalize, double* d_out /* [n] */,
+                 double* d_layers /* [n, 5] or NULL */, void* d_work, void* stream);
+/* Its building blocks on caller tensors.  conv3x3_act: bevgen_op_conv3x3 with an activation in the epilogue, act 0 = none, 1 = ReLU: max(0, acc + bias) (+ residual), a NaN
+ * stays; no separate pass over the tensor.
+ * maxpool2x2: d_x [n, H, W, C] NHWC -> d_y [n, H / 2, W / 2, C] (MaxPool2d(2, 2): odd sizes floor, a NaN stays) and, with d_planes non-NULL, the (hi, lo) f16 plane image
+ * [n (H / 2) (W / 2)][C / 32][2][32] of the pooled tensor in the same pass, bit for bit what bevgen_op_range_split writes for it at exponent 0 (out-of-range values raise
+ * BEVGEN_STATUS_F16_RANGE).  C % 32 == 0; H, W >= 2.
+ * lpips_tap: d_out[i] = d_k of the feature pair d_fa[i], d_fb[i] [pixels, C] with the weights d_w [C]; C = 64, 128, 256 or 512. */
+int bevgen_op_conv3x3_act(bevgen_ctx* ctx, const float* d_x_nhwc, const float* d_w_ohwi, const float* d_bias, const float* d_residual,
+                          float* d_y_nhwc, int n, int H, int W, int Cin, int Cout, int upsample2x, int act, void* stream);
+int bevgen_op_maxpool2x2(bevgen_ctx* ctx, const float* d_x_nhwc, float* d_y_nhwc, void* d_planes /* or NULL */, int n, int H, int W, int C, void* stream);
+int bevgen_op_lpips_tap(bevgen_ctx* ctx, const float* d_fa, const float* d_fb, const float* d_w, int n, int pixels, int C, double* d_out /* [n] */, void* stream);
 /* vq_quantize: VectorQuantizer2.forward's arg-min, d_ids[r] = argmin_j (|z_r|^2 + |e_j|^2) - 2 z_r . e_j with the lowest index on ties; d_z [rows, D], d_codebook [n_e, D],
  * D % 32 == 0; d_zz [rows] / d_ee [n_e] (or NULL) receive the squared norms.  A row without a finite distance gets id 0 and raises BEVGEN_STATUS_NONFINITE_LATENTS. */
 int bevgen_op_vq_quantize(bevgen_ctx* ctx, const float* d_z, const float* d_codebook, int64_t* d_ids, float* d_zz /* or NULL */, float* d_ee /* or NULL */, long rows, int n_e,
@@ -569,6 +599,10 @@ int bevgen_op_attention_tiles(bevgen_ctx* ctx, const float* d_q, const float* d_
 int bevgen_decode_attention_splits(int B, int H, int n);
 /* Bytes of workspace bevgen_op_image_sqerr (op 0; kernel_size ignored) / bevgen_op_ssim (op 1) need for these shapes: a pure function, no context.  -1: the call would be refused. */
 long bevgen_metrics_workspace_bytes(int op, int n, int C, int H, int W, int kernel_size);
+/* Bytes of the prepared-weight image of bevgen_lpips_prepare and of bevgen_lpips' workspace, for a context of BEVGEN_PRECISION_* `precision`: pure functions, no context,
+ * computed by the layout code that carves the two blocks.  -1: an unknown precision / a call that would be refused.  The workspace does not grow with n beyond one chunk. */
+long bevgen_lpips_prepared_bytes(int precision);
+long bevgen_lpips_workspace_bytes(int n, int H, int W, int precision);
 
 /* HIP-event timing of the hot kernels on their launch stream.  Between begin and end every launch of
  *   0 gemm (fp32 MFMA)   1 conv3x3 (implicit GEMM)   2 flash attention   3 decode attention   4 skinny GEMM
