@@ -42,14 +42,31 @@ struct SpinSerial {
 };
 }  // namespace
 
+// $BEVGEN_LN2_FOLD and $BEVGEN_MLP_FUSE once per process, $BEVGEN_PICK_TAIL at every call (ar_plan.h)
+ArSwitches ar_switches() {
+    const auto env = [](const char* name, int dflt) { const char* v = getenv(name); return v ? atoi(v) : dflt; };
+    static const ArSwitches once = [&] {
+        ArSwitches s;
+        s.ln2_fold = env("BEVGEN_LN2_FOLD", 1);
+        s.mlp_fuse = env("BEVGEN_MLP_FUSE", 1);
+        return s;
+    }();
+    ArSwitches s = once;
+    s.pick_tail = env("BEVGEN_PICK_TAIL", 1);
+    return s;
+}
+
 namespace {
 
-void gemm(const float* A, int lda, const float* W, int ldb, const float* bias, float* C, int ldc, int M, int N, int K, int act, const float* R, int ldr, hipStream_t s) {
+GemmArgs gemm_args(const float* A, int lda, const float* W, int ldb, const float* bias, float* C, int ldc, int M, int N, int K, int act, const float* R, int ldr) {
     GemmArgs g;
     g.A = A; g.B = W; g.C = C; g.R = R; g.bias_n = bias;
     g.M = M; g.N = N; g.K = K;
     g.lda = lda; g.ldb = ldb; g.ldc = ldc; g.ldr = ldr; g.act = act;
-    launch_gemm(g, s);
+    return g;
+}
+void gemm(const float* A, int lda, const float* W, int ldb, const float* bias, float* C, int ldc, int M, int N, int K, int act, const float* R, int ldr, hipStream_t s) {
+    launch_gemm(gemm_args(A, lda, W, ldb, bias, C, ldc, M, N, K, act, R, ldr), s);
 }
 
 size_t cache_elem_bytes(const Ctx& c) { return c.cfg.kv_cache_dtype == BEVGEN_KV_F16 ? 2 : 4; }
@@ -62,43 +79,19 @@ struct StepWs {
     int splits;
 };
 
-bool split_supported(const Ctx& c, int B) {
-    const int D = c.D;
-    return skinny_fused_supported(B, 3 * D, D, true) && (c.cfg.decode_weight_dtype != BEVGEN_W_F16 || skinny_fused_f16_ok(3 * D, D, true));
+// The plan of a decode step (ar_plan.h) for B sequences in groups of G, from the context as it is NOW: every entry point computes it once and hands it down -
+// mlpf_disabled may change between calls (Ctx::check_status), so a plan is never kept across calls.
+ArPlanIn plan_in(const Ctx& c, int B, int G) {
+    ArPlanIn in;
+    in.B = B; in.G = G;
+    in.D = c.D; in.H = c.H; in.K = c.K; in.L = c.L; in.V = c.V;
+    in.decode_path = c.cfg.decode_path; in.w_f16 = c.cfg.decode_weight_dtype == BEVGEN_W_F16; in.chains = c.cfg.decode_chains; in.trace = c.trace != nullptr;
+    in.mlpf_ready = c.mlpf_sync && !c.mlpf_disabled; in.mlpf_device_ok = c.mlpf_device_ok;
+    return in;
 }
-// BEVGEN_DECODE_AUTO: the split layer for up to four sequences (layout groups) per call, else the fused one.  Same box, config 4, fp32, full decodes, ms per step
-// split / fused: B = 1 0.99 / 1.28, B = 2 1.04 / 1.24, B = 3 1.14 / 1.22, B = 4 1.17 / 1.21, B = 6 1.27 / 1.21, B = 8 1.34 / 1.24, B = 16 1.47 / 1.42.  With 16-64
-// workgroups per layer the fused kernel's per-head GEMV cannot pull the 12.6 MB of q/k/v weights fast enough and a workgroup's 1.2 MB K/V range streams at one CU's
-// rate; the projection kernel spreads the weights over 192 workgroups and the attention-only kernel cuts each key walk into up to four ranges.
-// Round 5, with both MLP projections in one launch (ar_mlp_fused_kernel, fused path only), same box, full decodes, ms per step fused / split (profiles/r05_auto_threshold.txt):
-// fp16 cache + fp16 weights B = 1 0.710 / 0.829, 2 0.715 / 0.855, 4 0.727 / 0.940, 8 0.737 / 1.014 - the fused layer wins at EVERY batch size; fp32 storage
-// B = 1 1.116 / 0.919, 2 1.091 / 0.945, 3 1.094 / 1.044, 4 1.094 / 1.072, 6 1.095 / 1.186: the split layer up to four sequences, as before.
-int effective_decode_path(const Ctx& c, int B, int G) {
-    if (c.cfg.decode_path != BEVGEN_DECODE_AUTO) return c.cfg.decode_path;
-    if (c.cfg.decode_weight_dtype == BEVGEN_W_F16 && G <= 1 && c.mlpf_sync && !c.mlpf_disabled && mlp_fused_supported(B, c.D, true)) return BEVGEN_DECODE_FUSED;
-    return (B / std::max(G, 1) <= 4 && split_supported(c, B)) ? BEVGEN_DECODE_SPLIT : BEVGEN_DECODE_FUSED;
-}
-
-bool fused_path(const Ctx& c, int B, int G) {
-    const int path = effective_decode_path(c, B, G);
-    if (path != BEVGEN_DECODE_FUSED && path != BEVGEN_DECODE_SPLIT) return false;
-    const int D = c.D;
-    if (path == BEVGEN_DECODE_SPLIT && !split_supported(c, B)) return false;
-    if (G > 1 && c.K % 16 != 0) return false;   // the shared condition prefix must end on a 16-key chunk boundary (the per-operator path replicates it instead)
-    return ar_attn_fused_supported(B, G, D, c.H) && skinny_fused_supported(B, 4 * D, D, true) && skinny_fused_supported(B, D, 4 * D, false) &&
-           skinny_fused_supported(B, c.V, D, true) && ar_attn_fused_lds_bytes(G, D, (int)round_up(c.L, 4)) <= 64 * 1024 &&
-           (c.cfg.decode_weight_dtype != BEVGEN_W_F16 || (skinny_fused_f16_ok(4 * D, D, true) && skinny_fused_f16_ok(D, 4 * D, false) && skinny_fused_f16_ok(c.V, D, true)));
-}
+ArStepPlan step_plan(const Ctx& c, int B, int G) { return ar_step_plan(plan_in(c, B, G), ar_switches()); }
 
 size_t part_floats(const Ctx& c, int B) { return (size_t)std::max(skinny_fused_ksplit(c.D, 4 * c.D), MLP_FUSED_PLANES) * B * c.D; }
-
-// Both MLP projections of a layer in one launch (ar_mlp_fused_kernel): the fused three-launch layer, one chain, at most 64 rows (row chunks of 16), ln2 folded, a device whose CUs hold the
-// whole grid at once.  Otherwise the two skinny launches.
-bool mlp_fused_step(const Ctx& c, int Bc, bool split, int chains) {
-    static const int ln2_fold = getenv("BEVGEN_LN2_FOLD") ? atoi(getenv("BEVGEN_LN2_FOLD")) : 1;
-    return !split && chains == 1 && ln2_fold && c.mlpf_sync && !c.mlpf_disabled && skinny_fused_ksplit(c.D, 4 * c.D) > 1 &&
-           mlp_fused_supported(Bc, c.D, c.cfg.decode_weight_dtype == BEVGEN_W_F16);
-}
 
 // The decode-step buffers: a layout function (arena.h), fixed at the start of the per-call arena so that a captured graph keeps seeing the same addresses.  ar_prefill and
 // ar_forward start their layouts with it; ar_logits, ar_decode_step and ar_sample re-carve it alone after a reset() WITHOUT reserving: they rely on that reservation.
@@ -125,12 +118,72 @@ StepWs step_ws(const Ctx& c, Arena& a, int B) {
 
 void small_gemm(const float* A, int lda, const float* W, int ldb, const float* bias, float* C, int ldc, int M, int N, int K, int act, const float* R, int ldr,
                 float* ws, hipStream_t s) {
-    GemmArgs g;
-    g.A = A; g.B = W; g.C = C; g.R = R; g.bias_n = bias;
-    g.M = M; g.N = N; g.K = K;
-    g.lda = lda; g.ldb = ldb; g.ldc = ldc; g.ldr = ldr; g.act = act;
+    const GemmArgs g = gemm_args(A, lda, W, ldb, bias, C, ldc, M, N, K, act, R, ldr);
     if (M <= 64) launch_gemm_skinny_ws(g, ws, s);
     else launch_gemm(g, s);
+}
+
+// Flash attention over whole sequences: Q [B, H, Nq, 64], K / V [B, H, Lk, 64] (the first Nk_pad rows of a head are read), masked bias [H or 1][Nq][Nk_pad] and the
+// key-tile lists built from it.  The caller adds the residual and the output with its layout.
+AttnArgs attn_args(const float* Q, const float* K, const float* V, int Lk, const float* bias, const uint16_t* tiles, bool per_head, int B, int H, int Nq, int Nk_pad) {
+    AttnArgs a{};
+    a.Q = Q; a.K = K; a.V = V; a.bias = bias;
+    a.B = B; a.H = H; a.Nq = Nq; a.Nk_pad = Nk_pad;
+    a.q_bstride = (long)H * Nq * 64; a.q_hstride = (long)Nq * 64;
+    a.kv_bstride = (long)H * Lk * 64; a.kv_hstride = (long)Lk * 64;
+    a.ldbias = Nk_pad; a.bias_head_stride = per_head ? (long)Nq * Nk_pad : 0; a.scale = 0.125f;
+    a.tiles = tiles; a.tiles_head_stride = per_head ? (long)cdiv(Nq, 128) * (Nk_pad / 32 + 1) : 0; a.tiles_ld = Nk_pad / 32 + 1;
+    return a;
+}
+
+// masked bias of layer i over its first R rows and keys, and the key tiles of every query block that hold a present block
+void build_layer_bias(Ctx& c, int i, float* bias, uint16_t* tiles, int R, int Rpad, hipStream_t s) {
+    launch_build_masked_bias(c.attn_bias, c.vis_of_layer(i), bias, c.keep_heads, R, R, Rpad, c.L, 0.125f, s);
+    launch_build_attn_tiles(bias, (long)R * Rpad, Rpad, c.keep_heads, R, Rpad, tiles, s);
+}
+
+// One transformer layer over whole sequences from row 0 (Block.forward, mingpt_sparse.py:240-253), as ar_prefill and ar_forward run it; what differs between them:
+struct PrefixRows {
+    int nseq, R, Rpad;                      // sequences, rows of each, the rows padded to the attention's key tile
+    float *x, *xn, *x2, *h, *qkv, *m1, *Q;  // x [nseq R, D]: the residual stream, in and out; the others scratch of the same rows
+    float *k, *v; int Lk;                   // fp32 K / V that the attention reads, [nseq, H, Lk, 64]
+    void *kcache, *vcache;                  // these sequences' slots of the layer's cache - null when k / v ARE those slots (ar_prefill with an fp32 cache)
+    const float* bias; uint16_t* tiles;     // masked bias [keep_heads][R][Rpad] and its tile lists
+    float* layer_bias;                      // non-null: bias and tiles of THIS layer are built here, behind the scatters (ar_prefill with per-layer layouts)
+};
+void prefix_layer(Ctx& c, int i, const PrefixRows& p, hipStream_t s) {
+    const ArLayer& l = c.ar[i];
+    const int D = c.D, H = c.H, rows = p.nseq * p.R;
+    launch_layernorm(p.x, D, l.ln1_w, l.ln1_b, p.xn, D, rows, D, 1e-5f, s);
+    gemm(p.xn, D, l.wqkv, D, l.bqkv, p.qkv, 3 * D, rows, 3 * D, D, ACT_NONE, nullptr, 0, s);
+    launch_ar_qkv_scatter(p.qkv, p.Q, p.k, p.v, 0, p.nseq, H, p.R, 0, p.Lk, s);                                                    // what this pass's attention reads
+    if (p.kcache) launch_ar_qkv_scatter(p.qkv, nullptr, p.kcache, p.vcache, cache_dtype(c), p.nseq, H, p.R, 0, c.L, s);   // the persistent rows [0, R) the decode steps read
+    if (p.layer_bias) build_layer_bias(c, i, p.layer_bias, p.tiles, p.R, p.Rpad, s);
+    AttnArgs a = attn_args(p.Q, p.k, p.v, p.Lk, p.layer_bias ? p.layer_bias : p.bias, p.tiles, c.keep_heads > 1, p.nseq, H, p.R, p.Rpad);
+    a.R = p.xn; a.O = p.x2; a.o_bstride = (long)p.R * D; a.o_qstride = D; a.o_hstride = 64;
+    launch_attention(a, s);  // x2 = ln1(x) + attn
+    launch_layernorm(p.x2, D, l.ln2_w, l.ln2_b, p.h, D, rows, D, 1e-5f, s);
+    gemm(p.h, D, l.mlp0_w, D, l.mlp0_b, p.m1, 4 * D, rows, 4 * D, D, ACT_GELU, nullptr, 0, s);
+    gemm(p.m1, 4 * D, l.mlp2_w, 4 * D, l.mlp2_b, p.x, D, rows, D, 4 * D, ACT_NONE, p.x2, D, s);
+}
+
+// Camera embeddings of all B sequences (state of the decode steps), then the condition rows of the first sequence of every group of S into x [B / S, K, D]; S > 1:
+// cg / eg take contiguous [B / S, ...] copies of those sequences' ids and camera embeddings
+void embed_condition(Ctx& c, const int64_t* cond, const float* I_inv, const float* E_inv, int B, int S, int64_t* cg, float* eg, float* x, hipStream_t s) {
+    const auto& g = c.cfg;
+    auto& st = c.ars;
+    const int D = c.D, K = c.K, G = B / S;
+    if (g.image_embed)
+        launch_camera_embed(I_inv, E_inv, c.image_plane, c.pf("img_embed.weight"), c.pf("cam_embed.weight"), st.img_embed, st.c_embed, B, g.num_cams, c.T, D, s);
+    const float* c_embed = st.c_embed;
+    if (S > 1) {
+        HIP_CHECK(hipMemcpy2DAsync(cg, (size_t)K * 8, cond, (size_t)S * K * 8, (size_t)K * 8, G, hipMemcpyDeviceToDevice, s));
+        HIP_CHECK(hipMemcpy2DAsync(eg, (size_t)g.num_cams * D * 4, st.c_embed, (size_t)S * g.num_cams * D * 4, (size_t)g.num_cams * D * 4, G, hipMemcpyDeviceToDevice, s));
+        cond = cg; c_embed = eg;
+    }
+    const bool bev = g.bev_embed;
+    launch_cond_embed(cond, c.pf("cond_tok_emb.weight"), c.pf("cond_pos_emb"), bev ? c.pf("bev_grid") : nullptr, bev ? c.pf("bev_embed.weight") : nullptr,
+                      bev ? c.pf("bev_embed.bias") : nullptr, bev ? c.pf("bev_cam_pos_emb") : nullptr, c_embed, x, G, g.num_cams, K, D, g.cond_vocab_size, s);
 }
 
 }  // namespace
@@ -171,14 +224,8 @@ void sparse_self_attention_op(Ctx& c, const float* q, const float* k, const floa
         HIP_CHECK(hipMemcpy2DAsync(vpad, (size_t)Lpad * 256, v, (size_t)L * 256, (size_t)L * 256, (size_t)B * H, hipMemcpyDeviceToDevice, s));
         kp = kpad; vp = vpad;
     }
-    AttnArgs a{};
-    a.Q = q; a.K = kp; a.V = vp; a.bias = bias; a.R = nullptr; a.O = out;
-    a.B = B; a.H = H; a.Nq = L; a.Nk_pad = Lpad;
-    a.q_bstride = (long)H * L * 64; a.q_hstride = (long)L * 64;
-    a.kv_bstride = (long)H * Lpad * 64; a.kv_hstride = (long)Lpad * 64;
-    a.ldbias = Lpad; a.bias_head_stride = (long)L * Lpad; a.scale = 0.125f;
-    a.o_bstride = (long)H * L * 64; a.o_qstride = 64; a.o_hstride = (long)L * 64;  // [B,H,L,64] like the reference op
-    a.tiles = tiles; a.tiles_head_stride = (long)cdiv(L, 128) * (Lpad / 32 + 1); a.tiles_ld = Lpad / 32 + 1;
+    AttnArgs a = attn_args(q, kp, vp, Lpad, bias, tiles, true, B, H, L, Lpad);
+    a.O = out; a.o_bstride = (long)H * L * 64; a.o_qstride = 64; a.o_hstride = (long)L * 64;  // [B,H,L,64] like the reference op
     launch_attention(a, s);
 }
 
@@ -216,7 +263,9 @@ void ar_prefill(Ctx& c, const int64_t* cond, const float* I_inv, const float* E_
     const int D = c.D, H = c.H, K = c.K, L = c.L;
     auto& st = c.ars;
     // decode_path = auto: the split layer's QKV operand image is packed by the first batch that will run it (S sequences per workgroup only on the fused paths)
-    if (effective_decode_path(c, B, fused_path(c, B, S) ? S : 1) == BEVGEN_DECODE_SPLIT) ctx_pack_split_qkv(c, s);
+    const ArSwitches sw = ar_switches();
+    const int group = ar_prefill_group(plan_in(c, B, 1), sw, S);
+    if (ar_step_plan(plan_in(c, B, group), sw).needs_split_qkv_image) ctx_pack_split_qkv(c, s);
     ar_state_setup(c, B, s);
 
     // workspace: the decode-step buffers first (stable addresses), then the prefill activations
@@ -245,58 +294,27 @@ void ar_prefill(Ctx& c, const int64_t* cond, const float* I_inv, const float* E_
     });
     if (c.prefill_bias) launch_build_attn_tiles(c.prefill_bias, (long)K * c.Kpad, c.Kpad, c.keep_heads, K, c.Kpad, ltiles, s);
 
-    if (g.image_embed)   // per-sequence state of the decode steps: for all B sequences
-        launch_camera_embed(I_inv, E_inv, c.image_plane, c.pf("img_embed.weight"), c.pf("cam_embed.weight"), st.img_embed, st.c_embed, B, g.num_cams, c.T, D, s);
-    const int64_t* cond_g = cond;
-    const float* c_embed_g = st.c_embed;
-    if (S > 1) {
-        HIP_CHECK(hipMemcpy2DAsync(cg, (size_t)K * 8, cond, (size_t)S * K * 8, (size_t)K * 8, G, hipMemcpyDeviceToDevice, s));
-        HIP_CHECK(hipMemcpy2DAsync(eg, (size_t)g.num_cams * D * 4, st.c_embed, (size_t)S * g.num_cams * D * 4, (size_t)g.num_cams * D * 4, G, hipMemcpyDeviceToDevice, s));
-        cond_g = cg; c_embed_g = eg;
-    }
-    launch_cond_embed(cond_g, c.pf("cond_tok_emb.weight"), c.pf("cond_pos_emb"), g.bev_embed ? c.pf("bev_grid") : nullptr, g.bev_embed ? c.pf("bev_embed.weight") : nullptr,
-                      g.bev_embed ? c.pf("bev_embed.bias") : nullptr, g.bev_embed ? c.pf("bev_cam_pos_emb") : nullptr, c_embed_g, x, G, g.num_cams, K, D,
-                      g.cond_vocab_size, s);
+    embed_condition(c, cond, I_inv, E_inv, B, S, cg, eg, x, s);
     if (kvd) {
         HIP_CHECK(hipMemsetAsync(tk, 0, (size_t)G * H * c.Kpad * 64 * sizeof(float), s));   // pad rows K..Kpad stay zero
         HIP_CHECK(hipMemsetAsync(tv, 0, (size_t)G * H * c.Kpad * 64 * sizeof(float), s));
     }
     const size_t layer_bytes_p = (size_t)B * H * L * 64 * cache_elem_bytes(c);
-    for (int i = 0; i < g.num_layers; ++i) {
-        const ArLayer& l = c.ar[i];
+    BG_REQUIRE(c.Kpad <= L, "condition length padded to %d exceeds the cache length %d", c.Kpad, L);
+    PrefixRows p{G, K, c.Kpad, x, xn, x2, h, qkv, m1, Q, tk, tv, c.Kpad, nullptr, nullptr, c.prefill_bias, ltiles, lbias};
+    for (int i = 0; i < g.num_layers; ++i) {   // all G K rows at once, into cache slots [0, G) for now
         char* kcb = reinterpret_cast<char*>(st.kcache) + i * layer_bytes_p;
         char* vcb = reinterpret_cast<char*>(st.vcache) + i * layer_bytes_p;
-        float* kc = kvd ? tk : reinterpret_cast<float*>(kcb);   // what the prefill attention reads
-        float* vc = kvd ? tv : reinterpret_cast<float*>(vcb);
-        const int Lk = kvd ? c.Kpad : L;                        // row capacity per (sequence, head) of that buffer
-        launch_layernorm(x, D, l.ln1_w, l.ln1_b, xn, D, (int)rows, D, 1e-5f, s);
-        gemm(xn, D, l.wqkv, D, l.bqkv, qkv, 3 * D, (int)rows, 3 * D, D, ACT_NONE, nullptr, 0, s);
-        launch_ar_qkv_scatter(qkv, Q, kc, vc, 0, G, H, K, 0, Lk, s);   // cache slots [0, G) for now
-        if (kvd) launch_ar_qkv_scatter(qkv, nullptr, kcb, vcb, kvd, G, H, K, 0, L, s);   // the fp16 image the decode steps read
-        AttnArgs a{};
-        if (lbias) {
-            launch_build_masked_bias(c.attn_bias, c.vis_of_layer(i), lbias, c.keep_heads, K, K, c.Kpad, c.L, 0.125f, s);
-            launch_build_attn_tiles(lbias, (long)K * c.Kpad, c.Kpad, c.keep_heads, K, c.Kpad, ltiles, s);
-        }
-        a.Q = Q; a.K = kc; a.V = vc; a.bias = lbias ? lbias : c.prefill_bias; a.R = xn; a.O = x2;
-        a.B = G; a.H = H; a.Nq = K; a.Nk_pad = c.Kpad;
-        a.q_bstride = (long)H * K * 64; a.q_hstride = (long)K * 64;
-        a.kv_bstride = (long)H * Lk * 64; a.kv_hstride = (long)Lk * 64;
-        a.ldbias = c.Kpad; a.bias_head_stride = c.keep_heads > 1 ? (long)K * c.Kpad : 0; a.scale = 0.125f;
-        a.tiles = ltiles; a.tiles_head_stride = c.keep_heads > 1 ? (long)cdiv(K, 128) * (c.Kpad / 32 + 1) : 0; a.tiles_ld = c.Kpad / 32 + 1;
-        a.o_bstride = (long)K * D; a.o_qstride = D; a.o_hstride = 64;
-        BG_REQUIRE(c.Kpad <= L, "condition length padded to %d exceeds the cache length %d", c.Kpad, L);
-        launch_attention(a, s);  // x2 = ln1(x) + attn
-        launch_layernorm(x2, D, l.ln2_w, l.ln2_b, h, D, (int)rows, D, 1e-5f, s);
-        gemm(h, D, l.mlp0_w, D, l.mlp0_b, m1, 4 * D, (int)rows, 4 * D, D, ACT_GELU, nullptr, 0, s);
-        gemm(m1, 4 * D, l.mlp2_w, 4 * D, l.mlp2_b, x, D, (int)rows, D, 4 * D, ACT_NONE, x2, D, s);
+        if (kvd) { p.kcache = kcb; p.vcache = vcb; }                                                               // the fp16 image the decode steps read
+        else { p.k = reinterpret_cast<float*>(kcb); p.v = reinterpret_cast<float*>(vcb); p.Lk = L; }   // the attention reads the cache itself
+        prefix_layer(c, i, p, s);
     }
     st.G = 1;
     if (S == 1) {
         launch_gather_rows(x, st.hidden, B, K - 1, K, D, s);
         return;
     }
-    if (fused_path(c, B, S)) {
+    if (group == S) {
         // the fused decode kernel reads the K prefix rows of a group from the group's FIRST cache slot: move slot g -> slot g*S, highest group first
         // (a destination never holds a source that is still needed); the other slots of the group keep only their private rows >= K
         st.G = S;
@@ -313,9 +331,9 @@ void ar_prefill(Ctx& c, const int64_t* cond, const float* I_inv, const float* E_
 }
 
 // ln_f + head on the newest rows (mingpt_sparse.py:386-387)
-static void head_logits(Ctx& c, StepWs& w, int B, float* logits, hipStream_t s) {
+static void head_logits(Ctx& c, StepWs& w, const ArStepPlan& plan, int B, float* logits, hipStream_t s) {
     auto& st = c.ars;
-    if (fused_path(c, B, st.G)) {
+    if (plan.fused) {
         SkinnyFusedArgs g;
         g.A = st.hidden; g.lda = c.D;
         g.ln_w = c.pf("ln_f.weight"); g.ln_b = c.pf("ln_f.bias"); g.eps = 1e-5f;
@@ -334,31 +352,16 @@ void ar_logits(Ctx& c, float* logits, hipStream_t s) {
     BG_REQUIRE(st.B > 0, "bevgen_ar_prefill must be called first");
     c.arena.reset();
     StepWs w = step_ws(c, c.arena, st.B);
-    head_logits(c, w, st.B, logits, s);
-}
-
-// Number of independent sequence groups ("chains") the fused step is cut into.  A decode step is a chain of ~75 short, strictly dependent kernels; each one pays its ramp,
-// one cold weight burst and its tail alone (the weight-streaming projections reach ~2 TB/s while they run, the chip idles in between).  Sequences are independent, so
-// the batch is cut into chains enqueued on separate streams: the hardware then always has another chain's kernel to run - a projection's 16.8 MB weight burst under the
-// other chain's K/V stream.  The price: every chain streams the layer's projection weights (50 MB / layer with fp32 storage) itself; the second read of a matrix
-// follows the first within a layer and is served by the memory-side cache.  (A persistent single-launch layer was measured instead and rejected: a grid-wide
-// exchange between phases costs 7.9 us on this 8-XCD part, profiles/r03_xchg_probe.txt - more than a kernel boundary.)
-static int decode_chains(const Ctx& c, int B, int G) {
-    int n = c.cfg.decode_chains;
-    if (n <= 0) n = 1;   // measured (profiles/r03_chain_probe.txt, B = 16): 1 chain 1.41 ms/step, 2 chains 1.60, 4 chains 1.96 - the option stays for experiments
-    n = std::min(n, 4);
-    while (n > 1 && ((B / G) % n != 0 || (B / G) / n < 1)) --n;
-    if (c.trace) n = 1;   // the phase-timestamp buffers are indexed by workgroup of ONE launch per kind
-    return n;
+    head_logits(c, w, step_plan(c, st.B, st.G), st.B, logits, s);
 }
 
 // One chain = the sequences [r0, r0 + Bc) through all layers.  Fused form of the step (decode_fused.hip): per layer {ln1 + qkv + attention, ln2 + MLP up + GELU,
 // MLP down split over K}; the down-projection's partial sums, bias and residual are folded into the next consumer's row fetch (RowSrc), the last layer's into
 // the hidden-state write.
-static void decode_chain_launch(Ctx& c, StepWs& w, const int64_t* tok, int r0, int Bc, int* counter, hipStream_t s) {
+static void decode_chain_launch(Ctx& c, StepWs& w, const ArStepPlan& plan, const int64_t* tok, int r0, int* counter, hipStream_t s) {
     const auto& g = c.cfg;
     auto& st = c.ars;
-    const int D = c.D, H = c.H, B = st.B, L = c.L;
+    const int D = c.D, H = c.H, B = st.B, Bc = plan.Bc, L = c.L;
     const size_t eb = cache_elem_bytes(c);
     float* x = w.x + (size_t)r0 * D;
     if (!(st.pick_embeds && tok == w.tok && r0 == 0 && Bc == B))   // (ar_sample's pick launch already wrote the new rows' embeddings)
@@ -366,12 +369,10 @@ static void decode_chain_launch(Ctx& c, StepWs& w, const int64_t* tok, int r0, i
                          st.d_step, x, Bc, g.num_cams, c.T, D, g.vocab_size + 1, s);
     const size_t layer_bytes = (size_t)B * H * L * 64 * eb;
     const size_t chain_off = (size_t)r0 * H * L * 64 * eb;    // this chain's first cache slot inside a layer
-    const int ks = skinny_fused_ksplit(D, 4 * D);
+    const int ks = plan.down_ksplit;
     const int wf16 = g.decode_weight_dtype == BEVGEN_W_F16;
     float* part = w.part + (size_t)ks * r0 * D;               // [ks][Bc][D] per chain, chains back to back
     float* m1 = w.m1 + (size_t)r0 * 4 * D;
-    const bool split = effective_decode_path(c, B, st.G) == BEVGEN_DECODE_SPLIT;
-    const bool mlpf = mlp_fused_step(c, Bc, split, Bc == B ? 1 : 2);
     float* qkv = w.qkv + (size_t)r0 * 3 * D;
     float* xn = w.xn + (size_t)r0 * D;
     RowSrc src;
@@ -380,7 +381,7 @@ static void decode_chain_launch(Ctx& c, StepWs& w, const int64_t* tok, int r0, i
         const ArLayer& l = c.ar[i];
         float* x2 = ((i & 1) ? w.x2b : w.x2) + (size_t)r0 * D;
         ArAttnFusedArgs a;
-        if (split) {   // LayerNorm + QKV projection of the chain's rows in one MFMA kernel (the weight is read once), ln1(x) kept for the residual
+        if (plan.split) {   // LayerNorm + QKV projection of the chain's rows in one MFMA kernel (the weight is read once), ln1(x) kept for the residual
             SkinnyFusedArgs pq;
             pq.a_src = &src;
             pq.ln_w = l.ln1_w; pq.ln_b = l.ln1_b; pq.eps = 1e-5f;
@@ -390,12 +391,7 @@ static void decode_chain_launch(Ctx& c, StepWs& w, const int64_t* tok, int r0, i
             pq.M = Bc; pq.N = 3 * D; pq.K = D; pq.ksplit = 1;
             launch_skinny_fused(pq, s);
             a.qkv = qkv; a.xn = xn;
-            // one or two sequences: 16-32 workgroups cannot pull a 1.2 MB K/V range each at the chip's rate - split the key walk over more of them (the partial
-            // states live in the per-operator path's workspace, sized for at least this many splits)
-            if (st.G == 1 && Bc * H < 128) {
-                const int ks = std::min(std::min(4, 128 / (Bc * H)), w.splits);
-                if (ks > 1) { a.ksplit = ks; a.kws = w.dec_ws + (size_t)r0 * H * w.splits * 66; }   // (per chain: its sequences' slots)
-            }
+            if (plan.attn_ksplit > 1) { a.ksplit = plan.attn_ksplit; a.kws = w.dec_ws + (size_t)r0 * H * w.splits * 66; }   // (per chain: its sequences' slots of the per-operator path's workspace)
         } else {
             a.x = src;
             a.ln_w = l.ln1_w; a.ln_b = l.ln1_b; a.eps = 1e-5f;
@@ -413,7 +409,7 @@ static void decode_chain_launch(Ctx& c, StepWs& w, const int64_t* tok, int r0, i
         a.prefix = c.K; a.scale = 0.125f;
         a.trace = c.trace;
         launch_ar_attn_fused(a, s);
-        if (mlpf) {   // ln2 + MLP up + GELU + MLP down in one launch: 8 partial planes (one per XCD) for the next consumer's row fetch
+        if (plan.mlp_fused) {   // ln2 + MLP up + GELU + MLP down in one launch: 8 partial planes (one per XCD) for the next consumer's row fetch
             MlpFusedArgs mf;
             mf.A = x2; mf.lda = D;
             mf.ln_w = l.ln2_w; mf.ln_cs = l.mlp0_cs; mf.ln_ds = l.mlp0_ds; mf.eps = 1e-5f;
@@ -433,8 +429,7 @@ static void decode_chain_launch(Ctx& c, StepWs& w, const int64_t* tok, int r0, i
         up.Wp = l.mlp0_wp; up.w_f16 = wf16; up.bias = l.mlp0_b;
         // ln2 folded into the product (skinny_fused_kernel<.., FD>).  Same-box A/B, ms per decode step, folded vs direct: fp16 cache + fp16 weights 0.989-0.994 vs
         // 0.992-0.998, fp16 cache + fp32 weights 1.137-1.151 vs 1.154-1.163, fp32 both 1.447-1.454 vs 1.466-1.482 (profiles/r04_ab_ln2_fold.txt).  $BEVGEN_LN2_FOLD=0: direct form
-        static const int ln2_fold = getenv("BEVGEN_LN2_FOLD") ? atoi(getenv("BEVGEN_LN2_FOLD")) : 1;
-        if (ln2_fold) { up.ln_cs = l.mlp0_cs; up.ln_ds = l.mlp0_ds; }
+        if (plan.ln2_fold) { up.ln_cs = l.mlp0_cs; up.ln_ds = l.mlp0_ds; }
         up.C = m1; up.ldc = 4 * D;
         up.M = Bc; up.N = 4 * D; up.K = D; up.ksplit = 1; up.act = ACT_GELU;
         up.trace = c.trace ? c.trace + 4096 * 8 : nullptr;
@@ -459,12 +454,11 @@ static void decode_chain_launch(Ctx& c, StepWs& w, const int64_t* tok, int r0, i
     launch_rowsrc_materialize(src, st.hidden + (size_t)r0 * D, Bc, D, counter, s);   // hidden state of the chain's new rows (+ the step counter when this is the only chain)
 }
 
-static void decode_step_launch_fused(Ctx& c, StepWs& w, const int64_t* tok, hipStream_t s) {
+static void decode_step_launch_fused(Ctx& c, StepWs& w, const ArStepPlan& plan, const int64_t* tok, hipStream_t s) {
     auto& st = c.ars;
-    const int B = st.B;
-    const int nch = decode_chains(c, B, st.G);
+    const int nch = plan.chains, Bc = plan.Bc;
     if (nch == 1) {
-        decode_chain_launch(c, w, tok, 0, B, st.d_step, s);
+        decode_chain_launch(c, w, plan, tok, 0, st.d_step, s);
         return;
     }
     // fork: chains 1.. on side streams behind everything already enqueued on s; join before the step counter moves (every kernel of the step reads it)
@@ -478,24 +472,23 @@ static void decode_step_launch_fused(Ctx& c, StepWs& w, const int64_t* tok, hipS
     }
     if (!c.chain_fork) HIP_CHECK(hipEventCreateWithFlags(&c.chain_fork, hipEventDisableTiming));
     HIP_CHECK(hipEventRecord(c.chain_fork, s));
-    const int Bc = B / nch;
     for (int k = 1; k < nch; ++k) {
         hipStream_t q = c.chain_streams[k - 1];
         HIP_CHECK(hipStreamWaitEvent(q, c.chain_fork, 0));
-        decode_chain_launch(c, w, tok, k * Bc, Bc, nullptr, q);
+        decode_chain_launch(c, w, plan, tok, k * Bc, nullptr, q);
         HIP_CHECK(hipEventRecord(c.chain_join[k - 1], q));
     }
-    decode_chain_launch(c, w, tok, 0, Bc, nullptr, s);
+    decode_chain_launch(c, w, plan, tok, 0, nullptr, s);
     for (int k = 1; k < nch; ++k) HIP_CHECK(hipStreamWaitEvent(s, c.chain_join[k - 1], 0));
     launch_increment(st.d_step, s);
 }
 
 // one new row through all layers; position / bias row / cache slot are derived from the device-side step counter
-static void decode_step_launch(Ctx& c, StepWs& w, const int64_t* tok, hipStream_t s) {
+static void decode_step_launch(Ctx& c, StepWs& w, const ArStepPlan& plan, const int64_t* tok, hipStream_t s) {
     const auto& g = c.cfg;
     auto& st = c.ars;
-    if (fused_path(c, st.B, st.G)) {
-        decode_step_launch_fused(c, w, tok, s);
+    if (plan.fused) {
+        decode_step_launch_fused(c, w, plan, tok, s);
         return;
     }
     const int D = c.D, H = c.H, B = st.B, L = c.L;
@@ -535,7 +528,7 @@ void ar_decode_step(Ctx& c, const int64_t* tok, hipStream_t s) {
     StepWs w = step_ws(c, c.arena, st.B);
     st.pick_embeds = false;   // the caller's tokens: embed them here
     SpinSerial serial(c, s);
-    decode_step_launch(c, w, tok, s);
+    decode_step_launch(c, w, step_plan(c, st.B, st.G), tok, s);
     st.step += 1;
 }
 
@@ -548,6 +541,7 @@ void ar_sample(Ctx& c, const int64_t* cond, const float* I_inv, const float* E_i
     c.step_events_used = 0;   // bevgen_ar_step_times describes THIS call: a call that takes the eager path below reports no steps
     c.arena.reset();
     StepWs w = step_ws(c, c.arena, B);
+    const ArStepPlan plan = step_plan(c, B, st.G);
     launch_fill_i64(out, (long)B * c.N, c.cfg.vocab_size, s);  // x = vocab_size everywhere (ar_lm:157)
 
     // one decode iteration: logits of the newest row -> token -> (optionally) push the token through the stack.
@@ -556,23 +550,23 @@ void ar_sample(Ctx& c, const int64_t* cond, const float* I_inv, const float* E_i
     // (the token's store into `out` and - fused path, one chain - the new row's embedding ride in the pick launch: two launches per step less)
     ArPickTail tail;
     tail.out_all = out; tail.fwd_idx = c.fwd_idx; tail.N = c.N;
-    st.pick_embeds = fused_path(c, B, st.G) && decode_chains(c, B, st.G) == 1 && !(getenv("BEVGEN_PICK_TAIL") && atoi(getenv("BEVGEN_PICK_TAIL")) == 0);
+    st.pick_embeds = plan.pick_embeds;
     if (st.pick_embeds) {
         tail.tok_emb = c.pf("x_tok_emb.weight"); tail.img_embed = st.img_embed; tail.pos_emb = c.pf("x_pos_emb"); tail.x = w.x;
         tail.C = c.cfg.num_cams; tail.T = c.T; tail.D = c.D; tail.vocab_rows = c.cfg.vocab_size + 1;
     }
     auto head_and_pick = [&](float* lg, hipStream_t q) {
-        head_logits(c, w, B, lg, q);
+        head_logits(c, w, plan, B, lg, q);
         launch_ar_pick(lg, c.V, greedy ? nullptr : noise_u, st.d_step, forced, w.tok, B, c.V, top_k, temperature, q, &tail);
     };
 
-    const bool use_graph = steps > 2 && !step_logits && !prof_enabled() && !c.disable_graphs;
+    const bool use_graph = ar_use_graph(steps, step_logits != nullptr, prof_enabled(), c.disable_graphs);
     SpinSerial serial(c, s);
     if (!use_graph) {
         for (int step = 0; step < steps; ++step) {
             head_and_pick(step_logits ? step_logits + (size_t)step * B * c.V : w.logits, s);
             if (step + 1 < steps) {
-                decode_step_launch(c, w, w.tok, s);
+                decode_step_launch(c, w, plan, w.tok, s);
                 st.step += 1;
             }
         }
@@ -591,7 +585,7 @@ void ar_sample(Ctx& c, const int64_t* cond, const float* I_inv, const float* E_i
     HIP_CHECK(hipStreamWaitEvent(q, c.graph_ev_in, 0));
     serial.q = s;   // (the call's last launches rejoin the caller's stream below: the chain event is recorded there)
     Ctx::GraphKey key;
-    key.B = B; key.G = st.G; key.chains = fused_path(c, B, st.G) ? decode_chains(c, B, st.G) : 1; key.top_k = top_k; key.greedy = greedy; key.kv = cache_dtype(c); key.temperature = temperature;
+    key.B = B; key.G = st.G; key.fused = plan.fused; key.split = plan.split; key.chains = plan.chains; key.mlp_fused = plan.mlp_fused; key.top_k = top_k; key.greedy = greedy; key.kv = cache_dtype(c); key.temperature = temperature;
     key.noise = greedy ? nullptr : noise_u; key.forced = forced; key.out = out; key.arena = c.arena.base; key.persist = c.persist.base; key.trace = c.trace;
     if (!c.graph_exec || !(c.graph_key == key)) {
         if (c.graph_exec) c.retire_graph(c.graph_exec, c.graph);
@@ -600,7 +594,7 @@ void ar_sample(Ctx& c, const int64_t* cond, const float* I_inv, const float* E_i
         HIP_CHECK(hipStreamBeginCapture(q, hipStreamCaptureModeThreadLocal));
         try {
             head_and_pick(w.logits, q);
-            decode_step_launch(c, w, w.tok, q);
+            decode_step_launch(c, w, plan, w.tok, q);
         } catch (...) {
             (void)hipStreamEndCapture(q, &graph);
             if (graph) (void)hipGraphDestroy(graph);
@@ -652,7 +646,7 @@ void ar_forward(Ctx& c, const int64_t* cond, const float* I_inv, const float* E_
     const int R = K + n, Rpad = (int)round_up(R, 32);
     BG_REQUIRE(R <= L, "ar_forward: %d condition + %d image rows exceed the sequence length %d", K, n, L);
     auto& st = c.ars;
-    if (effective_decode_path(c, B, 1) == BEVGEN_DECODE_SPLIT) ctx_pack_split_qkv(c, s);   // decode steps may follow
+    if (step_plan(c, B, 1).needs_split_qkv_image) ctx_pack_split_qkv(c, s);   // decode steps may follow
     ar_state_setup(c, B, s);
     st.G = 1;
     st.pick_embeds = false;
@@ -686,46 +680,23 @@ void ar_forward(Ctx& c, const int64_t* cond, const float* I_inv, const float* E_
     HIP_CHECK(hipMemsetAsync(tv, 0, kv_g * sizeof(float), s));
 
     // ---- embeddings: condition rows [0, K), image rows [K, R) in decode order
-    if (g.image_embed)
-        launch_camera_embed(I_inv, E_inv, c.image_plane, c.pf("img_embed.weight"), c.pf("cam_embed.weight"), st.img_embed, st.c_embed, B, g.num_cams, c.T, D, s);
-    launch_cond_embed(cond, c.pf("cond_tok_emb.weight"), c.pf("cond_pos_emb"), g.bev_embed ? c.pf("bev_grid") : nullptr, g.bev_embed ? c.pf("bev_embed.weight") : nullptr,
-                      g.bev_embed ? c.pf("bev_embed.bias") : nullptr, g.bev_embed ? c.pf("bev_cam_pos_emb") : nullptr, st.c_embed, cx, B, g.num_cams, K, D, g.cond_vocab_size, s);
+    embed_condition(c, cond, I_inv, E_inv, B, 1, nullptr, nullptr, cx, s);
     HIP_CHECK(hipMemcpy2DAsync(x, (size_t)R * D * 4, cx, (size_t)K * D * 4, (size_t)K * D * 4, B, hipMemcpyDeviceToDevice, s));
     launch_ar_seq_embed(ids, c.pf("x_tok_emb.weight"), st.img_embed, c.pf("x_pos_emb"), c.fwd_idx, x, B, n, R, K, c.N, D, g.vocab_size + 1, s);
 
     // ---- layers
-    const int kvd = cache_dtype(c);
     const size_t eb = cache_elem_bytes(c);
     const size_t layer_bytes = (size_t)B * H * L * 64 * eb;
     const size_t seq_bytes = (size_t)H * L * 64 * eb;
+    PrefixRows p{0, R, Rpad, nullptr, xn, x2, h, qkv, m1, Q, tk, tv, Rpad, nullptr, nullptr, bias, tiles, nullptr};
     for (int i = 0; i < g.num_layers; ++i) {
-        const ArLayer& l = c.ar[i];
-        if (i == 0 || c.keep_layers > 1) {   // shared layout (density 1): one bias image and one set of tile lists per call
-            launch_build_masked_bias(c.attn_bias, c.vis_of_layer(i), bias, Hk, R, R, Rpad, L, 0.125f, s);
-            launch_build_attn_tiles(bias, (long)R * Rpad, Rpad, Hk, R, Rpad, tiles, s);
-        }
+        if (i == 0 || c.keep_layers > 1) build_layer_bias(c, i, bias, tiles, R, Rpad, s);   // shared layout (density 1): one bias image and one set of tile lists per call
         for (int b0 = 0; b0 < B; b0 += Bg) {
-            const int nb = std::min(Bg, B - b0);
-            const int rows = nb * R;
-            float* xg = x + (size_t)b0 * R * D;
-            char* kcb = reinterpret_cast<char*>(st.kcache) + i * layer_bytes + b0 * seq_bytes;
-            char* vcb = reinterpret_cast<char*>(st.vcache) + i * layer_bytes + b0 * seq_bytes;
-            launch_layernorm(xg, D, l.ln1_w, l.ln1_b, xn, D, rows, D, 1e-5f, s);
-            gemm(xn, D, l.wqkv, D, l.bqkv, qkv, 3 * D, rows, 3 * D, D, ACT_NONE, nullptr, 0, s);
-            launch_ar_qkv_scatter(qkv, Q, tk, tv, 0, nb, H, R, 0, Rpad, s);          // what this pass's attention reads
-            launch_ar_qkv_scatter(qkv, nullptr, kcb, vcb, kvd, nb, H, R, 0, L, s);   // the persistent cache rows [0, R) the decode steps read (fp32 or fp16)
-            AttnArgs a{};
-            a.Q = Q; a.K = tk; a.V = tv; a.bias = bias; a.R = xn; a.O = x2;
-            a.B = nb; a.H = H; a.Nq = R; a.Nk_pad = Rpad;
-            a.q_bstride = (long)H * R * 64; a.q_hstride = (long)R * 64;
-            a.kv_bstride = (long)H * Rpad * 64; a.kv_hstride = (long)Rpad * 64;
-            a.ldbias = Rpad; a.bias_head_stride = Hk > 1 ? (long)R * Rpad : 0; a.scale = 0.125f;
-            a.tiles = tiles; a.tiles_head_stride = Hk > 1 ? (long)cdiv(R, 128) * (Rpad / 32 + 1) : 0; a.tiles_ld = Rpad / 32 + 1;
-            a.o_bstride = (long)R * D; a.o_qstride = D; a.o_hstride = 64;
-            launch_attention(a, s);   // x2 = ln1(x) + attn
-            launch_layernorm(x2, D, l.ln2_w, l.ln2_b, h, D, rows, D, 1e-5f, s);
-            gemm(h, D, l.mlp0_w, D, l.mlp0_b, m1, 4 * D, rows, 4 * D, D, ACT_GELU, nullptr, 0, s);
-            gemm(m1, 4 * D, l.mlp2_w, 4 * D, l.mlp2_b, xg, D, rows, D, 4 * D, ACT_NONE, x2, D, s);
+            p.nseq = std::min(Bg, B - b0);
+            p.x = x + (size_t)b0 * R * D;
+            p.kcache = reinterpret_cast<char*>(st.kcache) + i * layer_bytes + b0 * seq_bytes;   // (fp32 or fp16)
+            p.vcache = reinterpret_cast<char*>(st.vcache) + i * layer_bytes + b0 * seq_bytes;
+            prefix_layer(c, i, p, s);
         }
     }
 
@@ -747,9 +718,6 @@ void ar_forward(Ctx& c, const int64_t* cond, const float* I_inv, const float* E_
     if (loss) launch_mean_fixed_order(wnll, (long)B * n, loss, s);
 }
 
-}  // namespace bevgen
-
-namespace bevgen {
 // durations of the graph replays of the most recent bevgen_ar_sample (one decode step each), in milliseconds; synchronises the library stream
 int ar_step_times(Ctx& c, float* out_ms, int cap) {
     if (c.step_events_used < 2) return 0;

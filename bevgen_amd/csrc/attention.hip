@@ -16,6 +16,7 @@
 // 2. decode_attention_kernel (+ combine) - Route A per-token decode against the growing KV cache: one query row per
 //    (sequence, head), HBM-bandwidth bound.  Lanes are laid out so every vector load is a fully coalesced 1 KiB
 //    (LPK lanes x 16 B cover one key row; 64/LPK keys per instruction); split-K over the context for occupancy.
+#include "ar_plan.h"
 #include "common.h"
 #include "kernels.h"
 #include "profiler.h"
@@ -400,15 +401,6 @@ __global__ __launch_bounds__(64) void decode_attention_combine_kernel(DecodeAttn
 void launch_decode_attention_combine(const DecodeAttnArgs& a, const float* ws, int S, hipStream_t s) {
     hipLaunchKernelGGL(decode_attention_combine_kernel, dim3(a.H, a.B), dim3(64), 0, s, a, ws, S);
     LAUNCH_CHECK();
-}
-
-int decode_attention_splits(int B, int H, int n_max) {
-    // B*H >= 192 workgroups already cover the chip: one 16-wave workgroup per (sequence, head), direct epilogue.
-    // Fewer than that: split the context over workgroups (at least 256 keys per split) and merge in a second kernel.
-    if ((long)B * H >= 192) return 1;
-    int S = 1;
-    while ((long)B * H * S < 1024 && n_max / (S * 2) >= 256) S *= 2;
-    return S;
 }
 
 size_t decode_attention_ws_bytes(int B, int H, int S) { return (size_t)B * H * S * 66 * sizeof(float); }

@@ -328,7 +328,7 @@ static void finalize_ar(Ctx& c) {
             // belong and no timed region is open - for decode_path = split and for auto unless the context was created for batches the auto rule never sends down
             // the split layer (cfg.max_batch > 4).  Only such a context, when it is later called with <= 4 sequences after all, packs on that first call
             // (ctx_pack_split_qkv: one allocation per layer + one stream synchronisation, once per context; documented in include/bevgen_hip.h)
-            if (g.decode_path == BEVGEN_DECODE_SPLIT || (g.decode_path == BEVGEN_DECODE_AUTO && g.max_batch <= 4)) pack_split_qkv_layer(c, l, 0);
+            if (g.decode_path == BEVGEN_DECODE_SPLIT || (g.decode_path == BEVGEN_DECODE_AUTO && g.max_batch <= kArAutoSplitMaxSeqs)) pack_split_qkv_layer(c, l, 0);
             l.mlp0_wp = reinterpret_cast<float*>(c.own(skinny_packed_floats(4 * D, D) * eb));
             l.mlp2_wp = reinterpret_cast<float*>(c.own(skinny_packed_floats(D, 4 * D) * eb));
             if (wf16) {
@@ -347,8 +347,9 @@ static void finalize_ar(Ctx& c) {
     if (fused_like) {   // state of the fused MLP launch (both projections of a layer in one launch, XCD-local exchange)
         c.mlpf_sync = reinterpret_cast<unsigned*>(c.own(mlp_fused_sync_words() * sizeof(unsigned)));
         HIP_CHECK(hipMemset(c.mlpf_sync, 0, mlp_fused_sync_words() * sizeof(unsigned)));
-        (void)mlp_fused_supported(1, D, wf16);   // (runs the device's one-time placement probe here, never inside a stream capture)
-
+        // CU count and XCD placement, asked once per context and only under a switch and for a width that admit the launch (runs the device's one-time placement
+        // probe here, never inside a stream capture)
+        c.mlpf_device_ok = mlp_fused_supported(1, D, wf16);
     }
     if (fused_like) {
         c.head_wp = reinterpret_cast<float*>(c.own(skinny_packed_floats(g.vocab_size, D) * (wf16 ? sizeof(_Float16) : sizeof(float))));

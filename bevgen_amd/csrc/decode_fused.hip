@@ -21,6 +21,7 @@
 #include <hip/hip_ext.h>
 #include <type_traits>
 
+#include "ar_plan.h"
 #include "common.h"
 #include "kernels.h"
 #include "profiler.h"
@@ -31,8 +32,6 @@ namespace bevgen {
 // Every load of an element is requested before the first one is used, and UNCONDITIONALLY: a predicated load (`k < ns ? p[k] : 0`) becomes a
 // divergent branch whose join point waits for the load, i.e. one serialised memory round trip per partial.  The launchers therefore make every
 // pointer valid (rowsrc_fix: absent partials / bias alias `base`) and the kernel only selects which values count.
-constexpr int ROWSRC_MAX_SPLITS = 8;   // (4 K slices of the MLP-down launch; 8 XCD planes of the fused MLP launch)
-constexpr int ROWSRC_RS_SPLITS = 4;    // the row-source form of skinny_fused_kernel (decode_path = split) keeps its register budget: at most 4 partials
 inline RowSrc rowsrc_fix(RowSrc r) {
     if (!r.partial || r.ns == 0) { r.partial = r.base; r.ns = 0; r.pstride = 0; r.pld = r.ld; }
     r.has_bias = r.bias != nullptr;
@@ -120,7 +119,6 @@ __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(
 __device__ __forceinline__ float4 mul4(float4 a, float4 b) { return make_float4(a.x * b.x, a.y * b.y, a.z * b.z, a.w * b.w); }
 constexpr long long MLPF_TIMEOUT_TICKS = 200LL * 1000 * 100;   // bound of the XCD-local barrier spin (ar_mlp_fused_kernel): 200 ms of the 100 MHz clock
 constexpr float kLog2eF = 1.44269504088896340736f;
-constexpr int AF_WAVES = 16;
 
 // One online-softmax state per query: running maximum (base-2 domain), denominator, weighted value sum of this lane's DPL dims.
 template <int DT, int NQ, int U>
@@ -805,11 +803,6 @@ size_t ar_attn_lds_bytes(int G, int Lpad) {
     return ((size_t)Lpad + (size_t)G * 64 + (size_t)G * 192 + (size_t)AF_WAVES * (G + 1) * 66) * sizeof(float) + ((size_t)Lpad / 16 + 2 + 8) * sizeof(uint16_t) + 1024;
 }
 
-size_t ar_attn_fused_lds_bytes(int G, int D, int Lpad) {
-    return ((size_t)Lpad + (size_t)G * D + (size_t)G * 192 + (size_t)AF_WAVES * (G + 1) * 66 + (size_t)AF_WAVES * G) * sizeof(float) + ((size_t)Lpad / 16 + 2 + 8) * sizeof(uint16_t) +
-           1024;   // (+ 1 KiB of slack)
-}
-
 // LDS a workgroup may allocate on the CURRENT device (gfx950: 160 KB), queried once per device: one process may drive contexts on several GPUs, and both this limit
 // and the > 64 KB opt-in below (hipFuncSetAttribute) are per-device state
 constexpr int MAX_DEVICES = 64;
@@ -849,8 +842,6 @@ void launch_ar_ln_fold(const float* W, const float* b, const float* gamma, const
     hipLaunchKernelGGL(ar_ln_fold_kernel, dim3(cdiv(N, 4)), dim3(256), 0, s, W, b, gamma, beta, cs, ds, N, K);
     LAUNCH_CHECK();
 }
-
-bool ar_attn_fused_supported(int B, int G, int D, int H) { return D == H * 64 && D % 4 == 0 && D <= 1024 && (G == 1 || G == 2 || G == 4) && B % G == 0; }
 
 void launch_ar_attn_fused(const ArAttnFusedArgs& a0, hipStream_t s) {
     ArAttnFusedArgs a = a0;
@@ -934,8 +925,6 @@ void launch_ar_attn_fused(const ArAttnFusedArgs& a0, hipStream_t s) {
 // optionally LayerNorm-ed (two-pass statistics, 32 values per lane, lanes -> waves through LDS), and stored k-chunk-major
 // ([k/4][16 rows][4]) so that both the staging stores and the MFMA operand reads are contiguous 1 KiB per wave (conflict free).
 // v_mfma_f32_16x16x4_f32 (exact fp32): the four k-slots of one MFMA are the four 16-lane quarters, quarter q owns k = 16c + 4q .. +3.
-constexpr int SF_WAVES = 8;
-
 __device__ __forceinline__ float4 ldg_nt4(const float* p) {
     const f32x4 v = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(p));
     return make_float4(v[0], v[1], v[2], v[3]);
@@ -1543,12 +1532,12 @@ static bool xcd_placement_ok() {
 bool xcd_placement_verified() { return xcd_placement_ok(); }
 
 bool mlp_fused_supported(int M, int D, bool w_f16) {
-    static const int env = getenv("BEVGEN_MLP_FUSE") ? atoi(getenv("BEVGEN_MLP_FUSE")) : 1;
-    if (!env || M < 1 || M > 64 || D != 1024) return false;   // (the K slices per wave - 128 of D, 64 of the XCD's D / 2 - are written out for D = 1024)
+    static const int env = ar_switches().mlp_fuse;   // ($BEVGEN_MLP_FUSE, once per process)
+    if (!env || !mlp_fused_shape_ok(M, D)) return false;
     int dev = 0, cus = 0;
     if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return false;
     (void)w_f16;
-    return cus >= 4 * D / 16 && xcd_placement_ok();   // one workgroup per CU: every workgroup of an XCD must be resident at once; workgroup i on XCD i % 8
+    return mlp_fused_cus_ok(cus, D) && xcd_placement_ok();
 }
 
 void launch_ar_mlp_fused(const MlpFusedArgs& g, hipStream_t s) {
@@ -1615,27 +1604,6 @@ void launch_pack_skinny_weight(const float* W, float* Wp, int N, int K, hipStrea
     const long total = (long)cdiv(N, 16) * (K >> 4) * 64;
     hipLaunchKernelGGL(pack_skinny_weight_kernel, dim3(cdiv(total, 256)), dim3(256), 0, s, W, Wp, N, K);
     LAUNCH_CHECK();
-}
-
-int skinny_fused_ksplit(int N, int K) {
-    // the K slice of one workgroup is at most 1024 (A tile in LDS, W slice in registers); beyond that, split until the grid covers the chip
-    int s = 1;
-    while (K / s > 1024 || (s < ROWSRC_RS_SPLITS && cdiv(N, 16) * s < 192 && (K / (s * 2)) % (SF_WAVES * 16) == 0 && K / (s * 2) >= 256)) s *= 2;
-    return s;
-}
-
-bool skinny_fused_supported(int M, int N, int K, bool ln) {
-    if (M < 1 || M > 64 || K % 4 != 0) return false;
-    const int s = ln ? 1 : skinny_fused_ksplit(N, K);
-    if (K % s != 0 || s > ROWSRC_RS_SPLITS) return false;   // the consumer's row source adds at most ROWSRC_RS_SPLITS partials
-    const int kw = K / s;
-    return kw <= 1024 && kw % (SF_WAVES * 16) == 0;
-}
-
-// fp16 weight images: the K slice of a workgroup must be a multiple of 32 per wave
-bool skinny_fused_f16_ok(int N, int K, bool ln) {
-    const int s = ln ? 1 : skinny_fused_ksplit(N, K);
-    return K % s == 0 && (K / s) % (SF_WAVES * 32) == 0;
 }
 
 void launch_skinny_fused(const SkinnyFusedArgs& g0, hipStream_t s) {

@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "ar_plan.h"
 
 namespace bevgen {
 
@@ -259,7 +260,6 @@ struct DecodeAttnArgs {
     int group = 1;
     unsigned* status = nullptr;      // the context's device status word, filled in by the launcher
 };
-int decode_attention_splits(int B, int H, int n_max);
 size_t decode_attention_ws_bytes(int B, int H, int S);
 void launch_decode_attention_ws(const DecodeAttnArgs& a, float* ws, int S, hipStream_t s);
 void launch_decode_attention_combine(const DecodeAttnArgs& a, const float* ws, int S, hipStream_t s);   // o / l (+ R) from [B][H][S][66] partials
@@ -307,7 +307,6 @@ struct ArAttnFusedArgs {
     int has_bias = 0;                  // filled in by the launcher
     unsigned* status = nullptr;        // the context's device status word, filled in by the launcher (fp16 cache: a key / value outside the fp16 range raises BG_ST_F16_RANGE)
 };
-bool ar_attn_fused_supported(int B, int G, int D, int H);
 // per-row constants of LayerNorm folded into a projection: cs[j] = sum_k W[j][k] gamma[k], ds[j] = sum_k W[j][k] beta[k] + b[j]   (W [N, K] row-major; fp64 accumulation)
 void launch_ar_ln_fold(const float* W, const float* b, const float* gamma, const float* beta, float* cs, float* ds, int N, int K, hipStream_t s);
 void launch_ar_attn_fused(const ArAttnFusedArgs& a, hipStream_t s);
@@ -349,17 +348,13 @@ struct MlpFusedArgs {
     long long* trace = nullptr;
     int acq = 1;                                       // acquire form of the exchange (decode_fused.hip), filled in by the launcher
 };
-constexpr int MLP_FUSED_PLANES = 8;
 size_t mlp_fused_sync_words();
-bool mlp_fused_supported(int M, int D, bool w_f16);    // shape + device (CU count) check
+ArSwitches ar_switches();                              // ar.cpp: Route A's environment switches (ar_plan.h)
+bool mlp_fused_supported(int M, int D, bool w_f16);    // switch + shape (ar_plan.h) + device (CU count, XCD placement) check
 void launch_ar_mlp_fused(const MlpFusedArgs& g, hipStream_t s);
 size_t skinny_packed_floats(int N, int K);
 void launch_pack_skinny_weight(const float* W, float* Wp, int N, int K, hipStream_t s);
 void launch_pack_skinny_weight_f16(const float* W, void* Wp /* N16 * K halves */, int N, int K, hipStream_t s);
-int skinny_fused_ksplit(int N, int K);
-bool skinny_fused_supported(int M, int N, int K, bool ln);
-bool skinny_fused_f16_ok(int N, int K, bool ln);   // fp16 weight image: K slice per wave a multiple of 32
-size_t ar_attn_fused_lds_bytes(int G, int D, int Lpad);
 size_t ar_attn_fused_max_lds();   // LDS bytes a workgroup may allocate on the current device
 size_t ar_attn_lds_bytes(int G, int Lpad);   // the attention-only kernel (decode_path = split)
 void launch_skinny_fused(const SkinnyFusedArgs& g, hipStream_t s);

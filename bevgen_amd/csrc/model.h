@@ -158,10 +158,11 @@ struct Ctx {
     std::vector<std::pair<hipGraphExec_t, hipGraph_t>> retired_graphs;
     // the instantiated decode-step graph is kept and replayed by later bevgen_ar_sample calls that bake in the same pointers / parameters
     struct GraphKey {
-        int B = 0, G = 0, top_k = 0, greedy = 0, kv = 0, chains = 0; float temperature = 0.f;
+        int B = 0, G = 0, top_k = 0, greedy = 0, kv = 0; float temperature = 0.f;
+        bool fused = false, split = false, mlp_fused = false; int chains = 0;   // the captured step's shape (ArStepPlan)
         const void *noise = nullptr, *forced = nullptr, *out = nullptr, *arena = nullptr, *persist = nullptr, *trace = nullptr;
         bool operator==(const GraphKey& o) const {
-            return B == o.B && G == o.G && chains == o.chains && top_k == o.top_k && greedy == o.greedy && kv == o.kv && temperature == o.temperature && noise == o.noise &&
+            return B == o.B && G == o.G && fused == o.fused && split == o.split && mlp_fused == o.mlp_fused && chains == o.chains && top_k == o.top_k && greedy == o.greedy && kv == o.kv && temperature == o.temperature && noise == o.noise &&
                    forced == o.forced && out == o.out && arena == o.arena && persist == o.persist && trace == o.trace;
         }
     } graph_key;
@@ -176,6 +177,7 @@ struct Ctx {
     // under the tail of their K/V walk.  Measured slower on the same box (1.55 -> 1.65 / 1.61 ms/step, profiles/r03_ab_prefetch.txt): default off
     // fused MLP launch of the decode step (decode_fused.hip ar_mlp_fused_kernel): barrier words (device, zeroed at finalize) and the host-visible error word
     unsigned* mlpf_sync = nullptr;
+    bool mlpf_device_ok = false;  // the device holds the launch's whole grid on XCDs placed as the exchange needs (bevgen_finalize; ArPlanIn::mlpf_device_ok)
     bool mlpf_disabled = false;   // a fused MLP launch of this context reported a timeout / wrong placement: every later step takes the two-launch form
     // device status word (common.h BG_ST_*): one mapped host word per context, allocated at bevgen_create; kernels OR bits into it, the host reads it without synchronising
     unsigned *status_host = nullptr, *status_dev = nullptr;
