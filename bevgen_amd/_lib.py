@@ -16,13 +16,14 @@ HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "bevgen_hip.h")
 ABI_VERSION = 10
 ROUTE_MASKGIT, ROUTE_AR = 0, 1
 PRECISION_FP32, PRECISION_BF16, PRECISION_F16X3, PRECISION_F16X1 = 0, 1, 2, 3
-KV_F32, KV_F16 = 0, 1
+KV_F32, KV_F16, KV_I8 = 0, 1, 2
 DECODE_FUSED, DECODE_PER_OP, DECODE_SPLIT, DECODE_AUTO = 0, 1, 2, 3
 VQ_OUT_RAW, VQ_OUT_DENORM, VQ_OUT_U8 = 0, 1, 2
 W_F32, W_F16 = 0, 1
 DTYPE_F32, DTYPE_I64, DTYPE_U8, DTYPE_F64 = 0, 1, 2, 3
 ERR_NUMERIC = -5
 STATUS_MLP_BARRIER, STATUS_MLP_PLACEMENT, STATUS_NONFINITE_LOGITS, STATUS_F16_RANGE, STATUS_NONFINITE_PIXELS, STATUS_NONFINITE_LATENTS = 1, 2, 4, 8, 16, 32
+STATUS_KV_NONFINITE = 64
 
 
 class BevgenError(RuntimeError):

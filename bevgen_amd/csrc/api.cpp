@@ -49,7 +49,7 @@ int bevgen_create(const bevgen_cfg* cfg, int device, bevgen_ctx** out) {
         BG_REQUIRE(cfg && out, "bevgen_create: null argument");
         BG_REQUIRE(cfg->abi_version == BEVGEN_ABI_VERSION, "bevgen_create: ABI version %d, library is %d", cfg->abi_version, BEVGEN_ABI_VERSION);
         BG_REQUIRE(cfg->route == BEVGEN_ROUTE_MASKGIT || cfg->route == BEVGEN_ROUTE_AR, "bevgen_create: unknown route %d", cfg->route);
-        BG_REQUIRE(cfg->kv_cache_dtype == BEVGEN_KV_F32 || cfg->kv_cache_dtype == BEVGEN_KV_F16, "bevgen_create: kv_cache_dtype must be BEVGEN_KV_F32 or BEVGEN_KV_F16");
+        BG_REQUIRE(cfg->kv_cache_dtype == BEVGEN_KV_F32 || cfg->kv_cache_dtype == BEVGEN_KV_F16 || cfg->kv_cache_dtype == BEVGEN_KV_I8, "bevgen_create: kv_cache_dtype must be BEVGEN_KV_F32, BEVGEN_KV_F16 or BEVGEN_KV_I8");
         const bool f16x1 = cfg->precision == BEVGEN_PRECISION_F16X1;
         BG_REQUIRE(cfg->precision == BEVGEN_PRECISION_FP32 || cfg->precision == BEVGEN_PRECISION_F16X3 || f16x1,
                    "bevgen_create: precision must be BEVGEN_PRECISION_FP32, BEVGEN_PRECISION_F16X3 or BEVGEN_PRECISION_F16X1");
@@ -700,6 +700,7 @@ int bevgen_op_attention_ex(bevgen_ctx* ctx, const float* q, const float* k, cons
 int bevgen_op_decode_attention(bevgen_ctx* ctx, const float* q, const void* kc, const void* vc, int kv_dtype, const float* bias, int ldbias, const uint8_t* keep,
                                int ldkeep, long keep_head_stride, int B, int H, int n, int Lmax, float scale, float* out, void* stream) {
     return guarded(ctx, [&] {
+        BG_REQUIRE(kv_dtype >= 0 && kv_dtype <= 2, "op_decode_attention: kv_dtype %d", kv_dtype);
         DecodeAttnArgs a;
         a.q = q; a.ldq = H * 64; a.kcache = kc; a.vcache = vc; a.kv_dtype = kv_dtype;
         a.bias = bias; a.ldbias = ldbias;
@@ -718,7 +719,7 @@ int bevgen_op_ar_attn_fused(bevgen_ctx* ctx, const float* x, const float* partia
     return guarded(ctx, [&] {
         hipStream_t s = (hipStream_t)stream;
         const int D = H * 64, L = Lmax;
-        BG_REQUIRE(x && ln_w && ln_b && wqkv && bqkv && kc && vc && out && n >= 1 && n <= Lmax, "op_ar_attn_fused: bad arguments");
+        BG_REQUIRE(x && ln_w && ln_b && wqkv && bqkv && kc && vc && out && n >= 1 && n <= Lmax && kv_dtype >= 0 && kv_dtype <= 2, "op_ar_attn_fused: bad arguments");
         BG_REQUIRE(ar_attn_fused_supported(B, G, D, H), "op_ar_attn_fused: unsupported shape B=%d G=%d D=%d H=%d", B, G, D, H);
         BG_REQUIRE(!layout || (block >= 1 && L % block == 0), "op_ar_attn_fused: Lmax %d is not a multiple of the block size %d", L, block);
         const int nb = layout ? L / block : 0, cld = (int)cdiv(L, 16) + 1;
@@ -1043,7 +1044,7 @@ int bevgen_op_kv_cache_write(bevgen_ctx* ctx, int kind, const float* qkv, float*
                              int layers, int rows, int src, int dst0, int count, void* stream) {
     return guarded(ctx, [&] {
         hipStream_t s = (hipStream_t)stream;
-        BG_REQUIRE(kind >= 0 && kind <= 2 && kc && vc && (kv_dtype == 0 || kv_dtype == 1) && B >= 1 && H >= 1 && Lmax >= 1, "op_kv_cache_write: bad arguments");
+        BG_REQUIRE(kind >= 0 && kind <= 2 && kc && vc && kv_dtype >= 0 && kv_dtype <= 2 && B >= 1 && H >= 1 && Lmax >= 1, "op_kv_cache_write: bad arguments");
         if (kind == 0) {
             BG_REQUIRE(qkv && n >= 1 && pos0 >= 0 && pos0 + n <= Lmax, "op_kv_cache_write (scatter): rows [%d, %d) do not fit Lmax = %d", pos0, pos0 + n, Lmax);
             launch_ar_qkv_scatter(qkv, q, kc, vc, kv_dtype, B, H, n, pos0, Lmax, s);
@@ -1053,7 +1054,7 @@ int bevgen_op_kv_cache_write(bevgen_ctx* ctx, int kind, const float* qkv, float*
         } else {
             BG_REQUIRE(layers >= 1 && rows >= 0 && rows <= Lmax && src >= 0 && src < B && dst0 >= 0 && count >= 0 && dst0 + count <= B,
                        "op_kv_cache_write (replicate_prefix): slots [%d, %d) / source %d / %d rows do not fit B = %d, Lmax = %d", dst0, dst0 + count, src, rows, B, Lmax);
-            launch_replicate_prefix(kc, vc, layers, B, H, Lmax, rows, src, dst0, count, kv_dtype == 0 ? 4 : 2, s);
+            launch_replicate_prefix(kc, vc, layers, B, H, Lmax, rows, src, dst0, count, kv_dtype == 0 ? 4 : kv_dtype == 1 ? 2 : 1, s);
         }
     });
 }

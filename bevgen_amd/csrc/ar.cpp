@@ -69,8 +69,17 @@ void gemm(const float* A, int lda, const float* W, int ldb, const float* bias, f
     launch_gemm(gemm_args(A, lda, W, ldb, bias, C, ldc, M, N, K, act, R, ldr), s);
 }
 
-size_t cache_elem_bytes(const Ctx& c) { return c.cfg.kv_cache_dtype == BEVGEN_KV_F16 ? 2 : 4; }
-int cache_dtype(const Ctx& c) { return c.cfg.kv_cache_dtype == BEVGEN_KV_F16 ? 1 : 0; }
+int cache_dtype(const Ctx& c) { return c.cfg.kv_cache_dtype == BEVGEN_KV_F16 ? 1 : c.cfg.kv_cache_dtype == BEVGEN_KV_I8 ? 2 : 0; }
+// The KV cache of one layer, K or V: [B, H, L, 64] elements; the int8 mode appends its [B, H, L] fp32 row scales (bevgen_hip.h).  Every size, stride and offset of the cache
+// goes through these three.
+size_t cache_layer_bytes(const Ctx& c, int B) {
+    const size_t rows = (size_t)B * c.H * c.L;
+    switch (cache_dtype(c)) { case 1: return rows * 128; case 2: return rows * kKvI8RowBytes; default: return rows * 256; }
+}
+size_t cache_slot_bytes(const Ctx& c, int b0) { return (size_t)b0 * c.H * c.L * 64 * (cache_dtype(c) == 0 ? 4 : cache_dtype(c) == 1 ? 2 : 1); }   // slot b0's first element inside a layer
+// int8: bytes from slot b0's codes to slot b0's scales, in a layer of B slots (the kernels' sc_off; unused otherwise)
+long cache_scale_off(const Ctx& c, int B, int b0) { return (long)c.H * c.L * (64L * B - 60L * b0); }
+int replicate_elem_bytes(const Ctx& c) { return cache_dtype(c) == 0 ? 4 : cache_dtype(c) == 1 ? 2 : 1; }
 
 struct StepWs {
     float *x, *xn, *qkv, *x2, *h, *m1, *dec_ws, *gemm_ws, *logits;
@@ -151,13 +160,13 @@ struct PrefixRows {
     const float* bias; uint16_t* tiles;     // masked bias [keep_heads][R][Rpad] and its tile lists
     float* layer_bias;                      // non-null: bias and tiles of THIS layer are built here, behind the scatters (ar_prefill with per-layer layouts)
 };
-void prefix_layer(Ctx& c, int i, const PrefixRows& p, hipStream_t s) {
+void prefix_layer(Ctx& c, int i, const PrefixRows& p, hipStream_t s, long sc_off = 0) {
     const ArLayer& l = c.ar[i];
     const int D = c.D, H = c.H, rows = p.nseq * p.R;
     launch_layernorm(p.x, D, l.ln1_w, l.ln1_b, p.xn, D, rows, D, 1e-5f, s);
     gemm(p.xn, D, l.wqkv, D, l.bqkv, p.qkv, 3 * D, rows, 3 * D, D, ACT_NONE, nullptr, 0, s);
     launch_ar_qkv_scatter(p.qkv, p.Q, p.k, p.v, 0, p.nseq, H, p.R, 0, p.Lk, s);                                                    // what this pass's attention reads
-    if (p.kcache) launch_ar_qkv_scatter(p.qkv, nullptr, p.kcache, p.vcache, cache_dtype(c), p.nseq, H, p.R, 0, c.L, s);   // the persistent rows [0, R) the decode steps read
+    if (p.kcache) launch_ar_qkv_scatter(p.qkv, nullptr, p.kcache, p.vcache, cache_dtype(c), p.nseq, H, p.R, 0, c.L, s, sc_off);   // the persistent rows [0, R) the decode steps read
     if (p.layer_bias) build_layer_bias(c, i, p.layer_bias, p.tiles, p.R, p.Rpad, s);
     AttnArgs a = attn_args(p.Q, p.k, p.v, p.Lk, p.layer_bias ? p.layer_bias : p.bias, p.tiles, c.keep_heads > 1, p.nseq, H, p.R, p.Rpad);
     a.R = p.xn; a.O = p.x2; a.o_bstride = (long)p.R * D; a.o_qstride = D; a.o_hstride = 64;
@@ -232,9 +241,10 @@ void sparse_self_attention_op(Ctx& c, const float* q, const float* k, const floa
 // persistent per-batch state of a decode (K/V cache of every layer, geometric embeddings, newest hidden row, device step counter): zeroed cache, step 0
 static void ar_state_setup(Ctx& c, int B, hipStream_t s) {
     const auto& g = c.cfg;
-    const int D = c.D, H = c.H, L = c.L;
+    const int D = c.D, L = c.L;
     auto& st = c.ars;
-    const size_t cache_b = (size_t)g.num_layers * B * H * L * 64 * cache_elem_bytes(c);
+    BG_REQUIRE(cache_dtype(c) != 2 || L % 4 == 0, "kv_cache = i8: the sequence length %d must be a multiple of 4 (16-byte aligned layers)", L);
+    const size_t cache_b = (size_t)g.num_layers * cache_layer_bytes(c, B);
     st.B = B;
     st.step = 0;
     c.persist.carve([&](Arena& a) {
@@ -299,7 +309,7 @@ void ar_prefill(Ctx& c, const int64_t* cond, const float* I_inv, const float* E_
         HIP_CHECK(hipMemsetAsync(tk, 0, (size_t)G * H * c.Kpad * 64 * sizeof(float), s));   // pad rows K..Kpad stay zero
         HIP_CHECK(hipMemsetAsync(tv, 0, (size_t)G * H * c.Kpad * 64 * sizeof(float), s));
     }
-    const size_t layer_bytes_p = (size_t)B * H * L * 64 * cache_elem_bytes(c);
+    const size_t layer_bytes_p = cache_layer_bytes(c, B);
     BG_REQUIRE(c.Kpad <= L, "condition length padded to %d exceeds the cache length %d", c.Kpad, L);
     PrefixRows p{G, K, c.Kpad, x, xn, x2, h, qkv, m1, Q, tk, tv, c.Kpad, nullptr, nullptr, c.prefill_bias, ltiles, lbias};
     for (int i = 0; i < g.num_layers; ++i) {   // all G K rows at once, into cache slots [0, G) for now
@@ -307,7 +317,7 @@ void ar_prefill(Ctx& c, const int64_t* cond, const float* I_inv, const float* E_
         char* vcb = reinterpret_cast<char*>(st.vcache) + i * layer_bytes_p;
         if (kvd) { p.kcache = kcb; p.vcache = vcb; }                                                               // the fp16 image the decode steps read
         else { p.k = reinterpret_cast<float*>(kcb); p.v = reinterpret_cast<float*>(vcb); p.Lk = L; }   // the attention reads the cache itself
-        prefix_layer(c, i, p, s);
+        prefix_layer(c, i, p, s, cache_scale_off(c, B, 0));   // (G of the layer's B slots are written)
     }
     st.G = 1;
     if (S == 1) {
@@ -319,11 +329,11 @@ void ar_prefill(Ctx& c, const int64_t* cond, const float* I_inv, const float* E_
         // (a destination never holds a source that is still needed); the other slots of the group keep only their private rows >= K
         st.G = S;
         for (int gi = G - 1; gi >= 1; --gi)
-            launch_replicate_prefix(st.kcache, st.vcache, g.num_layers, B, H, L, K, gi, gi * S, 1, (int)cache_elem_bytes(c), s);
+            launch_replicate_prefix(st.kcache, st.vcache, g.num_layers, B, H, L, K, gi, gi * S, 1, replicate_elem_bytes(c), s);
     } else {
         // per-operator path: fan the shared prefix out into every slot of the group
         for (int gi = G - 1; gi >= 0; --gi)
-            launch_replicate_prefix(st.kcache, st.vcache, g.num_layers, B, H, L, K, gi, gi * S, S, (int)cache_elem_bytes(c), s);
+            launch_replicate_prefix(st.kcache, st.vcache, g.num_layers, B, H, L, K, gi, gi * S, S, replicate_elem_bytes(c), s);
     }
     launch_gather_rows(x, hid, G, K - 1, K, D, s);
     for (int j = 0; j < S; ++j)
@@ -362,13 +372,12 @@ static void decode_chain_launch(Ctx& c, StepWs& w, const ArStepPlan& plan, const
     const auto& g = c.cfg;
     auto& st = c.ars;
     const int D = c.D, H = c.H, B = st.B, Bc = plan.Bc, L = c.L;
-    const size_t eb = cache_elem_bytes(c);
     float* x = w.x + (size_t)r0 * D;
     if (!(st.pick_embeds && tok == w.tok && r0 == 0 && Bc == B))   // (ar_sample's pick launch already wrote the new rows' embeddings)
     launch_ar_step_embed(tok + r0, c.pf("x_tok_emb.weight"), st.img_embed ? st.img_embed + (size_t)r0 * g.num_cams * c.T * D : nullptr, c.pf("x_pos_emb"), c.fwd_idx,
                          st.d_step, x, Bc, g.num_cams, c.T, D, g.vocab_size + 1, s);
-    const size_t layer_bytes = (size_t)B * H * L * 64 * eb;
-    const size_t chain_off = (size_t)r0 * H * L * 64 * eb;    // this chain's first cache slot inside a layer
+    const size_t layer_bytes = cache_layer_bytes(c, B);
+    const size_t chain_off = cache_slot_bytes(c, r0);         // this chain's first cache slot inside a layer
     const int ks = plan.down_ksplit;
     const int wf16 = g.decode_weight_dtype == BEVGEN_W_F16;
     float* part = w.part + (size_t)ks * r0 * D;               // [ks][Bc][D] per chain, chains back to back
@@ -400,7 +409,7 @@ static void decode_chain_launch(Ctx& c, StepWs& w, const ArStepPlan& plan, const
         }
         a.kcache = reinterpret_cast<char*>(st.kcache) + i * layer_bytes + chain_off;
         a.vcache = reinterpret_cast<char*>(st.vcache) + i * layer_bytes + chain_off;
-        a.kv_dtype = cache_dtype(c);
+        a.kv_dtype = cache_dtype(c); a.sc_off = cache_scale_off(c, B, r0);
         a.bias = c.attn_bias; a.ldbias = L;
         a.vis = c.vis_of_layer(i);
         a.out = x2; a.ldo = D;
@@ -493,7 +502,7 @@ static void decode_step_launch(Ctx& c, StepWs& w, const ArStepPlan& plan, const 
     }
     const int D = c.D, H = c.H, B = st.B, L = c.L;
     launch_ar_step_embed(tok, c.pf("x_tok_emb.weight"), st.img_embed, c.pf("x_pos_emb"), c.fwd_idx, st.d_step, w.x, B, g.num_cams, c.T, D, g.vocab_size + 1, s);
-    const size_t layer_bytes = (size_t)B * H * L * 64 * cache_elem_bytes(c);
+    const size_t layer_bytes = cache_layer_bytes(c, B);
     const float* xin = w.x;
     for (int i = 0; i < g.num_layers; ++i) {
         const ArLayer& l = c.ar[i];
@@ -685,18 +694,16 @@ void ar_forward(Ctx& c, const int64_t* cond, const float* I_inv, const float* E_
     launch_ar_seq_embed(ids, c.pf("x_tok_emb.weight"), st.img_embed, c.pf("x_pos_emb"), c.fwd_idx, x, B, n, R, K, c.N, D, g.vocab_size + 1, s);
 
     // ---- layers
-    const size_t eb = cache_elem_bytes(c);
-    const size_t layer_bytes = (size_t)B * H * L * 64 * eb;
-    const size_t seq_bytes = (size_t)H * L * 64 * eb;
+    const size_t layer_bytes = cache_layer_bytes(c, B);
     PrefixRows p{0, R, Rpad, nullptr, xn, x2, h, qkv, m1, Q, tk, tv, Rpad, nullptr, nullptr, bias, tiles, nullptr};
     for (int i = 0; i < g.num_layers; ++i) {
         if (i == 0 || c.keep_layers > 1) build_layer_bias(c, i, bias, tiles, R, Rpad, s);   // shared layout (density 1): one bias image and one set of tile lists per call
         for (int b0 = 0; b0 < B; b0 += Bg) {
             p.nseq = std::min(Bg, B - b0);
             p.x = x + (size_t)b0 * R * D;
-            p.kcache = reinterpret_cast<char*>(st.kcache) + i * layer_bytes + b0 * seq_bytes;   // (fp32 or fp16)
-            p.vcache = reinterpret_cast<char*>(st.vcache) + i * layer_bytes + b0 * seq_bytes;
-            prefix_layer(c, i, p, s);
+            p.kcache = reinterpret_cast<char*>(st.kcache) + i * layer_bytes + cache_slot_bytes(c, b0);   // (fp32, fp16 or int8 codes)
+            p.vcache = reinterpret_cast<char*>(st.vcache) + i * layer_bytes + cache_slot_bytes(c, b0);
+            prefix_layer(c, i, p, s, cache_scale_off(c, B, b0));
         }
     }
 

@@ -227,6 +227,17 @@ template <> struct KvTraits<1> {  // fp16 rows: 128 B = 8 lanes x 16 B
         for (int i = 0; i < 8; ++i) out[i] = (float)v[i];
     }
 };
+template <> struct KvTraits<2> {  // int8 rows: 64 B = 8 lanes x 8 B of codes; the row's fp32 scale is applied to the score / the probability, not per element
+    static constexpr int LPK = 8, DPL = 8;
+    __device__ static __forceinline__ void load(const void* base, long row, int sub, float (&out)[8]) {
+        const uint2 v = *reinterpret_cast<const uint2*>(reinterpret_cast<const char*>(base) + row * 64 + sub * 8);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            out[i] = (float)(int)(signed char)(v.x >> (8 * i));
+            out[4 + i] = (float)(int)(signed char)(v.y >> (8 * i));
+        }
+    }
+};
 
 constexpr int DEC_UNROLL = 4;
 
@@ -286,7 +297,13 @@ __global__ __launch_bounds__(NW * 64) void decode_attention_kernel(DecodeAttnArg
             void* cache = const_cast<void*>(is_v ? a.vcache : a.kcache);
             const long idx = (cache_row0 + row) * 64 + d;
             if (DT == 0) reinterpret_cast<float*>(cache)[idx] = val;
-            else {
+            else if (DT == 2) {   // (waves 0 / 1 hold the k / v row)
+                float sc;
+                bool bad;
+                const int code = kv_i8_quant(val, sc, bad);
+                kv_i8_store_row(cache, a.sc_off, cache_row0 + row, d, code, sc);
+                if (bad && d == 0) status_raise(a.status, BG_ST_KV_NONFINITE);
+            } else {
                 const _Float16 hv = (_Float16)val;
                 unsigned bad = 0;
                 guard_half(hv, bad);
@@ -304,7 +321,7 @@ __global__ __launch_bounds__(NW * 64) void decode_attention_kernel(DecodeAttnArg
     constexpr int stride = NW * KPI;  // keys consumed per unroll slot by the workgroup's waves
     const int iters = k_end > k_begin ? (k_end - k_begin + stride * DEC_UNROLL - 1) / (stride * DEC_UNROLL) : 0;
     for (int it = 0; it < iters; ++it) {
-        float kx[DEC_UNROLL][DPL], vx[DEC_UNROLL][DPL], sc[DEC_UNROLL];
+        float kx[DEC_UNROLL][DPL], vx[DEC_UNROLL][DPL], sc[DEC_UNROLL], ksc[DEC_UNROLL], vsc[DEC_UNROLL];
         int key[DEC_UNROLL];
 #pragma unroll
         for (int u = 0; u < DEC_UNROLL; ++u) {
@@ -312,6 +329,10 @@ __global__ __launch_bounds__(NW * 64) void decode_attention_kernel(DecodeAttnArg
             const int kc = min(key[u], k_end - 1);  // clamped address, masked below
             T::load(a.kcache, cache_row0 + kc, sub, kx[u]);
             T::load(a.vcache, cache_row0 + kc, sub, vx[u]);
+            if (DT == 2) {
+                ksc[u] = reinterpret_cast<const float*>(reinterpret_cast<const char*>(a.kcache) + a.sc_off)[cache_row0 + kc];
+                vsc[u] = reinterpret_cast<const float*>(reinterpret_cast<const char*>(a.vcache) + a.sc_off)[cache_row0 + kc];
+            }
         }
         float mx = m_run;
 #pragma unroll
@@ -320,6 +341,7 @@ __global__ __launch_bounds__(NW * 64) void decode_attention_kernel(DecodeAttnArg
 #pragma unroll
             for (int i = 0; i < DPL; ++i) d = fmaf(qv[i], kx[u][i], d);
             d = group_sum<LPK>(d);
+            if (DT == 2) d *= ksc[u];   // the key row's scale, once per score
             const int kc = min(key[u], k_end - 1);
             const bool ok = key[u] < k_end && (!vis.has_allowed || arow[kc]) && (!vis.has_lay || lrow[kc / vis.blk]);
             sc[u] = ok ? d + (bias_row ? bias_row[kc] * (a.scale * kLog2eDec) : 0.f) : kNegBig;
@@ -333,8 +355,9 @@ __global__ __launch_bounds__(NW * 64) void decode_attention_kernel(DecodeAttnArg
         for (int u = 0; u < DEC_UNROLL; ++u) {
             const float p = sc[u] <= kNegBig ? 0.f : __builtin_amdgcn_exp2f(sc[u] - mx);
             l_run += p;
+            const float pv = DT == 2 ? p * vsc[u] : p;   // the value row's scale rides on the probability (accumulator only)
 #pragma unroll
-            for (int i = 0; i < DPL; ++i) acc[i] = fmaf(p, vx[u][i], acc[i]);
+            for (int i = 0; i < DPL; ++i) acc[i] = fmaf(pv, vx[u][i], acc[i]);
         }
         m_run = mx;
     }
@@ -414,10 +437,14 @@ void launch_decode_attention_ws(const DecodeAttnArgs& a0, float* ws, int S, hipS
     dim3 grid(S, a.H, a.B);
     // algorithmic bytes of one launch: K and V rows of the visible context, once each (2 * n * 64 * elem per (sequence, head))
     const double n_host = a.d_n ? a.n + a.n_hint : a.n;
-    ProfScope prof(PROF_DECODE_ATTN, 2.0 * a.B * a.H * n_host * 64 * (a.kv_dtype == 0 ? 4 : 2), s);
+    BG_REQUIRE(a.kv_dtype >= 0 && a.kv_dtype <= 2, "decode attention: kv_dtype %d", a.kv_dtype);
+    if (!a.sc_off) a.sc_off = 64L * a.B * a.H * a.Lmax;
+    ProfScope prof(PROF_DECODE_ATTN, 2.0 * a.B * a.H * n_host * (a.kv_dtype == 0 ? 256.0 : a.kv_dtype == 1 ? 128.0 : (double)kKvI8RowBytes), s);
     if (S == 1) {
         if (a.kv_dtype == 0)
             hipLaunchKernelGGL((decode_attention_kernel<0, 16>), grid, dim3(1024), 0, s, a, ws, S);
+        else if (a.kv_dtype == 2)
+            hipLaunchKernelGGL((decode_attention_kernel<2, 16>), grid, dim3(1024), 0, s, a, ws, S);
         else
             hipLaunchKernelGGL((decode_attention_kernel<1, 16>), grid, dim3(1024), 0, s, a, ws, S);
         LAUNCH_CHECK();
@@ -425,6 +452,8 @@ void launch_decode_attention_ws(const DecodeAttnArgs& a0, float* ws, int S, hipS
     }
     if (a.kv_dtype == 0)
         hipLaunchKernelGGL((decode_attention_kernel<0, 4>), grid, dim3(256), 0, s, a, ws, S);
+    else if (a.kv_dtype == 2)
+        hipLaunchKernelGGL((decode_attention_kernel<2, 4>), grid, dim3(256), 0, s, a, ws, S);
     else
         hipLaunchKernelGGL((decode_attention_kernel<1, 4>), grid, dim3(256), 0, s, a, ws, S);
     LAUNCH_CHECK();

@@ -69,7 +69,8 @@ enum : unsigned {
     BG_ST_F16_RANGE = 8u,        // a value written as an f16 operand (hi/lo planes of precision = f16x3, fp16 KV cache, fp16 decode activations) was NaN or |v| >= 65520:
                                  // the f16 image is inf / NaN where the reference's bf16 / fp32 arithmetic has an 8-bit exponent
     BG_ST_NONFINITE_PIXELS = 16u,// the VQGAN decoder produced a NaN / inf pixel
-    BG_ST_NONFINITE_LATENTS = 32u // the VQGAN quantizer met a row without a finite distance to any codebook entry (its id is written as 0)
+    BG_ST_NONFINITE_LATENTS = 32u,// the VQGAN quantizer met a row without a finite distance to any codebook entry (its id is written as 0)
+    BG_ST_KV_NONFINITE = 64u     // a key / value row written into the int8 KV cache held a NaN / inf (its row scale is meaningless)
 };
 // device address of the status word of the context whose C-ABI call is executing on this host thread (null outside a call): the launchers of the flagged kernels read it
 unsigned* status_current();
@@ -80,6 +81,30 @@ __device__ __forceinline__ void status_raise(unsigned* st, unsigned bits) {
 // both halves of a packed f16 pair: non-zero where the exponent field is all ones (inf / NaN) - three integer operations per pair
 __device__ __forceinline__ unsigned f16x2_nonfinite(unsigned packed) { return ((packed & 0x7C007C00u) + 0x04000400u) & 0x80008000u; }
 __device__ __forceinline__ bool nonfinite(float v) { return (__float_as_uint(v) & 0x7F800000u) == 0x7F800000u; }
+
+// -------- int8 KV cache (kv_dtype 2): a layer's buffer is [B, H, Lmax, 64] int8 codes followed by [B, H, Lmax] fp32 row scales (68 B H Lmax bytes; the scale plane
+// starts at byte 64 B H Lmax).  Quantiser of one 64-element row (one head's k or v of one token), IEEE fp32 throughout so that torch on the CPU gives the same bytes:
+// amax = max |r_i|; amax < 1e-30 -> codes 0, scale 0; else scale = amax / 127, code_i = clamp(rint(r_i * (127 / amax)), -127, 127) (nearest even); value = code_i * scale.
+constexpr long kKvI8RowBytes = 68;   // 64 codes + one fp32 scale per cached row
+// called by all 64 lanes of a wave, lane = element of the row: the row's scale (every lane) and this lane's code; `bad` is set (every lane) when the row holds a NaN / inf
+__device__ __forceinline__ int kv_i8_quant(float v, float& scale, bool& bad) {
+    float amax = fabsf(v);
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) amax = fmaxf(amax, __shfl_xor(amax, o, 64));
+    bad = __builtin_amdgcn_ballot_w64(nonfinite(v)) != 0ull;
+    if (!(amax >= 1e-30f)) { scale = 0.f; return 0; }
+    scale = __fdiv_rn(amax, 127.f);
+    const float inv = __fdiv_rn(127.f, amax);
+    return (int)fminf(fmaxf(rintf(__fmul_rn(v, inv)), -127.f), 127.f);
+}
+// store the row: four codes per dword (lanes 4 j .. 4 j + 3 -> dword j of the 64-byte row), the scale by lane 0.  `sc_off`: bytes from `cache` to the scale of its row 0
+__device__ __forceinline__ void kv_i8_store_row(void* cache, long sc_off, long row, int lane, int code, float scale) {
+    unsigned w = ((unsigned)code & 0xFFu) << (8 * (lane & 3));
+    w |= (unsigned)__shfl_xor((int)w, 1, 64);
+    w |= (unsigned)__shfl_xor((int)w, 2, 64);
+    if ((lane & 3) == 0) reinterpret_cast<unsigned*>(reinterpret_cast<char*>(cache) + row * 64)[lane >> 2] = w;
+    if (lane == 0) reinterpret_cast<float*>(reinterpret_cast<char*>(cache) + sc_off)[row] = scale;
+}
 
 // -------- split precision: v = hi + lo * 2^-11 with hi, lo in f16 (gemm_split.hip); interleaved plane layout [row][k/32][hi 32 | lo 32]
 __device__ __forceinline__ _Float16 split_hi(float v) { return (_Float16)v; }

@@ -85,6 +85,7 @@ void Ctx::check_status(const char* when) {
              "5-bit exponent where the reference's bf16 / fp32 arithmetic has 8 (precision='f16x1', Route M's single-product mode, has the same operand range).  Run this checkpoint with "
              "precision='fp32' (and kv_cache='f32'); the VQGAN (decoder and encoder) alone "
              "also with precision='f16x3r', which rescales its un-normalised activations instead of refusing them.";
+    if (e & BG_ST_KV_NONFINITE) m += "  A key / value row written into the int8 KV cache (kv_cache='i8') held a NaN / inf.";
     if (e & BG_ST_NONFINITE_PIXELS) m += "  The VQGAN decoder produced a NaN / inf pixel.";
     if (e & BG_ST_NONFINITE_LATENTS)
         m += "  The VQGAN quantizer met a latent row without a finite distance to any codebook entry (NaN / inf in the input image, or an overflow inside the encoder): "
@@ -96,7 +97,7 @@ void Ctx::check_status(const char* when) {
         mlpf_disabled = true;
         if (graph_exec) { retire_graph(graph_exec, graph); graph_exec = nullptr; graph = nullptr; }   // the captured step contains the fused launch
     }
-    fail((e & (BG_ST_NONFINITE_LOGITS | BG_ST_F16_RANGE | BG_ST_NONFINITE_PIXELS | BG_ST_NONFINITE_LATENTS)) ? BEVGEN_ERR_NUMERIC : BEVGEN_ERR_INTERNAL, "%s", m.c_str());
+    fail((e & (BG_ST_NONFINITE_LOGITS | BG_ST_F16_RANGE | BG_ST_NONFINITE_PIXELS | BG_ST_NONFINITE_LATENTS | BG_ST_KV_NONFINITE)) ? BEVGEN_ERR_NUMERIC : BEVGEN_ERR_INTERNAL, "%s", m.c_str());
 }
 const DevTensor* Ctx::find(const std::string& name) const {
     auto it = params.find(name);

@@ -65,6 +65,7 @@ void launch_rowsrc_materialize(const RowSrc& r0, float* out, int M, int D, int* 
 
 // ----------------------------------------------------------------------------------------------------------------- helpers
 typedef _Float16 half8_t __attribute__((ext_vector_type(8)));
+typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 // K / V rows are read with the NON-TEMPORAL hint (registers and LDS-DMA alike): a decode step streams ~85 MB of them per layer through 8 x 4 MB of L2 exactly once, and
 // without the hint that stream evicts what the step does reuse - the head's q/k/v weight rows its 16 workgroups share, and the weight images the MLP launches park in L2
 // for each other.  Same-box A/B, fp16 cache + fp16 weights: 0.996-0.999 -> 0.959-0.964 ms/step (profiles/r04_ab_kv_nontemporal.txt).
@@ -84,6 +85,15 @@ template <> struct KvRow<1> {  // fp16 rows: 128 B = 8 lanes x 16 B; kept packed
         return __builtin_nontemporal_load(reinterpret_cast<const half8_t*>(reinterpret_cast<const _Float16*>(base) + row * 64 + sub * 8));
     }
     __device__ static __forceinline__ float get(const Raw& r, int i) { return (float)r[i]; }
+};
+template <> struct KvRow<2> {  // int8 rows: 64 B of codes = 8 lanes x 8 B (LPK and DPL of the fp16 rows: the walk, the merges and the register budget carry over; 512 B per
+    static constexpr int LPK = 8, DPL = 8;   // load instruction); the row's fp32 scale is a load of its own (Attend::Buf) and multiplies the score / the probability
+    typedef uint2 Raw;
+    __device__ static __forceinline__ Raw load(const void* base, long row, int sub) {
+        const u32x2 v = __builtin_nontemporal_load(reinterpret_cast<const u32x2*>(reinterpret_cast<const char*>(base) + row * 64 + sub * 8));
+        return make_uint2(v[0], v[1]);
+    }
+    __device__ static __forceinline__ float get(const Raw& r, int i) { return (float)(int)(signed char)((i < 4 ? r.x : r.y) >> (8 * (i & 3))); }
 };
 
 // sum over aligned groups of 8 / 16 lanes with DPP row operations (every lane of the group ends with the group's sum)
@@ -125,19 +135,23 @@ template <int DT, int NQ, int U>
 struct Attend {
     using T = KvRow<DT>;
     static constexpr int LPK = T::LPK, DPL = T::DPL;
-    struct Buf { typename T::Raw k[U], v[U]; };
+    struct Buf { typename T::Raw k[U], v[U]; float ks[U], vs[U]; };   // ks / vs: the rows' scales (int8 cache only; never touched otherwise)
 
     // A wave walks 16-key chunks.  KPS keys per pipeline step (U loads of KPI consecutive keys = 1 KiB each), SPC steps per chunk.
     static constexpr int KPI = 64 / LPK, KPS = U * KPI, SPC = 16 / KPS;
     static_assert(KPS <= 16 && 16 % KPS == 0, "a pipeline step must tile a 16-key chunk");
 
     template <int USTRIDE>
-    __device__ static __forceinline__ void load(Buf& b, const void* kc, const void* vc, long row0, int key0, int k_end, int sub) {
+    __device__ static __forceinline__ void load(Buf& b, const void* kc, const void* vc, long row0, int key0, int k_end, int sub, long sc_off = 0) {
 #pragma unroll
         for (int u = 0; u < U; ++u) {
             const int kcl = min(key0 + u * USTRIDE, k_end - 1);   // clamped address, masked in compute()
             b.k[u] = T::load(kc, row0 + kcl, sub);
             b.v[u] = T::load(vc, row0 + kcl, sub);
+            if constexpr (DT == 2) {   // (the 8 lanes of a key read one address: one 4-byte request per key)
+                b.ks[u] = __builtin_nontemporal_load(reinterpret_cast<const float*>(reinterpret_cast<const char*>(kc) + sc_off) + row0 + kcl);
+                b.vs[u] = __builtin_nontemporal_load(reinterpret_cast<const float*>(reinterpret_cast<const char*>(vc) + sc_off) + row0 + kcl);
+            }
         }
     }
     template <int USTRIDE>
@@ -154,6 +168,7 @@ struct Attend {
 #pragma unroll
                 for (int i = 0; i < DPL; ++i) d = fmaf(q[qi][i], T::get(b.k[u], i), d);
                 d = lane_group_sum<LPK>(d);
+                if constexpr (DT == 2) d *= b.ks[u];   // the key row's scale, once per score
                 sc[qi][u] = bv <= kNegBig ? kNegBig : d + bv;
             }
         }
@@ -170,8 +185,10 @@ struct Attend {
             for (int u = 0; u < U; ++u) {
                 const float p = sc[qi][u] <= kNegBig ? 0.f : __builtin_amdgcn_exp2f(sc[qi][u] - mx);
                 l[qi] += p;
+                float pv = p;
+                if constexpr (DT == 2) pv = p * b.vs[u];   // the value row's scale rides on the probability: the accumulator only, not l
 #pragma unroll
-                for (int i = 0; i < DPL; ++i) acc[qi][i] = fmaf(p, T::get(b.v[u], i), acc[qi][i]);
+                for (int i = 0; i < DPL; ++i) acc[qi][i] = fmaf(pv, T::get(b.v[u], i), acc[qi][i]);
             }
             m[qi] = mx;
         }
@@ -186,7 +203,7 @@ struct Attend {
     // address arithmetic of the eight loads per step cost 1.8 us of the 27 us K/V phase)
     template <bool LIST, int NSLOTS>
     __device__ static __forceinline__ void run_as(const void* kc, const void* vc, long row0, const uint16_t* list_s, int lo, int hi, int slot, int kslot, int k_end,
-                                                  int sub, const float* bias_s, const float (&q)[NQ][DPL], float (&m)[NQ], float (&l)[NQ], float (&acc)[NQ][DPL]) {
+                                                  int sub, const float* bias_s, const float (&q)[NQ][DPL], float (&m)[NQ], float (&l)[NQ], float (&acc)[NQ][DPL], long sc_off = 0) {
         constexpr int USTRIDE = LIST ? KPI : NSLOTS * KPI, SPAN = U * NSLOTS * KPI;
         int steps;
         if (LIST) {
@@ -202,11 +219,11 @@ struct Attend {
             return 16 * lo + j * SPAN + slot * KPI + kslot;
         };
         Buf b0, b1;
-        load<USTRIDE>(b0, kc, vc, row0, key_of(0), k_end, sub);
+        load<USTRIDE>(b0, kc, vc, row0, key_of(0), k_end, sub, sc_off);
         for (int j = 0; j < steps; j += 2) {
-            if (j + 1 < steps) load<USTRIDE>(b1, kc, vc, row0, key_of(j + 1), k_end, sub);
+            if (j + 1 < steps) load<USTRIDE>(b1, kc, vc, row0, key_of(j + 1), k_end, sub, sc_off);
             compute<USTRIDE>(b0, key_of(j), k_end, bias_s, q, m, l, acc);
-            if (j + 2 < steps) load<USTRIDE>(b0, kc, vc, row0, key_of(j + 2), k_end, sub);
+            if (j + 2 < steps) load<USTRIDE>(b0, kc, vc, row0, key_of(j + 2), k_end, sub, sc_off);
             if (j + 1 < steps) compute<USTRIDE>(b1, key_of(j + 1), k_end, bias_s, q, m, l, acc);
         }
     }
@@ -222,6 +239,7 @@ struct Attend {
                                                       const float (&q)[NQ][DPL], float (&m)[NQ], float (&l)[NQ], float (&acc)[NQ][DPL], const uint16_t* list_s = nullptr,
                                                       int hi = 0) {
         static_assert(!LIST || SPC == 1, "the staged chunk-list walk takes one chunk per pipeline step");
+        static_assert(DT != 2 || NSLOTS < 0, "int8 rows are not staged: a step's pieces are 512 B and its scales a load of their own (the vmcnt bookkeeping below counts two loads per key)");
         constexpr int USTRIDE = LIST ? KPI : NSLOTS * KPI, SPAN = U * NSLOTS * KPI;
         int steps;
         if (LIST) steps = hi - slot > 0 ? (hi - slot + NSLOTS - 1) / NSLOTS : 0;
@@ -311,7 +329,13 @@ __device__ __forceinline__ void af_append_attend_store(const ArAttnFusedArgs& a,
         void* cache = is_v ? a.vcache : a.kcache;
         const long idx = ((((long)(b0 + g)) * a.H + head) * a.Lmax + row) * 64 + d;
         if (DT == 0) reinterpret_cast<float*>(cache)[idx] = val;
-        else {
+        else if (DT == 2) {   // one wave = one (sequence, k | v) row: wave max, packed codes + scale
+            float sc;
+            bool bad;
+            const int code = kv_i8_quant(val, sc, bad);
+            kv_i8_store_row(cache, a.sc_off, (((long)(b0 + g)) * a.H + head) * a.Lmax + row, d, code, sc);
+            if (bad && d == 0) status_raise(a.status, BG_ST_KV_NONFINITE);
+        } else {
             const _Float16 hv = (_Float16)val;
             unsigned bad = 0;
             guard_half(hv, bad);   // a key / value outside the fp16 range of the cache (or NaN)
@@ -334,8 +358,8 @@ __device__ __forceinline__ void af_append_attend_store(const ArAttnFusedArgs& a,
         const int p_lo = (int)((long)kz * n_pos / ksl), p_hi = (int)((long)(kz + 1) * n_pos / ksl);
         // (the dense walk strides over whole 256-key spans: its end must be clipped to this share's last key, or the next share's keys are counted twice)
         const int k_hi = SP ? n_old : min(n_old, 16 * p_hi);
-        if constexpr (STG) Attend<DT, 1, U>::template run_staged<NW, SP>(a.kcache, a.vcache, row0, wave, kslot, k_hi, sub, bias_s, st, js, q, m, l, acc, walk, p_hi);
-        else Attend<DT, 1, U>::template run_as<SP, NW>(a.kcache, a.vcache, row0, walk, p_lo, p_hi, wave, kslot, k_hi, sub, bias_s, q, m, l, acc);
+        if constexpr (STG && DT != 2) Attend<DT, 1, U>::template run_staged<NW, SP>(a.kcache, a.vcache, row0, wave, kslot, k_hi, sub, bias_s, st, js, q, m, l, acc, walk, p_hi);
+        else Attend<DT, 1, U>::template run_as<SP, NW>(a.kcache, a.vcache, row0, walk, p_lo, p_hi, wave, kslot, k_hi, sub, bias_s, q, m, l, acc, a.sc_off);
         wave_merge<LPK, DPL>(m[0], l[0], acc[0]);
         if (kslot == 0) {
             if (sub == 0) { my_red[0] = m[0]; my_red[1] = l[0]; }
@@ -353,7 +377,7 @@ __device__ __forceinline__ void af_append_attend_store(const ArAttnFusedArgs& a,
                 for (int i = 0; i < DPL; ++i) { q[g][i] = qkv_s[g * 192 + sub * DPL + i] * sl2; acc[g][i] = 0.f; }
             }
             const long row0 = ((long)b0 * a.H + head) * a.Lmax;
-            Attend<DT, G, UP>::template run_as<SP, NW>(a.kcache, a.vcache, row0, walk, 0, p_pos, wave, kslot, min(a.prefix, n_old), sub, bias_s, q, m, l, acc);
+            Attend<DT, G, UP>::template run_as<SP, NW>(a.kcache, a.vcache, row0, walk, 0, p_pos, wave, kslot, min(a.prefix, n_old), sub, bias_s, q, m, l, acc, a.sc_off);
 #pragma unroll
             for (int g = 0; g < G; ++g) {
                 wave_merge<LPK, DPL>(m[g], l[g], acc[g]);
@@ -371,7 +395,7 @@ __device__ __forceinline__ void af_append_attend_store(const ArAttnFusedArgs& a,
 #pragma unroll
             for (int i = 0; i < DPL; ++i) { q[0][i] = qkv_s[g_own * 192 + sub * DPL + i] * sl2; acc[0][i] = 0.f; }
             const long row0 = ((long)(b0 + g_own) * a.H + head) * a.Lmax;
-            Attend<DT, 1, U>::template run_as<SP, TW>(a.kcache, a.vcache, row0, walk, p_pos, n_pos, wt, kslot, n_old, sub, bias_s, q, m, l, acc);
+            Attend<DT, 1, U>::template run_as<SP, TW>(a.kcache, a.vcache, row0, walk, p_pos, n_pos, wt, kslot, n_old, sub, bias_s, q, m, l, acc, a.sc_off);
             wave_merge<LPK, DPL>(m[0], l[0], acc[0]);
             if (kslot == 0) {
                 if (sub == 0) { my_red[G * 66] = m[0]; my_red[G * 66 + 1] = l[0]; }
@@ -413,6 +437,12 @@ __device__ __forceinline__ void af_append_attend_store(const ArAttnFusedArgs& a,
         if (blockIdx.z + 1 == gridDim.z) {   // the new key (row n-1), from LDS: wave g = sequence g, lane d = dim d
             float kn = qkv_s[g * 192 + 64 + d], vn = qkv_s[g * 192 + 128 + d];
             if (DT == 1) { kn = (float)(_Float16)kn; vn = (float)(_Float16)vn; }
+            if (DT == 2) {   // dequantised from its own codes (this wave holds the whole row), exactly as the next step reads it
+                float sk, sv;
+                bool bad;
+                const int ck = kv_i8_quant(kn, sk, bad), cv = kv_i8_quant(vn, sv, bad);
+                kn = (float)ck * sk; vn = (float)cv * sv;
+            }
             const float bv = bias_s[row];
             const float sn = wave_sum_dpp(qkv_s[g * 192 + d] * sl2 * kn) + bv;
             if (bv > kNegBig) {
@@ -483,9 +513,9 @@ __global__ __launch_bounds__(1024) void ar_attn_fused_kernel(ArAttnFusedArgs a) 
     // pipeline steps of ITS OWN share of the key walk - U K pieces + U V pieces of 1 KiB per step - by LDS-DMA into its region behind the sink, and the walk reads them
     // from there (Attend::run_staged).  HBM has nothing else to do for the 13 us of the prologue; the 128 KB the CU's 160 KB of LDS leave free are 40 % of a
     // (sequence, head)'s fp16 K/V rows at the mean context of a decode.
-    constexpr bool STG = G == 1;
+    constexpr bool STG = G == 1 && DT != 2;   // (int8 rows: no staged opening, see Attend::run_staged)
     using TS = KvRow<DT>;
-    constexpr int KPI = 64 / TS::LPK, PIECE = NW * KPI, SU = WalkU<DT, G>::value, ROWB = 64 * (DT ? 2 : 4);
+    constexpr int KPI = 64 / TS::LPK, PIECE = NW * KPI, SU = WalkU<DT, G>::value, ROWB = DT == 2 ? 64 : 64 * (DT ? 2 : 4);
     const int wave_u = __builtin_amdgcn_readfirstlane(wave);
     const char* st_w = stage + (wave_u * a.stage_cap) * 1024;   // this wave's region
     // staged steps of this wave.  Dense walk: whole pipeline steps of rows that are in the cache at kernel start.  Chunk-list walk (SP): its leading list positions
@@ -863,7 +893,9 @@ void launch_ar_attn_fused(const ArAttnFusedArgs& a0, hipStream_t s) {
     BG_REQUIRE(lds <= 64 * 1024, "fused decode attention: %zu bytes of LDS needed (sequence length %d too long)", lds, a.Lmax);
     // K/V staging (fused kernel, G = 1, dense walk): what the CU's LDS has left beyond the kernel's own 24 KB, in whole pipeline steps per wave (gfx950: 160 KB per
     // workgroup -> 8 pieces per wave = 128 KB).  $BEVGEN_KV_STAGE overrides the launcher's choice (A/B switch; 0 = off)
-    if (!pre && a.G == 1) {
+    BG_REQUIRE(a.kv_dtype >= 0 && a.kv_dtype <= 2, "fused decode attention: kv_dtype %d", a.kv_dtype);
+    if (!a.sc_off) a.sc_off = 64L * a.B * a.H * a.Lmax;
+    if (!pre && a.G == 1 && a.kv_dtype != 2) {
         static const int env_cap = getenv("BEVGEN_KV_STAGE") ? atoi(getenv("BEVGEN_KV_STAGE")) : -1;
         const int step_pieces = 2 * (a.kv_dtype == 0 ? 4 : 2);   // K + V pieces of one pipeline step (WalkU)
         const int room = (int)((ar_attn_fused_max_lds() - 1024 - lds) / (AF_WAVES * 1024));   // (1 KiB kept back: the block-sparse variants hold 256 B of static LDS)
@@ -878,7 +910,7 @@ void launch_ar_attn_fused(const ArAttnFusedArgs& a0, hipStream_t s) {
     dim3 grid(a.H, a.B / a.G, a.ksplit);
     // algorithmic bytes of one launch: K and V rows of the context, once each; the shared prefix once per group
     const double n_host = a.d_n ? a.n + a.n_hint : a.n;
-    const double eb = a.kv_dtype == 0 ? 4 : 2;
+    const double eb = a.kv_dtype == 0 ? 4 : a.kv_dtype == 1 ? 2 : kKvI8RowBytes / 64.0;
     const double pfx = a.G > 1 ? (double)a.prefix : 0.0;
     // SP instantiations only when a layout hides something (density < 1): chunk lists are then always present (context.cpp / the operator entry build both)
     const bool sp = a.vis.has_chunks;
@@ -898,14 +930,14 @@ void launch_ar_attn_fused(const ArAttnFusedArgs& a0, hipStream_t s) {
                            else hipLaunchKernelGGL(K, grid, dim3(1024), lds, s, a); } while (0)
 #define AP_LAUNCH(DT, GG) do { if (sp) AP_LAUNCH1((ar_attn_kernel<DT, GG, true>)); else AP_LAUNCH1((ar_attn_kernel<DT, GG, false>)); } while (0)
 #define AP_LAUNCH_G(DT) do { if (a.G == 1) AP_LAUNCH(DT, 1); else if (a.G == 2) AP_LAUNCH(DT, 2); else AP_LAUNCH(DT, 4); } while (0)
-        if (a.kv_dtype == 0) AP_LAUNCH_G(0); else AP_LAUNCH_G(1);
+        if (a.kv_dtype == 0) AP_LAUNCH_G(0); else if (a.kv_dtype == 1) AP_LAUNCH_G(1); else AP_LAUNCH_G(2);
 #undef AP_LAUNCH_G
 #undef AP_LAUNCH
 #undef AP_LAUNCH1
     } else if (a.wqkv_h) {
-        if (a.kv_dtype == 0) AF_LAUNCH_G(0, 1); else AF_LAUNCH_G(1, 1);
+        if (a.kv_dtype == 0) AF_LAUNCH_G(0, 1); else if (a.kv_dtype == 1) AF_LAUNCH_G(1, 1); else AF_LAUNCH_G(2, 1);
     } else {
-        if (a.kv_dtype == 0) AF_LAUNCH_G(0, 0); else AF_LAUNCH_G(1, 0);
+        if (a.kv_dtype == 0) AF_LAUNCH_G(0, 0); else if (a.kv_dtype == 1) AF_LAUNCH_G(1, 0); else AF_LAUNCH_G(2, 0);
     }
 #undef AF_LAUNCH_G
 #undef AF_LAUNCH

@@ -173,7 +173,7 @@ __device__ __forceinline__ void cache_store(void* cache, int kv_dtype, long idx,
 }
 
 __global__ __launch_bounds__(256) void ar_qkv_scatter_kernel(const float* __restrict__ qkv, float* __restrict__ Q, void* kcache, void* vcache, int kv_dtype,
-                                                             int H, int n, int pos0, const int* __restrict__ d_pos, int Lmax, long total, unsigned* __restrict__ status) {
+                                                             int H, int n, int pos0, const int* __restrict__ d_pos, int Lmax, long total, unsigned* __restrict__ status, long sc_off) {
     const int lane = threadIdx.x & 63;
     const long w = (long)blockIdx.x * 4 + (threadIdx.x >> 6);  // (b*n + i)*H + h
     if (w >= total) return;
@@ -184,6 +184,16 @@ __global__ __launch_bounds__(256) void ar_qkv_scatter_kernel(const float* __rest
     const float* src = qkv + bi * (3L * H * 64) + h * 64 + lane;
     const int pos = (d_pos ? *d_pos : 0) + pos0 + i;
     if (Q) Q[((b * H + h) * n + i) * 64 + lane] = src[0];
+    if (kv_dtype == 2) {   // int8 rows: the wave holds one k and one v row - row amax by a wave reduction, packed codes + scale (common.h kv_i8_*)
+        const long r = (b * H + h) * Lmax + pos;
+        float sk, sv;
+        bool bk, bv;
+        const int ck = kv_i8_quant(src[H * 64], sk, bk), cv = kv_i8_quant(src[2 * H * 64], sv, bv);
+        kv_i8_store_row(kcache, sc_off, r, lane, ck, sk);
+        kv_i8_store_row(vcache, sc_off, r, lane, cv, sv);
+        if ((bk || bv) && lane == 0) status_raise(status, BG_ST_KV_NONFINITE);
+        return;
+    }
     const long dst = ((b * H + h) * Lmax + pos) * 64 + lane;
     unsigned bad = 0;
     cache_store(kcache, kv_dtype, dst, src[H * 64], bad);
@@ -191,15 +201,18 @@ __global__ __launch_bounds__(256) void ar_qkv_scatter_kernel(const float* __rest
     if (bad) status_raise(status, BG_ST_F16_RANGE);
 }
 
-void launch_ar_qkv_scatter(const float* qkv, float* Q, void* kcache, void* vcache, int kv_dtype, int B, int H, int n, int pos0, int Lmax, hipStream_t s) {
+// sc_off (int8 cache): bytes from kcache / vcache to the scale of their row 0; 0 = the pointers are the layer's base and B its slots (64 B H Lmax)
+void launch_ar_qkv_scatter(const float* qkv, float* Q, void* kcache, void* vcache, int kv_dtype, int B, int H, int n, int pos0, int Lmax, hipStream_t s, long sc_off) {
+    if (!sc_off) sc_off = 64L * B * H * Lmax;
     const long total = (long)B * n * H;
-    hipLaunchKernelGGL(ar_qkv_scatter_kernel, dim3((int)((total + 3) / 4)), dim3(256), 0, s, qkv, Q, kcache, vcache, kv_dtype, H, n, pos0, (const int*)nullptr, Lmax, total, status_current());
+    hipLaunchKernelGGL(ar_qkv_scatter_kernel, dim3((int)((total + 3) / 4)), dim3(256), 0, s, qkv, Q, kcache, vcache, kv_dtype, H, n, pos0, (const int*)nullptr, Lmax, total, status_current(), sc_off);
     LAUNCH_CHECK();
 }
 
-void launch_ar_kv_append(const float* qkv, void* kcache, void* vcache, int kv_dtype, int B, int H, int pos0, const int* d_pos, int Lmax, hipStream_t s) {
+void launch_ar_kv_append(const float* qkv, void* kcache, void* vcache, int kv_dtype, int B, int H, int pos0, const int* d_pos, int Lmax, hipStream_t s, long sc_off) {
+    if (!sc_off) sc_off = 64L * B * H * Lmax;
     const long total = (long)B * H;
-    hipLaunchKernelGGL(ar_qkv_scatter_kernel, dim3((int)((total + 3) / 4)), dim3(256), 0, s, qkv, (float*)nullptr, kcache, vcache, kv_dtype, H, 1, pos0, d_pos, Lmax, total, status_current());
+    hipLaunchKernelGGL(ar_qkv_scatter_kernel, dim3((int)((total + 3) / 4)), dim3(256), 0, s, qkv, (float*)nullptr, kcache, vcache, kv_dtype, H, 1, pos0, d_pos, Lmax, total, status_current(), sc_off);
     LAUNCH_CHECK();
 }
 

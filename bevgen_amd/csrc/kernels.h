@@ -255,10 +255,11 @@ struct DecodeAttnArgs {
     int n_hint = 0;                  // host's copy of *d_n (profiling only)
     int Lmax = 0;
     float scale = 1.f;               // dh^-0.5, applied to (q.k + bias)
-    int kv_dtype = 0;                // 0 = fp32, 1 = fp16 storage (fp32 accumulate)
+    int kv_dtype = 0;                // 0 = fp32, 1 = fp16 storage (fp32 accumulate), 2 = int8 codes + fp32 row scales (common.h kv_i8_*)
     int shared_prefix = 0;           // reserved: leading keys shared by groups of `group` consecutive sequences
     int group = 1;
     unsigned* status = nullptr;      // the context's device status word, filled in by the launcher
+    long sc_off = 0;                 // int8 cache: bytes from kcache / vcache to the scale of their row 0; 0 = 64 B H Lmax (the pointers are the layer's base)
 };
 size_t decode_attention_ws_bytes(int B, int H, int S);
 void launch_decode_attention_ws(const DecodeAttnArgs& a, float* ws, int S, hipStream_t s);
@@ -286,7 +287,7 @@ struct ArAttnFusedArgs {
     const float *ln_cs = nullptr, *ln_ds = nullptr;   // [3D] each: W gamma and W beta + b of the fused matrix (launch_ar_ln_fold): the fused kernel folds ln1 into its projection
     void* kcache = nullptr;            // this layer's [B, H, Lmax, 64]
     void* vcache = nullptr;
-    int kv_dtype = 0;                  // 0 fp32, 1 fp16 storage
+    int kv_dtype = 0;                  // 0 fp32, 1 fp16 storage, 2 int8 codes + fp32 row scales (common.h kv_i8_*)
     const float* bias = nullptr; int ldbias = 0;                               // camera-bias matrix [L, ldbias] (unscaled) or null
     SparseVis vis;                     // visibility of the keys (element mask x block layout) + the chunk lists the key walk follows
     float* out = nullptr; int ldo = 0; // x2 [B, D] = ln1(x) + attention
@@ -306,6 +307,7 @@ struct ArAttnFusedArgs {
     int stage_cap = -1;
     int has_bias = 0;                  // filled in by the launcher
     unsigned* status = nullptr;        // the context's device status word, filled in by the launcher (fp16 cache: a key / value outside the fp16 range raises BG_ST_F16_RANGE)
+    long sc_off = 0;                   // int8 cache: bytes from kcache / vcache to the scale of their row 0; 0 = 64 B H Lmax (the pointers are the layer's base)
 };
 // per-row constants of LayerNorm folded into a projection: cs[j] = sum_k W[j][k] gamma[k], ds[j] = sum_k W[j][k] beta[k] + b[j]   (W [N, K] row-major; fp64 accumulation)
 void launch_ar_ln_fold(const float* W, const float* b, const float* gamma, const float* beta, float* cs, float* ds, int N, int K, hipStream_t s);
@@ -379,9 +381,9 @@ void launch_muse_kv_prep(const float* kvraw, const float* null_kv /*[2,H,1,64]*/
                          int B, int H, int Nk, int Nk_pad, hipStream_t s);
 // Route A: split fused qkv rows [rows, 3*H*64] (q|k|v) -> Q [B,H,n,64] (optional) and cache rows [B,H,Lmax,64] at position pos0..pos0+n
 void launch_ar_qkv_scatter(const float* qkv, float* Q /*[B,H,n,64] or null*/, void* kcache, void* vcache, int kv_dtype,
-                           int B, int H, int n, int pos0, int Lmax, hipStream_t s);
+                           int B, int H, int n, int pos0, int Lmax, hipStream_t s, long sc_off = 0 /* int8 cache: bytes from the cache pointers to their scale plane; 0 = 64 B H Lmax */);
 // Route A decode: pos0 read from a device counter (graph-replayable)
-void launch_ar_kv_append(const float* qkv, void* kcache, void* vcache, int kv_dtype, int B, int H, int pos0, const int* d_pos, int Lmax, hipStream_t s);
+void launch_ar_kv_append(const float* qkv, void* kcache, void* vcache, int kv_dtype, int B, int H, int pos0, const int* d_pos, int Lmax, hipStream_t s, long sc_off = 0);
 
 // ---------------------------------------------------------------- sampler.hip
 // MaskGit re-masking (muse_net:569-574): the n_mask highest scores of each row (ties: lower index first) get mask_id; init ids re-imposed

@@ -184,7 +184,32 @@ __global__ void replicate_prefix_kernel(char* __restrict__ kc, char* __restrict_
         }
     }
 }
+// int8 cache (elem_bytes 1): a layer is [B][H][L][64] codes followed by [B][H][L] fp32 row scales - both planes of the rows are copied
+__global__ void replicate_prefix_i8_kernel(char* __restrict__ kc, char* __restrict__ vc, int B, int H, int L, int rows, int src, int dst0, int count) {
+    const int layer = blockIdx.z, h = blockIdx.y;
+    const long layer_b = (long)layer * B * H * L * kKvI8RowBytes;
+    const long codes = layer_b + (long)h * L * 64, slot_c = (long)H * L * 64;          // + slot * slot_c
+    const long scales = layer_b + (long)B * H * L * 64 + (long)h * L * 4, slot_s = (long)H * L * 4;
+    const long n16 = (long)rows * 4;   // 16-byte pieces of the code rows
+    for (int j = 0; j < count; ++j) {
+        const int d = dst0 + j;
+        if (d == src) continue;
+        for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n16; i += (long)gridDim.x * blockDim.x) {
+            reinterpret_cast<uint4*>(kc + codes + d * slot_c)[i] = reinterpret_cast<const uint4*>(kc + codes + src * slot_c)[i];
+            reinterpret_cast<uint4*>(vc + codes + d * slot_c)[i] = reinterpret_cast<const uint4*>(vc + codes + src * slot_c)[i];
+        }
+        for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < rows; i += (long)gridDim.x * blockDim.x) {
+            reinterpret_cast<float*>(kc + scales + d * slot_s)[i] = reinterpret_cast<const float*>(kc + scales + src * slot_s)[i];
+            reinterpret_cast<float*>(vc + scales + d * slot_s)[i] = reinterpret_cast<const float*>(vc + scales + src * slot_s)[i];
+        }
+    }
+}
 void launch_replicate_prefix(void* kc, void* vc, int layers, int B, int H, int L, int rows, int src, int dst0, int count, int elem_bytes, hipStream_t s) {
+    if (elem_bytes == 1) {
+        hipLaunchKernelGGL(replicate_prefix_i8_kernel, dim3(8, H, layers), dim3(256), 0, s, reinterpret_cast<char*>(kc), reinterpret_cast<char*>(vc), B, H, L, rows, src, dst0, count);
+        LAUNCH_CHECK();
+        return;
+    }
     hipLaunchKernelGGL(replicate_prefix_kernel, dim3(8, H, layers), dim3(256), 0, s, reinterpret_cast<char*>(kc), reinterpret_cast<char*>(vc), B, H, L, rows, src, dst0, count,
                        elem_bytes);
     LAUNCH_CHECK();

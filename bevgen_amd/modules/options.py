@@ -14,7 +14,8 @@ option is: a key next to the ``_target_`` (``+model.transformer.kv_cache=f16`` o
                                                                             per call (the reference's bf16 autocast: 8), tokens are no longer those of the fp32 model -
                                                                             the VQGAN and Route A treat it exactly as f16x3)
     weights         $BEVGEN_WEIGHTS          f32 | f16              f32     (f16: GEMM / conv matrices rounded once at load, two MFMAs per product)
-    kv_cache        $BEVGEN_KV_CACHE         f32 | f16              f32     (Route A; f16 = fp16 storage / fp32 accumulate: BASELINE config 4)
+    kv_cache        $BEVGEN_KV_CACHE         f32 | f16 | i8         f32     (Route A; f16 = fp16 storage / fp32 accumulate: BASELINE config 4; i8 = opt-in, lossy: int8
+                                                                            codes + one fp32 scale per (token, head) row, fp32 accumulate)
     decode_weights  $BEVGEN_DECODE_WEIGHTS   f32 | f16              f32     (Route A decode step streams 2-byte q/k/v, MLP and head weights)
     decode_path     $BEVGEN_DECODE_PATH      auto | fused | split | per_op   auto
 
@@ -29,7 +30,7 @@ from typing import Dict, Mapping, MutableMapping, Optional
 CHOICES = {
     "precision": ("fp32", "f16x3", "f16x3r", "f16x1"),
     "weights": ("f32", "f16"),
-    "kv_cache": ("f32", "f16"),
+    "kv_cache": ("f32", "f16", "i8"),
     "decode_weights": ("f32", "f16"),
     "decode_path": ("auto", "fused", "split", "per_op"),
 }

@@ -69,7 +69,7 @@ class Context:
         kv_cache = kv_cache or os.environ.get("BEVGEN_KV_CACHE") or "f32"
         decode_path = decode_path or os.environ.get("BEVGEN_DECODE_PATH") or "auto"
         decode_weights = decode_weights or os.environ.get("BEVGEN_DECODE_WEIGHTS") or "f32"
-        for key, val, ok in (("kv_cache", kv_cache, ("f32", "f16")), ("decode_path", decode_path, ("auto", "fused", "split", "per_op")),
+        for key, val, ok in (("kv_cache", kv_cache, ("f32", "f16", "i8")), ("decode_path", decode_path, ("auto", "fused", "split", "per_op")),
                              ("decode_weights", decode_weights, ("f32", "f16"))):
             if val not in ok:
                 raise ValueError(f"{key} must be one of {ok}, got {val!r}")
@@ -83,8 +83,9 @@ class Context:
         c.precision = {"fp32": _lib.PRECISION_FP32, "f16x3": _lib.PRECISION_F16X3, "f16x3r": _lib.PRECISION_F16X3, "f16x1": _lib.PRECISION_F16X1}[precision]
         c.vq_range = 1 if precision == "f16x3r" else 0
         c.max_batch = max_batch
-        # Route A KV-cache storage: 'f32' (bit-exact tokens) or 'f16' (fp16 storage / fp32 accumulate, BASELINE config 4: half the decode traffic)
-        c.kv_cache_dtype = {"f32": _lib.KV_F32, "f16": _lib.KV_F16}[kv_cache]
+        # Route A KV-cache storage: 'f32' (bit-exact tokens), 'f16' (fp16 storage / fp32 accumulate, BASELINE config 4: half the decode traffic) or 'i8' (opt-in, lossy:
+        # int8 codes + one fp32 scale per (token, head) row, 68 bytes per row; BEVGEN_KV_I8 in bevgen_hip.h)
+        c.kv_cache_dtype = {"f32": _lib.KV_F32, "f16": _lib.KV_F16, "i8": _lib.KV_I8}[kv_cache]
         self.kv_cache = kv_cache
         # Route A decode step: 'auto' (default: 'split' for one or two sequences per call, else 'fused'), 'fused' (three launches per layer), 'split' (LayerNorm + QKV projection kernel, then the attention-only kernel: four launches)
         # or 'per_op' (one kernel per operator, the A/B reference)
@@ -145,7 +146,7 @@ class Context:
             self.lib.bevgen_destroy(self._h)
             self._h = None
             if pending:
-                raise _lib.BevgenError(_lib.ERR_NUMERIC if pending & 60 else -4, f"context closed with device status word {pending} pending: results of its last calls were invalid "
+                raise _lib.BevgenError(_lib.ERR_NUMERIC if pending & 124 else -4, f"context closed with device status word {pending} pending: results of its last calls were invalid "
                                        "(include/bevgen_hip.h BEVGEN_STATUS_*)")
 
     def __del__(self):
@@ -701,10 +702,19 @@ class Context:
                                                     self._s()))
         return out
 
-    def op_decode_attention(self, q, kcache, vcache, n, bias=None, keep=None, scale=0.125, kv_dtype=0):
+    @staticmethod
+    def _cache_lmax(kcache, kv_dtype, Lmax):
+        # kv_dtype 2 (int8): the cache is a flat uint8 buffer in the BEVGEN_KV_I8 layout (codes, then row scales) and says nothing about Lmax
+        if int(kv_dtype) == 2:
+            if Lmax is None:
+                raise ValueError("kv_dtype=2 (int8 cache): pass Lmax explicitly, the cache is a flat uint8 buffer")
+            return int(Lmax)
+        return kcache.shape[2] if Lmax is None else int(Lmax)
+
+    def op_decode_attention(self, q, kcache, vcache, n, bias=None, keep=None, scale=0.125, kv_dtype=0, Lmax=None):
         B, HD = q.shape
         H = HD // 64
-        Lmax = kcache.shape[2]
+        Lmax = self._cache_lmax(kcache, kv_dtype, Lmax)
         out = torch.empty((B, HD), dtype=torch.float32, device=self.device)
         ldb = 0 if bias is None else bias.shape[-1]
         ldk = 0 if keep is None else keep.shape[-1]
@@ -714,11 +724,11 @@ class Context:
         return out
 
     def op_ar_attn_fused(self, x, ln_w, ln_b, wqkv, bqkv, kcache, vcache, n, *, partial=None, rbias=None, bias=None, attn_mask=None, layout=None, block=1, G=1, prefix=0,
-                         kv_dtype=0, w_f16=False, split=False):
-        """Attention half of a fused Route A decode layer (appends k/v to cache row n-1 in place) -> x2 [B, D]."""
+                         kv_dtype=0, w_f16=False, split=False, Lmax=None):
+        """Attention half of a fused Route A decode layer (appends k/v to cache row n-1 in place) -> x2 [B, D].  kv_dtype 2: flat uint8 caches + an explicit Lmax."""
         B, D = x.shape
         H = D // 64
-        Lmax = kcache.shape[2]
+        Lmax = self._cache_lmax(kcache, kv_dtype, Lmax)
         out = torch.empty((B, D), dtype=torch.float32, device=self.device)
         ns = 0 if partial is None else partial.shape[0]
         self._check(self.lib.bevgen_op_ar_attn_fused(self._h, _ptr(x), _ptr(partial), ns, _ptr(rbias), _ptr(ln_w), _ptr(ln_b), _ptr(wqkv), _ptr(bqkv), int(w_f16),
@@ -1016,7 +1026,7 @@ class Context:
                                                          int(Nq), int(Nk), int(Nk_pad), self._s()))
 
     def op_kv_cache_write(self, kind, kcache, vcache, *, kv_dtype, B, H, Lmax, qkv=None, q=None, n=1, pos0=0, pos=None, layers=1, rows=0, src=0, dst0=0, count=0):
-        """kind 'scatter' | 'append' | 'replicate_prefix' on caches [(layers,) B, H, Lmax, 64] of kv_dtype 0 (fp32) / 1 (fp16); `pos`: the device int32 position of append."""
+        """kind 'scatter' | 'append' | 'replicate_prefix' on caches [(layers,) B, H, Lmax, 64] of kv_dtype 0 (fp32) / 1 (fp16) / 2 (int8: flat uint8 buffers of 68 B H Lmax bytes per layer); `pos`: the device int32 position of append."""
         k = {"scatter": 0, "append": 1, "replicate_prefix": 2}[kind]
         self._check(self.lib.bevgen_op_kv_cache_write(self._h, k, _ptr(qkv), _ptr(q), _ptr(kcache), _ptr(vcache), int(kv_dtype), int(B), int(H), int(n), int(pos0), _ptr(pos),
                                                       int(Lmax), int(layers), int(rows), int(src), int(dst0), int(count), self._s()))

@@ -46,7 +46,11 @@ enum { BEVGEN_ROUTE_MASKGIT = 0, BEVGEN_ROUTE_AR = 1 };
  *         rounded to 11 significant bits on every call, where the reference's bf16 autocast keeps 8.  (A value of this enum and not a word of bevgen_cfg.reserved[]: a
  *         library that does not know the mode refuses the context instead of running it with three products.) */
 enum { BEVGEN_PRECISION_FP32 = 0, BEVGEN_PRECISION_BF16 = 1 /* reserved */, BEVGEN_PRECISION_F16X3 = 2, BEVGEN_PRECISION_F16X1 = 3 };
-enum { BEVGEN_KV_F32 = 0, BEVGEN_KV_F16 = 1 };
+/* KV-cache storage of Route A.  BEVGEN_KV_I8 (opt-in, lossy): per layer, K and V each are [B, H, Lmax, 64] int8 codes followed immediately by [B, H, Lmax] fp32 row scales
+ * - 68 B H Lmax bytes, the scale plane at byte offset 64 B H Lmax.  Quantiser of one 64-element row r (one head's k or v of one token), IEEE fp32 throughout:
+ * amax = max |r_i|; amax < 1e-30: codes 0, scale 0; else scale = amax / 127, code_i = clamp(rint(r_i * (127 / amax)), -127, 127) (round to nearest even); the value read
+ * back is code_i * scale.  Every finite row is representable (no range refusal); a NaN / inf in a row raises BEVGEN_STATUS_KV_NONFINITE. */
+enum { BEVGEN_KV_F32 = 0, BEVGEN_KV_F16 = 1, BEVGEN_KV_I8 = 2 };
 enum { BEVGEN_DECODE_FUSED = 0, BEVGEN_DECODE_PER_OP = 1, BEVGEN_DECODE_SPLIT = 2, BEVGEN_DECODE_AUTO = 3 };
 enum { BEVGEN_W_F32 = 0, BEVGEN_W_F16 = 1 };
 enum { BEVGEN_DTYPE_F32 = 0, BEVGEN_DTYPE_I64 = 1, BEVGEN_DTYPE_U8 = 2, BEVGEN_DTYPE_F64 = 3 };
@@ -67,7 +71,7 @@ enum {
  *   - in bevgen_synchronize (after waiting for the stream: the call a caller makes before it trusts / copies the results),
  *   - at the entry of EVERY later entry point on the context (no synchronisation: an error raised by an earlier asynchronous call is reported by the next call at the latest),
  *   - in bevgen_finalize (weights outside the f16 range of the chosen precision) and, as a message on stderr, in bevgen_destroy.
- * A raised word is returned as BEVGEN_ERR_NUMERIC (bits 4, 8, 16, 32) or BEVGEN_ERR_INTERNAL (bits 1, 2) and then cleared.
+ * A raised word is returned as BEVGEN_ERR_NUMERIC (bits 4, 8, 16, 32, 64) or BEVGEN_ERR_INTERNAL (bits 1, 2) and then cleared.
  * Policy for precision = F16X3 / fp16 storage modes: an operand whose f16 image would be inf / NaN (|v| >= 65520) is an ERROR, not rescaled - the split keeps fp32-class
  * mantissas but f16's exponent range, where the reference's bf16 / fp32 arithmetic has 8 exponent bits; such a checkpoint must run with BEVGEN_PRECISION_FP32.
  * One opt-in exception, stage 1 only: with bevgen_cfg.vq_range = 1 the un-normalised activation tensors of the decoder and the encoder that become f16 operands (decoder: in
@@ -81,8 +85,9 @@ enum {
     BEVGEN_STATUS_NONFINITE_LOGITS = 4,   /* a sampler read a NaN / inf logit or critic score */
     BEVGEN_STATUS_F16_RANGE = 8,          /* a value written as an f16 operand (hi / lo planes, fp16 KV cache, fp16 decode activations, fp16 weights) was NaN or |v| >= 65520 */
     BEVGEN_STATUS_NONFINITE_PIXELS = 16,  /* the VQGAN decoder produced a NaN / inf pixel */
-    BEVGEN_STATUS_NONFINITE_LATENTS = 32  /* the VQGAN quantizer met a latent row without a finite distance to any codebook entry (NaN / inf in the image or an overflow in the
+    BEVGEN_STATUS_NONFINITE_LATENTS = 32, /* the VQGAN quantizer met a latent row without a finite distance to any codebook entry (NaN / inf in the image or an overflow in the
                                              encoder): that row's token id is written as 0 */
+    BEVGEN_STATUS_KV_NONFINITE = 64       /* a key / value row written into the int8 KV cache (BEVGEN_KV_I8) held a NaN / inf */
 };
 
 /* Sizes of the stage-2 transformer (mirror of GPTConfig, modules/transformer/mingpt_sparse.py:26-102) and of the
@@ -106,7 +111,8 @@ typedef struct bevgen_cfg {
     int32_t vq_attn_resolution;                        /* spatial size at which AttnBlocks are inserted (16) */
     int32_t vq_in_channels;                            /* encoder input channels (3 images / 7 Argoverse BEV classes); 0 = decoder only */
     int32_t kv_cache_dtype;                            /* Route A KV-cache storage: BEVGEN_KV_F32 (default, bit-exact tokens) or BEVGEN_KV_F16 (fp16 storage,
-                                                          fp32 accumulate: half the decode-attention HBM traffic; tokens no longer guaranteed identical) */
+                                                          fp32 accumulate: half the decode-attention HBM traffic; tokens no longer guaranteed identical) or
+                                                          BEVGEN_KV_I8 (int8 codes + one fp32 scale per (token, head) row, fp32 accumulate: 68 bytes per row; lossy) */
     int32_t decode_path;                               /* Route A decode step: BEVGEN_DECODE_FUSED (default: three launches per layer, decode_fused.hip) or
                                                           BEVGEN_DECODE_PER_OP (one kernel per operator: the round-1 path, kept as the A/B reference) or
                                                           BEVGEN_DECODE_SPLIT (four launches per layer: LayerNorm + QKV projection of the whole batch as one MFMA kernel that
@@ -571,7 +577,9 @@ int bevgen_op_token_rows(bevgen_ctx* ctx, int kind, const int64_t* d_ids, const 
  * [0, Nk] = (null key / value of d_null_kv [2, H, 64], then d_kvraw [B Nk, (k | v) 64 H]), keys l2-normalised o d_k_scale (d_kvraw NULL: skipped). */
 int bevgen_op_muse_qkv_prep_f32(bevgen_ctx* ctx, const float* d_qraw /* or NULL */, const float* d_kvraw /* or NULL */, const float* d_null_kv, const float* d_q_scale,
                                 const float* d_k_scale, float* d_q, float* d_k, float* d_v, int B, int H, int Nq, int Nk, int Nk_pad, void* stream);
-/* Route A's KV-cache writers on a cache [B, H, Lmax, 64] (kv_dtype 0 fp32 / 1 fp16; fp16 values outside the range raise BEVGEN_STATUS_F16_RANGE).
+/* Route A's KV-cache writers on a cache [B, H, Lmax, 64] (kv_dtype 0 fp32 / 1 fp16; fp16 values outside the range raise BEVGEN_STATUS_F16_RANGE; 2 int8: the
+ * BEVGEN_KV_I8 layout of B slots, [layers] of them back to back for replicate_prefix, which copies both planes; NaN / inf rows raise BEVGEN_STATUS_KV_NONFINITE).
+ * bevgen_op_decode_attention and bevgen_op_ar_attn_fused take the same three storage types.
  *   kind 0 scatter: rows [pos0, pos0 + n) of every (b, h) from d_qkv [B n, (q | k | v) 64 H]; d_q [B, H, n, 64] (or NULL) receives the queries
  *   kind 1 append:  n = 1, row *d_pos + pos0 (d_pos a device int)
  *   kind 2 replicate_prefix: cache [layers, B, H, Lmax, 64]: the first `rows` rows of sequence slot `src` are copied to slots [dst0, dst0 + count) of every layer and head */
