@@ -19,7 +19,7 @@ PRECISION_FP32, PRECISION_BF16, PRECISION_F16X3, PRECISION_F16X1 = 0, 1, 2, 3
 KV_F32, KV_F16, KV_I8 = 0, 1, 2
 DECODE_FUSED, DECODE_PER_OP, DECODE_SPLIT, DECODE_AUTO = 0, 1, 2, 3
 VQ_OUT_RAW, VQ_OUT_DENORM, VQ_OUT_U8 = 0, 1, 2
-W_F32, W_F16 = 0, 1
+W_F32, W_F16, W_I8 = 0, 1, 2
 DTYPE_F32, DTYPE_I64, DTYPE_U8, DTYPE_F64 = 0, 1, 2, 3
 ERR_NUMERIC = -5
 STATUS_MLP_BARRIER, STATUS_MLP_PLACEMENT, STATUS_NONFINITE_LOGITS, STATUS_F16_RANGE, STATUS_NONFINITE_PIXELS, STATUS_NONFINITE_LATENTS = 1, 2, 4, 8, 16, 32
@@ -87,6 +87,7 @@ SIGNATURES = {
     "bevgen_op_muse_ff": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p]),
     "bevgen_op_layernorm_planes": (_i, [_p, _p, _i, _p, _p, _p, _i, _i, _i, _i, _p]),
     "bevgen_op_ln_gemm": (_i, [_p, _p, _p, _p, _f, _p, _p, _p, _i, _i, _i, _i, _i, C.POINTER(_i), _p]),
+    "bevgen_op_quantize_rows_i8": (_i, [_p, _p, _i, _i, _p, _p, _p, _p]),
     "bevgen_op_mlp_fused": (_i, [_p, _p, _p, _p, _f, _p, _p, _p, _p, _i, _p, _i, _i, _p]),
     "bevgen_op_remask": (_i, [_p, _p, _p, _p, _i, _i, _i, C.c_int64, _p]),
     "bevgen_op_maskgit_pick": (_i, [_p, _p, _p, _i, _p, _i, _i, _i, _f, C.c_int64, C.c_uint64, C.c_uint, _p, _i, _p]),

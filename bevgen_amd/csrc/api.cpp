@@ -55,6 +55,8 @@ int bevgen_create(const bevgen_cfg* cfg, int device, bevgen_ctx** out) {
                    "bevgen_create: precision must be BEVGEN_PRECISION_FP32, BEVGEN_PRECISION_F16X3 or BEVGEN_PRECISION_F16X1");
         BG_REQUIRE(cfg->weight_dtype == BEVGEN_W_F32 || (cfg->weight_dtype == BEVGEN_W_F16 && (cfg->precision == BEVGEN_PRECISION_F16X3 || f16x1)),
                    "bevgen_create: weight_dtype must be BEVGEN_W_F32, or BEVGEN_W_F16 together with BEVGEN_PRECISION_F16X3 / _F16X1");
+        BG_REQUIRE(cfg->decode_weight_dtype == BEVGEN_W_F32 || cfg->decode_weight_dtype == BEVGEN_W_F16 || cfg->decode_weight_dtype == BEVGEN_W_I8,
+                   "bevgen_create: decode_weight_dtype must be BEVGEN_W_F32, BEVGEN_W_F16 or BEVGEN_W_I8, got %d", cfg->decode_weight_dtype);
         BG_REQUIRE(cfg->vq_range == 0 || cfg->vq_range == 1, "bevgen_create: vq_range must be 0 (refuse) or 1 (rescale), got %d", cfg->vq_range);
         int ndev = 0;
         HIP_CHECK(hipGetDeviceCount(&ndev));
@@ -508,13 +510,26 @@ int bevgen_op_ln_gemm(bevgen_ctx* ctx, const float* a, const float* ln_w, const 
         BG_REQUIRE(skinny_fused_supported(M, N, K, ln_w != nullptr), "op_ln_gemm: unsupported shape M=%d N=%d K=%d", M, N, K);
         SkinnyFusedArgs g;
         g.A = a; g.lda = K; g.ln_w = ln_w; g.ln_b = ln_b; g.eps = eps;
-        float *wp, *cs, *ds;
+        // a context created with decode_weight_dtype = i8 runs the operator on the int8 image of `w` (the model that mode defines: code * scale per row); the
+        // fold constants below then come from the dequantised matrix, as bevgen_finalize takes them
+        const bool wi8 = ctx->cfg.decode_weight_dtype == BEVGEN_W_I8;
+        float *wp, *cs, *ds, *sc, *wdq;
         ctx->arena.carve([&](Arena& ar) {
-            wp = ar.get<float>(skinny_packed_floats(N, K));
+            wp = wi8 ? reinterpret_cast<float*>(ar.alloc(skinny_packed_bytes_i8(N, K))) : ar.get<float>(skinny_packed_floats(N, K));
             cs = ksplit == -1 ? ar.get<float>((size_t)N) : nullptr;
             ds = ksplit == -1 ? ar.get<float>((size_t)N) : nullptr;
+            sc = wi8 ? ar.get<float>((size_t)N) : nullptr;
+            wdq = wi8 && ksplit == -1 ? ar.get<float>((size_t)N * K) : nullptr;
         });
-        launch_pack_skinny_weight(w, wp, N, K, (hipStream_t)stream);
+        if (wi8) {
+            const int kw = K / (ksplit > 0 ? ksplit : (ln_w ? 1 : skinny_fused_ksplit(N, K)));
+            BG_REQUIRE(kw % (SF_WAVES * 32) == 0, "op_ln_gemm: int8 weights need a K slice that is a multiple of %d (K=%d)", SF_WAVES * 32, K);
+            launch_pack_skinny_weight_i8(w, wp, sc, N, K, (hipStream_t)stream);
+            if (wdq) { launch_quantize_rows_i8(w, N, K, nullptr, nullptr, wdq, (hipStream_t)stream); w = wdq; }
+            g.w_f16 = 2; g.w_scale = sc;
+        } else {
+            launch_pack_skinny_weight(w, wp, N, K, (hipStream_t)stream);
+        }
         g.Wp = wp; g.bias = bias; g.C = c; g.ldc = N;
         g.M = M; g.N = N; g.K = K; g.act = act_gelu ? ACT_GELU : ACT_NONE;
         g.ksplit = ksplit > 0 ? ksplit : (ln_w ? 1 : skinny_fused_ksplit(N, K));
@@ -529,15 +544,23 @@ int bevgen_op_ln_gemm(bevgen_ctx* ctx, const float* a, const float* ln_w, const 
     });
 }
 
+int bevgen_op_quantize_rows_i8(bevgen_ctx* ctx, const float* w, int N, int K, void* codes, float* scales, float* dequant, void* stream) {
+    return guarded(ctx, [&] {
+        BG_REQUIRE(w && N >= 1 && K >= 1 && codes && scales, "op_quantize_rows_i8: bad arguments");
+        launch_quantize_rows_i8(w, N, K, codes, scales, dequant, (hipStream_t)stream);
+    });
+}
+
 int bevgen_op_mlp_fused(bevgen_ctx* ctx, const float* x, const float* ln_w, const float* ln_b, float eps, const float* w1, const float* b1, const float* w2, const float* b2,
                         int w_f16, float* out, int M, int D, void* stream) {
     return guarded(ctx, [&] {
         hipStream_t s = (hipStream_t)stream;
         BG_REQUIRE(x && ln_w && ln_b && w1 && b1 && w2 && b2 && out, "op_mlp_fused: missing operand");
+        BG_REQUIRE(w_f16 >= 0 && w_f16 <= 2, "op_mlp_fused: w_f16 = %d (0 fp32, 1 fp16, 2 int8 weights)", w_f16);
         BG_REQUIRE(mlp_fused_supported(M, D, w_f16 != 0), "op_mlp_fused: unsupported shape M=%d D=%d (or a device with fewer CUs than workgroups / BEVGEN_MLP_FUSE=0)", M, D);
-        const size_t eb = w_f16 ? sizeof(_Float16) : sizeof(float);
+        const size_t eb = w_f16 == 2 ? 1 : w_f16 ? sizeof(_Float16) : sizeof(float);   // (skinny_packed_bytes_i8 == skinny_packed_floats: one byte per element)
         void *w1p, *w2p;
-        float *cs, *ds, *hidden, *part, *zero, *w1r, *w2r;
+        float *cs, *ds, *hidden, *part, *zero, *w1r, *w2r, *sc1, *sc2;
         unsigned* sync;
         ctx->arena.carve([&](Arena& ar) {
             w1p = ar.alloc(skinny_packed_floats(4 * D, D) * eb);
@@ -549,10 +572,17 @@ int bevgen_op_mlp_fused(bevgen_ctx* ctx, const float* x, const float* ln_w, cons
             zero = ar.get<float>((size_t)M * D);
             sync = ar.get<unsigned>(mlp_fused_sync_words());
             w1r = w_f16 ? ar.get<float>((size_t)4 * D * D) : nullptr;
-            w2r = w_f16 ? ar.get<float>((size_t)4 * D * D) : nullptr;
+            w2r = w_f16 == 1 ? ar.get<float>((size_t)4 * D * D) : nullptr;
+            sc1 = w_f16 == 2 ? ar.get<float>((size_t)4 * D) : nullptr;
+            sc2 = w_f16 == 2 ? ar.get<float>((size_t)D) : nullptr;
         });
         const float *w1u = w1, *w2u = w2;
-        if (w_f16) {   // the model decode_weights = f16 defines: matrices rounded to fp16-representable values (row constants from the rounded matrix, as bevgen_finalize does)
+        if (w_f16 == 2) {   // the model decode_weights = i8 defines: code * scale per row (the row constants of the folded ln2 from the dequantised up matrix)
+            launch_pack_skinny_weight_i8(w1, w1p, sc1, 4 * D, D, s);
+            launch_pack_skinny_weight_i8(w2, w2p, sc2, D, 4 * D, s);
+            launch_quantize_rows_i8(w1, 4 * D, D, nullptr, nullptr, w1r, s);
+            w1u = w1r;
+        } else if (w_f16) {   // the model decode_weights = f16 defines: matrices rounded to fp16-representable values (row constants from the rounded matrix, as bevgen_finalize does)
             HIP_CHECK(hipMemcpyAsync(w1r, w1, (size_t)4 * D * D * sizeof(float), hipMemcpyDeviceToDevice, s));
             HIP_CHECK(hipMemcpyAsync(w2r, w2, (size_t)4 * D * D * sizeof(float), hipMemcpyDeviceToDevice, s));
             launch_round_to_f16(w1r, nullptr, (long)4 * D * D, s);
@@ -569,7 +599,7 @@ int bevgen_op_mlp_fused(bevgen_ctx* ctx, const float* x, const float* ln_w, cons
         HIP_CHECK(hipMemsetAsync(sync, 0, mlp_fused_sync_words() * sizeof(unsigned), s));
         MlpFusedArgs g;
         g.A = x; g.lda = D; g.ln_w = ln_w; g.ln_cs = cs; g.ln_ds = ds; g.eps = eps;
-        g.Wup = reinterpret_cast<const float*>(w1p); g.Wdn = reinterpret_cast<const float*>(w2p); g.w_f16 = w_f16;
+        g.Wup = reinterpret_cast<const float*>(w1p); g.Wdn = reinterpret_cast<const float*>(w2p); g.w_f16 = w_f16; g.Wup_sc = sc1; g.Wdn_sc = sc2;
         g.hidden = hidden; g.C = part; g.sync = sync; g.err = ctx->status_dev; g.M = M; g.D = D;
         g.trace = ctx->trace ? ctx->trace + 4096 * 8 : nullptr;
         // (twice: the second launch runs on the barrier state the first one left behind - the self-cleaning property the hipGraph replay of the decode step relies on)
@@ -720,17 +750,19 @@ int bevgen_op_ar_attn_fused(bevgen_ctx* ctx, const float* x, const float* partia
         hipStream_t s = (hipStream_t)stream;
         const int D = H * 64, L = Lmax;
         BG_REQUIRE(x && ln_w && ln_b && wqkv && bqkv && kc && vc && out && n >= 1 && n <= Lmax && kv_dtype >= 0 && kv_dtype <= 2, "op_ar_attn_fused: bad arguments");
+        BG_REQUIRE(w_f16 >= 0 && w_f16 <= 2, "op_ar_attn_fused: w_f16 = %d (0 fp32, 1 fp16, 2 int8 weights)", w_f16);
         BG_REQUIRE(ar_attn_fused_supported(B, G, D, H), "op_ar_attn_fused: unsupported shape B=%d G=%d D=%d H=%d", B, G, D, H);
         BG_REQUIRE(!layout || (block >= 1 && L % block == 0), "op_ar_attn_fused: Lmax %d is not a multiple of the block size %d", L, block);
         const int nb = layout ? L / block : 0, cld = (int)cdiv(L, 16) + 1;
         ArAttnFusedArgs a;
         if (split == -1) { a.stage_cap = 0; split = 0; }                       // the fused kernel without K/V pieces staged in LDS
         void* h;
-        float *tmp, *cs, *ds, *wp, *qkv, *xn;
+        float *tmp, *cs, *ds, *wp, *qkv, *xn, *sc;
         uint8_t *al, *lay;
         uint16_t* ch;
         ctx->arena.carve([&](Arena& ar) {
-            h = w_f16 ? ar.alloc((size_t)3 * D * D * 2) : nullptr;
+            h = w_f16 ? ar.alloc((size_t)3 * D * D * 2) : nullptr;   // (int8: the codes take half of it)
+            sc = w_f16 == 2 ? ar.get<float>((size_t)3 * D) : nullptr;
             tmp = w_f16 ? ar.get<float>((size_t)3 * D * D) : nullptr;   // round_to_f16 rounds in place: work on a copy of the caller's matrix (arena: no allocation, no sync)
             cs = ar.get<float>((size_t)3 * D);   // row constants of the folded ln1
             ds = ar.get<float>((size_t)3 * D);
@@ -747,7 +779,11 @@ int bevgen_op_ar_attn_fused(bevgen_ctx* ctx, const float* x, const float* partia
         a.x.bias = rbias;
         a.ln_w = ln_w; a.ln_b = ln_b; a.wqkv = wqkv; a.bqkv = bqkv;
         const float* w_rounded = nullptr;
-        if (w_f16) {
+        if (w_f16 == 2) {   // codes, scales and the dequantised matrix (fold constants) in one pass over the caller's matrix
+            launch_quantize_rows_i8(wqkv, 3 * D, D, h, sc, tmp, s);
+            a.wqkv_h = h; a.wqkv_sc = sc;
+            w_rounded = tmp;
+        } else if (w_f16) {
             HIP_CHECK(hipMemcpyAsync(tmp, wqkv, (size_t)3 * D * D * 4, hipMemcpyDeviceToDevice, s));
             launch_round_to_f16(tmp, h, 3L * D * D, s);
             a.wqkv_h = h;
@@ -772,12 +808,13 @@ int bevgen_op_ar_attn_fused(bevgen_ctx* ctx, const float* x, const float* partia
         a.trace = ctx->trace;
         if (split) {
             BG_REQUIRE(skinny_fused_supported(B, 3 * D, D, true) && (!w_f16 || skinny_fused_f16_ok(3 * D, D, true)), "op_ar_attn_fused: the split form does not support B=%d D=%d", B, D);
-            if (w_f16) launch_pack_skinny_weight_f16(wqkv, wp, 3 * D, D, s);   // rounds to fp16 while packing
+            if (w_f16 == 2) launch_pack_skinny_weight_i8(wqkv, wp, sc, 3 * D, D, s);   // (the same scales again)
+            else if (w_f16) launch_pack_skinny_weight_f16(wqkv, wp, 3 * D, D, s);   // rounds to fp16 while packing
             else launch_pack_skinny_weight(wqkv, wp, 3 * D, D, s);
             SkinnyFusedArgs pq;
             const RowSrc src = a.x;
             pq.a_src = &src;
-            pq.ln_w = ln_w; pq.ln_b = ln_b; pq.Wp = wp; pq.w_f16 = w_f16; pq.bias = bqkv;
+            pq.ln_w = ln_w; pq.ln_b = ln_b; pq.Wp = wp; pq.w_f16 = w_f16; pq.w_scale = sc; pq.bias = bqkv;
             pq.C = qkv; pq.ldc = 3 * D; pq.xn_out = xn; pq.ldxn = D;
             pq.M = B; pq.N = 3 * D; pq.K = D; pq.ksplit = 1;
             launch_skinny_fused(pq, s);

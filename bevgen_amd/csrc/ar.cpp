@@ -94,7 +94,7 @@ ArPlanIn plan_in(const Ctx& c, int B, int G) {
     ArPlanIn in;
     in.B = B; in.G = G;
     in.D = c.D; in.H = c.H; in.K = c.K; in.L = c.L; in.V = c.V;
-    in.decode_path = c.cfg.decode_path; in.w_f16 = c.cfg.decode_weight_dtype == BEVGEN_W_F16; in.chains = c.cfg.decode_chains; in.trace = c.trace != nullptr;
+    in.decode_path = c.cfg.decode_path; in.w_f16 = c.cfg.decode_weight_dtype; in.chains = c.cfg.decode_chains; in.trace = c.trace != nullptr;
     in.mlpf_ready = c.mlpf_sync && !c.mlpf_disabled; in.mlpf_device_ok = c.mlpf_device_ok;
     return in;
 }
@@ -347,7 +347,7 @@ static void head_logits(Ctx& c, StepWs& w, const ArStepPlan& plan, int B, float*
         SkinnyFusedArgs g;
         g.A = st.hidden; g.lda = c.D;
         g.ln_w = c.pf("ln_f.weight"); g.ln_b = c.pf("ln_f.bias"); g.eps = 1e-5f;
-        g.Wp = c.head_wp; g.w_f16 = c.cfg.decode_weight_dtype == BEVGEN_W_F16;
+        g.Wp = c.head_wp; g.w_f16 = c.cfg.decode_weight_dtype; g.w_scale = c.head_sc;
         g.C = logits; g.ldc = c.V;
         g.M = B; g.N = c.V; g.K = c.D; g.ksplit = 1;
         launch_skinny_fused(g, s);
@@ -379,7 +379,7 @@ static void decode_chain_launch(Ctx& c, StepWs& w, const ArStepPlan& plan, const
     const size_t layer_bytes = cache_layer_bytes(c, B);
     const size_t chain_off = cache_slot_bytes(c, r0);         // this chain's first cache slot inside a layer
     const int ks = plan.down_ksplit;
-    const int wf16 = g.decode_weight_dtype == BEVGEN_W_F16;
+    const int wf16 = g.decode_weight_dtype;   // storage kind of the images: 0 fp32, 1 fp16, 2 int8 (+ the layers' row scales)
     float* part = w.part + (size_t)ks * r0 * D;               // [ks][Bc][D] per chain, chains back to back
     float* m1 = w.m1 + (size_t)r0 * 4 * D;
     float* qkv = w.qkv + (size_t)r0 * 3 * D;
@@ -394,7 +394,7 @@ static void decode_chain_launch(Ctx& c, StepWs& w, const ArStepPlan& plan, const
             SkinnyFusedArgs pq;
             pq.a_src = &src;
             pq.ln_w = l.ln1_w; pq.ln_b = l.ln1_b; pq.eps = 1e-5f;
-            pq.Wp = l.wqkv_wp; pq.w_f16 = wf16; pq.bias = l.bqkv;
+            pq.Wp = l.wqkv_wp; pq.w_f16 = wf16; pq.w_scale = l.wqkv_sc; pq.bias = l.bqkv;
             pq.C = qkv; pq.ldc = 3 * D;
             pq.xn_out = xn; pq.ldxn = D;
             pq.M = Bc; pq.N = 3 * D; pq.K = D; pq.ksplit = 1;
@@ -404,7 +404,7 @@ static void decode_chain_launch(Ctx& c, StepWs& w, const ArStepPlan& plan, const
         } else {
             a.x = src;
             a.ln_w = l.ln1_w; a.ln_b = l.ln1_b; a.eps = 1e-5f;
-            a.wqkv = l.wqkv; a.bqkv = l.bqkv; a.wqkv_h = l.wqkv_h;
+            a.wqkv = l.wqkv; a.bqkv = l.bqkv; a.wqkv_h = l.wqkv_h; a.wqkv_sc = l.wqkv_sc;
             a.ln_cs = l.ln1_cs; a.ln_ds = l.ln1_ds;
         }
         a.kcache = reinterpret_cast<char*>(st.kcache) + i * layer_bytes + chain_off;
@@ -422,7 +422,7 @@ static void decode_chain_launch(Ctx& c, StepWs& w, const ArStepPlan& plan, const
             MlpFusedArgs mf;
             mf.A = x2; mf.lda = D;
             mf.ln_w = l.ln2_w; mf.ln_cs = l.mlp0_cs; mf.ln_ds = l.mlp0_ds; mf.eps = 1e-5f;
-            mf.Wup = l.mlp0_wp; mf.Wdn = l.mlp2_wp; mf.w_f16 = wf16;
+            mf.Wup = l.mlp0_wp; mf.Wdn = l.mlp2_wp; mf.w_f16 = wf16; mf.Wup_sc = l.mlp0_sc; mf.Wdn_sc = l.mlp2_sc;
             mf.hidden = m1; mf.C = part;
             mf.sync = c.mlpf_sync; mf.err = c.status_dev;
             mf.M = Bc; mf.D = D;
@@ -435,7 +435,7 @@ static void decode_chain_launch(Ctx& c, StepWs& w, const ArStepPlan& plan, const
         SkinnyFusedArgs up;
         up.A = x2; up.lda = D;
         up.ln_w = l.ln2_w; up.ln_b = l.ln2_b; up.eps = 1e-5f;
-        up.Wp = l.mlp0_wp; up.w_f16 = wf16; up.bias = l.mlp0_b;
+        up.Wp = l.mlp0_wp; up.w_f16 = wf16; up.w_scale = l.mlp0_sc; up.bias = l.mlp0_b;
         // ln2 folded into the product (skinny_fused_kernel<.., FD>).  Same-box A/B, ms per decode step, folded vs direct: fp16 cache + fp16 weights 0.989-0.994 vs
         // 0.992-0.998, fp16 cache + fp32 weights 1.137-1.151 vs 1.154-1.163, fp32 both 1.447-1.454 vs 1.466-1.482 (profiles/r04_ab_ln2_fold.txt).  $BEVGEN_LN2_FOLD=0: direct form
         if (plan.ln2_fold) { up.ln_cs = l.mlp0_cs; up.ln_ds = l.mlp0_ds; }
@@ -445,7 +445,7 @@ static void decode_chain_launch(Ctx& c, StepWs& w, const ArStepPlan& plan, const
         launch_skinny_fused(up, s);
         SkinnyFusedArgs dn;
         dn.A = m1; dn.lda = 4 * D;
-        dn.Wp = l.mlp2_wp; dn.w_f16 = wf16;
+        dn.Wp = l.mlp2_wp; dn.w_f16 = wf16; dn.w_scale = l.mlp2_sc;
         dn.M = Bc; dn.N = D; dn.K = 4 * D; dn.ksplit = ks;
         dn.trace = c.trace ? c.trace + 2 * 4096 * 8 : nullptr;
         if (ks > 1) {

@@ -36,7 +36,7 @@ inline bool skinny_fused_supported(int M, int N, int K, bool ln) {
     const int kw = K / s;
     return kw <= 1024 && kw % (SF_WAVES * 16) == 0;
 }
-// fp16 weight images: the K slice of a workgroup must be a multiple of 32 per wave
+// fp16 and int8 weight images (one lane map): the K slice of a workgroup must be a multiple of 32 per wave
 inline bool skinny_fused_f16_ok(int N, int K, bool ln) {
     const int s = ln ? 1 : skinny_fused_ksplit(N, K);
     return K % s == 0 && (K / s) % (SF_WAVES * 32) == 0;
@@ -67,7 +67,8 @@ struct ArPlanIn {
     int G = 1;                              // sequences per layout group: the state's G (ar_prefill: its samples_per_layout candidate, ar_prefill_group)
     int D = 0, H = 0, K = 0, L = 0, V = 0;  // model: width, heads, condition rows, sequence length, vocabulary (head rows)
     int decode_path = BEVGEN_DECODE_FUSED;  // as configured (BEVGEN_DECODE_*)
-    bool w_f16 = false;                     // decode_weight_dtype = f16
+    int w_f16 = 0;                          // decode_weight_dtype, the storage kind of the packed images: 0 fp32, 1 fp16 (BEVGEN_W_F16), 2 int8 codes + row scales (BEVGEN_W_I8:
+                                            // the int8 image keeps the fp16 image's lane map, so every rule below that asks `w_f16` holds for both)
     int chains = 0;                         // as configured ($BEVGEN_DECODE_CHAINS through the Python host)
     bool trace = false;                     // the phase-timestamp buffer is attached
     bool mlpf_ready = false;                // the context holds the fused MLP launch's barrier words and no launch of it has failed (mlpf_sync && !mlpf_disabled)

@@ -278,6 +278,11 @@ static void finalize_muse(Ctx& c) {
 static void pack_split_qkv_layer(Ctx& c, ArLayer& l, hipStream_t s) {
     const int D = c.D;
     const bool wf16 = c.cfg.decode_weight_dtype == BEVGEN_W_F16;
+    if (c.cfg.decode_weight_dtype == BEVGEN_W_I8) {   // (from the dequantised master: the quantiser reproduces its codes and the scales already in wqkv_sc, kernels.h)
+        l.wqkv_wp = reinterpret_cast<float*>(c.own(skinny_packed_bytes_i8(3 * D, D)));
+        launch_pack_skinny_weight_i8(l.wqkv, l.wqkv_wp, l.wqkv_sc, 3 * D, D, s);
+        return;
+    }
     l.wqkv_wp = reinterpret_cast<float*>(c.own(skinny_packed_floats(3 * D, D) * (wf16 ? sizeof(_Float16) : sizeof(float))));
     if (wf16) launch_pack_skinny_weight_f16(l.wqkv, l.wqkv_wp, 3 * D, D, s);
     else launch_pack_skinny_weight(l.wqkv, l.wqkv_wp, 3 * D, D, s);
@@ -291,9 +296,12 @@ static void finalize_ar(Ctx& c) {
     expect_shape(c, "x_pos_emb", {1, c.N, D});
     expect_shape(c, "cond_pos_emb", {1, c.K, D});
     expect_shape(c, "head.weight", {g.vocab_size, D});
-    const bool wf16 = g.decode_weight_dtype == BEVGEN_W_F16;
+    const bool wf16 = g.decode_weight_dtype == BEVGEN_W_F16, wi8 = g.decode_weight_dtype == BEVGEN_W_I8;
     const bool fused_like = g.decode_path == BEVGEN_DECODE_FUSED || g.decode_path == BEVGEN_DECODE_SPLIT || g.decode_path == BEVGEN_DECODE_AUTO;
     BG_REQUIRE(!wf16 || (fused_like && D % 256 == 0), "decode_weights = f16 needs the fused decode path and dim %% 256 == 0 (dim = %d)", D);
+    BG_REQUIRE(!wi8 || (fused_like && D % 256 == 0), "decode_weights = i8 needs the fused decode path and dim %% 256 == 0 (dim = %d)", D);
+    BG_REQUIRE(!wi8 || g.weight_dtype != BEVGEN_W_F16, "Route A: weight_dtype = f16 cannot be combined with decode_weight_dtype = i8 (the dequantised int8 matrices, "
+               "code * scale, are not fp16-representable: prefill and decode could not run ONE model)");
     BG_REQUIRE(g.weight_dtype != BEVGEN_W_F16 || wf16, "Route A: weight_dtype = f16 needs decode_weight_dtype = f16 as well (prefill and decode must run ONE rounded model)");
     c.ar.resize(g.num_layers);
     for (int i = 0; i < g.num_layers; ++i) {
@@ -316,6 +324,16 @@ static void finalize_ar(Ctx& c) {
             launch_round_to_f16(const_cast<float*>(l.mlp0_w), nullptr, 4L * D * D, 0);
             launch_round_to_f16(const_cast<float*>(l.mlp2_w), nullptr, 4L * D * D, 0);
         }
+        if (wi8) {   // the model becomes the one whose projection weights are code * scale, one scale per output row: every consumer below - fold constants, prefill planes,
+                     // bevgen_ar_forward, the decode images - sees the dequantised values
+            l.wqkv_h = c.own((size_t)3 * D * D);
+            l.wqkv_sc = reinterpret_cast<float*>(c.own((size_t)3 * D * sizeof(float)));
+            l.mlp0_sc = reinterpret_cast<float*>(c.own((size_t)4 * D * sizeof(float)));
+            l.mlp2_sc = reinterpret_cast<float*>(c.own((size_t)D * sizeof(float)));
+            launch_quantize_rows_i8(l.wqkv, 3 * D, D, l.wqkv_h, l.wqkv_sc, l.wqkv, 0);
+            launch_quantize_rows_i8(l.mlp0_w, 4 * D, D, nullptr, l.mlp0_sc, const_cast<float*>(l.mlp0_w), 0);
+            launch_quantize_rows_i8(l.mlp2_w, D, 4 * D, nullptr, l.mlp2_sc, const_cast<float*>(l.mlp2_w), 0);
+        }
         if (fused_like) {
             // (after the rounding above: the constants belong to the matrix the decode step multiplies by)
             l.ln1_cs = reinterpret_cast<float*>(c.own((size_t)3 * D * sizeof(float)));
@@ -330,9 +348,12 @@ static void finalize_ar(Ctx& c) {
             // the split layer (cfg.max_batch > 4).  Only such a context, when it is later called with <= 4 sequences after all, packs on that first call
             // (ctx_pack_split_qkv: one allocation per layer + one stream synchronisation, once per context; documented in include/bevgen_hip.h)
             if (g.decode_path == BEVGEN_DECODE_SPLIT || (g.decode_path == BEVGEN_DECODE_AUTO && g.max_batch <= kArAutoSplitMaxSeqs)) pack_split_qkv_layer(c, l, 0);
-            l.mlp0_wp = reinterpret_cast<float*>(c.own(skinny_packed_floats(4 * D, D) * eb));
-            l.mlp2_wp = reinterpret_cast<float*>(c.own(skinny_packed_floats(D, 4 * D) * eb));
-            if (wf16) {
+            l.mlp0_wp = reinterpret_cast<float*>(c.own(wi8 ? skinny_packed_bytes_i8(4 * D, D) : skinny_packed_floats(4 * D, D) * eb));
+            l.mlp2_wp = reinterpret_cast<float*>(c.own(wi8 ? skinny_packed_bytes_i8(D, 4 * D) : skinny_packed_floats(D, 4 * D) * eb));
+            if (wi8) {
+                launch_pack_skinny_weight_i8(l.mlp0_w, l.mlp0_wp, l.mlp0_sc, 4 * D, D, 0);
+                launch_pack_skinny_weight_i8(l.mlp2_w, l.mlp2_wp, l.mlp2_sc, D, 4 * D, 0);
+            } else if (wf16) {
                 launch_pack_skinny_weight_f16(l.mlp0_w, l.mlp0_wp, 4 * D, D, 0);
                 launch_pack_skinny_weight_f16(l.mlp2_w, l.mlp2_wp, D, 4 * D, 0);
             } else {
@@ -352,7 +373,12 @@ static void finalize_ar(Ctx& c) {
         // probe here, never inside a stream capture)
         c.mlpf_device_ok = mlp_fused_supported(1, D, wf16);
     }
-    if (fused_like) {
+    if (wi8) {
+        c.head_sc = reinterpret_cast<float*>(c.own((size_t)g.vocab_size * sizeof(float)));
+        launch_quantize_rows_i8(c.pf("head.weight"), g.vocab_size, D, nullptr, c.head_sc, const_cast<float*>(c.pf("head.weight")), 0);
+        c.head_wp = reinterpret_cast<float*>(c.own(skinny_packed_bytes_i8(g.vocab_size, D)));
+        launch_pack_skinny_weight_i8(c.pf("head.weight"), c.head_wp, c.head_sc, g.vocab_size, D, 0);
+    } else if (fused_like) {
         c.head_wp = reinterpret_cast<float*>(c.own(skinny_packed_floats(g.vocab_size, D) * (wf16 ? sizeof(_Float16) : sizeof(float))));
         if (wf16) launch_pack_skinny_weight_f16(c.pf("head.weight"), c.head_wp, g.vocab_size, D, 0);
         else launch_pack_skinny_weight(c.pf("head.weight"), c.head_wp, g.vocab_size, D, 0);
@@ -489,7 +515,7 @@ void ctx_finalize(Ctx& c) {
     }
     if (g.vq_ch > 0) vq_finalize(c);
     HIP_CHECK(hipDeviceSynchronize());
-    c.check_status("bevgen_finalize: a weight matrix");   // (a weight outside the f16 range of the split planes / the fp16 decode images)
+    c.check_status("bevgen_finalize: a weight matrix");   // (a weight outside the f16 range of the split planes / the fp16 decode images, a NaN / inf in a row of the int8 ones)
     c.finalized = true;
 }
 

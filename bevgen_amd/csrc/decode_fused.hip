@@ -66,6 +66,26 @@ void launch_rowsrc_materialize(const RowSrc& r0, float* out, int M, int D, int* 
 // ----------------------------------------------------------------------------------------------------------------- helpers
 typedef _Float16 half8_t __attribute__((ext_vector_type(8)));
 typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
+// int8 decode weights (WT == 2): the 8 codes a lane loaded in place of the fp16 image's half8_t.  |code| <= 127 is exact in f16, so behind this conversion the
+// matrix-pipe code of the fp16 image runs unchanged; the row's scale multiplies the fp32 accumulator in the epilogue.  (arithmetic shift of the byte moved to the
+// top of the word: sign extension for the codes -127 .. -1)
+__device__ __forceinline__ int i8_at(const u32x2& c, int e) { return (int)(c[e >> 2] << (24 - 8 * (e & 3))) >> 24; }
+// To f16 without a conversion instruction per element: code ^ 0x80 is the byte code + 128, and 0x6400 | byte is the f16 number 1024 + byte, so one v_perm_b32 builds a
+// pair of halves 1152 + code and one packed f16 subtraction (exact: integers below 2048) leaves the codes - 10 instructions per 8 codes where int -> fp32 -> f16 takes 16.
+typedef _Float16 half2_w __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ half8_t i8x8_to_half8(const u32x2& c) {
+    half8_t h;
+    const half2_w off = {(_Float16)1152.f, (_Float16)1152.f};
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+        const unsigned x = c[j] ^ 0x80808080u;
+        // v_perm_b32: selector bytes 0-3 take bytes of the second operand, 4-7 of the first -> (b0, 0x64, b1, 0x64) and (b2, 0x64, b3, 0x64)
+        const half2_w lo = __builtin_bit_cast(half2_w, __builtin_amdgcn_perm(0x64646464u, x, 0x04010400u)) - off;
+        const half2_w hi = __builtin_bit_cast(half2_w, __builtin_amdgcn_perm(0x64646464u, x, 0x04030402u)) - off;
+        h[4 * j + 0] = lo[0]; h[4 * j + 1] = lo[1]; h[4 * j + 2] = hi[0]; h[4 * j + 3] = hi[1];
+    }
+    return h;
+}
 // K / V rows are read with the NON-TEMPORAL hint (registers and LDS-DMA alike): a decode step streams ~85 MB of them per layer through 8 x 4 MB of L2 exactly once, and
 // without the hint that stream evicts what the step does reuse - the head's q/k/v weight rows its 16 workgroups share, and the weight images the MLP launches park in L2
 // for each other.  Same-box A/B, fp16 cache + fp16 weights: 0.996-0.999 -> 0.959-0.964 ms/step (profiles/r04_ab_kv_nontemporal.txt).
@@ -489,7 +509,7 @@ __device__ __forceinline__ void af_layout_attend(const ArAttnFusedArgs& a, const
 
 // ----------------------------------------------------------------------------------------------------------------- ln1 + qkv + attention
 // grid (H, B / G), 1024 threads.  Dynamic LDS: bias row [Lpad] | xn [G][D] | qkv [G][192] | red [16][G+1][66] | stat [16][G] | chunk list [Lpad/16 + 2] (uint16)
-template <int DT, int G, int WT, bool SP>   // KV-cache storage (0 fp32, 1 fp16), sequences per workgroup, decode-weight storage (0 fp32, 1 fp16), block-sparse layout
+template <int DT, int G, int WT, bool SP>   // KV-cache storage (0 fp32, 1 fp16, 2 int8), sequences per workgroup, decode-weight storage (0 fp32, 1 fp16, 2 int8 codes + row scales), block-sparse layout
 __global__ __launch_bounds__(1024) void ar_attn_fused_kernel(ArAttnFusedArgs a) {
     constexpr int NW = AF_WAVES;
     extern __shared__ float smem[];
@@ -556,6 +576,7 @@ __global__ __launch_bounds__(1024) void ar_attn_fused_kernel(ArAttnFusedArgs a) 
     // buffers.  The 16 workgroups of a head (one per sequence, same XCD) read the same rows through that XCD's L2: each starts at a different batch
     // so that at any moment they pull on different lines / channels instead of queueing on one.
     // fp16 weight storage: 8 elements per 16-byte load, twice the rows per batch for the same registers
+    // int8 weight storage: the fp16 form with 8-byte loads - the same 8 elements per lane and load, the same batches, the same x reads (experiments/r20.md)
     constexpr int EL = WT ? 8 : 4, NCH = WT ? 2 : 4;                 // elements per lane and load; loads per row (D <= 1024)
     // Rows per batch: small enough that NOTHING spills.  A spilled register is not free here: 1024 threads x 256 workgroups park 1 MB per register in scratch and
     // read it back, per launch - round 2's three-row batches (G = 1) spilled 1 / 4 registers in the fp32 / fp16-cache variants, i.e. up to 8 MB of extra traffic
@@ -563,7 +584,7 @@ __global__ __launch_bounds__(1024) void ar_attn_fused_kernel(ArAttnFusedArgs a) 
     // ms/step (fp16 cache + weights), and the FETCH_SIZE counter no longer shows MORE traffic at density 0.35 than at density 1.
     constexpr int RB = (G >= 4 ? 1 : 2) * (WT ? 2 : 1), NB = 12 / RB;
     constexpr bool PRE2 = G == 1;   // both register buffers requested when the x rows have arrived (in front of the staged K/V pieces), the loop refills behind each product
-    typedef typename std::conditional<WT == 1, half8_t, f32x4>::type WV;
+    typedef typename std::conditional<WT == 1, half8_t, typename std::conditional<WT == 2, u32x2, f32x4>::type>::type WV;
     const int rot = grp % NB;
     auto wrow = [&](int bi, int r) { return wave * 12 + ((bi + rot) % NB) * RB + r; };
     auto wbase = [&](int j) { return ((long)(j >> 6) * D + head * 64 + (j & 63)) * D; };
@@ -575,7 +596,8 @@ __global__ __launch_bounds__(1024) void ar_attn_fused_kernel(ArAttnFusedArgs a) 
 #pragma unroll
             for (int c = 0; c < NCH; ++c) {   // columns >= D: a clamped (valid) address, ignored by dot_batch
                 const long e = o + min(c * 64 * EL + lane * EL, D - EL);
-                if (WT) w[r][c] = *reinterpret_cast<const WV*>(reinterpret_cast<const _Float16*>(a.wqkv_h) + e);
+                if (WT == 2) w[r][c] = *reinterpret_cast<const WV*>(reinterpret_cast<const signed char*>(a.wqkv_h) + e);
+                else if (WT) w[r][c] = *reinterpret_cast<const WV*>(reinterpret_cast<const _Float16*>(a.wqkv_h) + e);
                 else w[r][c] = *reinterpret_cast<const WV*>(a.wqkv + e);
             }
         }
@@ -612,7 +634,7 @@ __global__ __launch_bounds__(1024) void ar_attn_fused_kernel(ArAttnFusedArgs a) 
     float* stat2 = red;                         // scratch inside `red` (free until the key walk): second-pass sums | raw x, gamma, beta of this head's 64 columns
     float* xh_s = red + NW * G;
     float* gh_s = xh_s + G * 64;
-    float c_mine, d_mine;
+    float c_mine, d_mine, s_mine = 1.f;   // s_mine (int8 weights): the scale of the weight row, on the raw sum before the LayerNorm fix-up
     {
         float s[G];
 #pragma unroll
@@ -641,6 +663,7 @@ __global__ __launch_bounds__(1024) void ar_attn_fused_kernel(ArAttnFusedArgs a) 
         // (the projection took 8 us with fp32 and with fp16 weights alike)
         c_mine = a.ln_cs[(long)(jb >> 6) * D + head * 64 + (jb & 63)];
         d_mine = a.ln_ds[(long)(jb >> 6) * D + head * 64 + (jb & 63)];
+        if constexpr (WT == 2) s_mine = a.wqkv_sc[(long)(jb >> 6) * D + head * 64 + (jb & 63)];
         // second statistics pass: in the shadow of the weight loads, read by the fix-up behind the row loop's closing barrier
         float mean[G];
 #pragma unroll
@@ -671,6 +694,10 @@ __global__ __launch_bounds__(1024) void ar_attn_fused_kernel(ArAttnFusedArgs a) 
     AF_TRACE(1);
     // ---- q/k/v projection of this head (folded form: on x o gamma)
     {
+        auto wel = [](const WV& v, int e) {
+            if constexpr (WT == 2) return (float)i8_at(v, e);
+            else return (float)v[e];
+        };
         auto dot_batch = [&](int bi, const WV (&w)[RB][NCH]) {
             float accp[RB][G];
 #pragma unroll
@@ -686,10 +713,10 @@ __global__ __launch_bounds__(1024) void ar_attn_fused_kernel(ArAttnFusedArgs a) 
 #pragma unroll
                             for (int e4 = 0; e4 < EL; e4 += 4) {
                                 const float4 x4 = *reinterpret_cast<const float4*>(xn_s + g * D + col + e4);
-                                accp[r][g] = fmaf((float)w[r][c][e4 + 0], x4.x, accp[r][g]);
-                                accp[r][g] = fmaf((float)w[r][c][e4 + 1], x4.y, accp[r][g]);
-                                accp[r][g] = fmaf((float)w[r][c][e4 + 2], x4.z, accp[r][g]);
-                                accp[r][g] = fmaf((float)w[r][c][e4 + 3], x4.w, accp[r][g]);
+                                accp[r][g] = fmaf(wel(w[r][c], e4 + 0), x4.x, accp[r][g]);
+                                accp[r][g] = fmaf(wel(w[r][c], e4 + 1), x4.y, accp[r][g]);
+                                accp[r][g] = fmaf(wel(w[r][c], e4 + 2), x4.z, accp[r][g]);
+                                accp[r][g] = fmaf(wel(w[r][c], e4 + 3), x4.w, accp[r][g]);
                             }
                         }
                     }
@@ -751,7 +778,7 @@ __global__ __launch_bounds__(1024) void ar_attn_fused_kernel(ArAttnFusedArgs a) 
 #pragma unroll
                 for (int w = 0; w < NW; ++w) { t1 += stat[w * G + g]; t2 += stat2[w * G + g]; }
                 const float mean = t1 / (float)D, rstd = rsqrtf(t2 / (float)D + a.eps);
-                if (lane < 12) qkv_s[g * 192 + jb] = rstd * (qkv_s[g * 192 + jb] - mean * c_mine) + d_mine;
+                if (lane < 12) qkv_s[g * 192 + jb] = rstd * ((WT == 2 ? qkv_s[g * 192 + jb] * s_mine : qkv_s[g * 192 + jb]) - mean * c_mine) + d_mine;
                 if ((tid >> 6) == g) xn_s[g * D + head * 64 + lane] = (xh_s[g * 64 + lane] - mean) * rstd * gh_s[lane] + gh_s[64 + lane];
             }
         }
@@ -915,7 +942,8 @@ void launch_ar_attn_fused(const ArAttnFusedArgs& a0, hipStream_t s) {
     // SP instantiations only when a layout hides something (density < 1): chunk lists are then always present (context.cpp / the operator entry build both)
     const bool sp = a.vis.has_chunks;
     BG_REQUIRE(sp || !a.vis.has_lay, "fused decode attention: a block layout needs its chunk lists");
-    BG_REQUIRE(pre || !a.wqkv_h || a.D % 8 == 0, "fused decode attention: fp16 weights need D %% 8 == 0");
+    BG_REQUIRE(pre || !a.wqkv_h || a.D % 8 == 0, "fused decode attention: fp16 / int8 weights need D %% 8 == 0");
+    BG_REQUIRE(pre || !a.wqkv_sc || a.wqkv_h, "fused decode attention: int8 row scales without the code matrix");
     // (every argument check is above: a ProfScope whose launch never happens would leave an unrecorded event pair behind)
     ProfScope prof(PROF_DECODE_ATTN, 2.0 * a.H * 64 * eb * ((double)a.B * (n_host - pfx) + (double)(a.B / a.G) * pfx), s, a.ksplit == 1);   // (one launch: events attached to it)
     const int dev_slot = current_device_slot();
@@ -934,6 +962,8 @@ void launch_ar_attn_fused(const ArAttnFusedArgs& a0, hipStream_t s) {
 #undef AP_LAUNCH_G
 #undef AP_LAUNCH
 #undef AP_LAUNCH1
+    } else if (a.wqkv_sc) {
+        if (a.kv_dtype == 0) AF_LAUNCH_G(0, 2); else if (a.kv_dtype == 1) AF_LAUNCH_G(1, 2); else AF_LAUNCH_G(2, 2);
     } else if (a.wqkv_h) {
         if (a.kv_dtype == 0) AF_LAUNCH_G(0, 1); else if (a.kv_dtype == 1) AF_LAUNCH_G(1, 1); else AF_LAUNCH_G(2, 1);
     } else {
@@ -967,7 +997,9 @@ __device__ __forceinline__ float4 ldg_nt4(const float* p) {
 //     rows' arrival and the first MFMA (two barrier rounds + the normalisation: 4.9 us from launch to "A tile staged" against 2.9 us in the MLP-down launch that has no
 //     LayerNorm) - the second pass runs behind the A barrier and mean / rstd only enter the epilogue, with the per-column constants cs = W gamma, ds = W beta + b
 //     (launch_ar_ln_fold, once per layer).
-template <bool LN, int WT, bool RS = false, bool FD = false>   // WT: weight storage of the packed image, 0 fp32 ([K/16][64 lanes][4]), 1 fp16 ([K/32][64 lanes][8]); RS: A is a row source
+// WT = 2 (int8 codes, launch_pack_skinny_weight_i8): the fp16 image's lane map with one byte per element - a wave load is 512 B, lane (r, q) holds the 8 codes of
+//     W[16 tile + r][32 chunk + 8 q .. + 7]; they are widened where the fp16 fragment is used and the column's scale multiplies the summed fp32 accumulator first thing in the epilogue
+template <bool LN, int WT, bool RS = false, bool FD = false>   // WT: weight storage of the packed image, 0 fp32 ([K/16][64 lanes][4]), 1 fp16 ([K/32][64 lanes][8]), 2 int8; RS: A is a row source
 __global__ __launch_bounds__(SF_WAVES * 64) void skinny_fused_kernel(SkinnyFusedArgs g) {
     static_assert(!FD || (LN && !RS), "the folded LayerNorm exists for the plain-A LayerNorm form");
     __shared__ float4 As[256 * 16];
@@ -1041,15 +1073,21 @@ __global__ __launch_bounds__(SF_WAVES * 64) void skinny_fused_kernel(SkinnyFused
     }
     float4 (*gb_s)[256] = reinterpret_cast<float4 (*)[256]>(&red[0][0][0]);   // gamma | beta share the 8 KB of `red` (free until the MFMAs are done)
     // epilogue constants of this thread's output column, requested here: fetched in the epilogue they put one more memory round trip behind the last MFMA
-    float e_bias = 0.f, e_cs = 0.f, e_ds = 0.f;
+    float e_bias = 0.f, e_cs = 0.f, e_ds = 0.f, e_sc = 1.f;
     if (tid < 256) {
         const int col = min(n0 + (tid & 15), g.N - 1);
         if (FD) { e_cs = g.ln_cs[col]; e_ds = g.ln_ds[col]; }
         else if (g.ksplit == 1 && g.bias) e_bias = g.bias[col];
+        if (WT == 2) e_sc = g.w_scale[col];
     }
     float4 wv[WT ? 1 : 8];
-    half8_t wh[WT ? 4 : 1];
-    if (WT) {
+    half8_t wh[WT == 1 ? 4 : 1];
+    u32x2 wq[WT == 2 ? 4 : 1];
+    if (WT == 2) {
+        const char* wp = reinterpret_cast<const char*>(g.Wp) + (((long)blockIdx.x * (g.K >> 5) + ((kbase + wave * kper) >> 5)) * 64 + lane) * 8;
+#pragma unroll
+        for (int u = 0; u < 4; ++u) wq[u] = __builtin_nontemporal_load(reinterpret_cast<const u32x2*>(wp + (long)min(u, (kper >> 5) - 1) * 512));
+    } else if (WT) {
         // fp16 image: one wave load = 1 KiB = a 32-wide k-chunk of the 16 columns; lane (r, q) holds W[16 tile + r][32 chunk + 8 q .. + 7]
         const _Float16* wp = reinterpret_cast<const _Float16*>(g.Wp) + (((long)blockIdx.x * (g.K >> 5) + ((kbase + wave * kper) >> 5)) * 64 + lane) * 8;
 #pragma unroll
@@ -1164,14 +1202,16 @@ __global__ __launch_bounds__(SF_WAVES * 64) void skinny_fused_kernel(SkinnyFused
                 if (32 * u < kper) {   // quarter q owns k = 32 c + 8 q .. + 7 of the chunk: two A float4 (chunks of 4 k), eight MFMAs
                     const int c4 = ((wave * kper + 32 * u) >> 2) + 2 * q;
                     const float4 a0 = FD ? aop[FD ? 2 * u : 0] : As[c4 * 16 + r], a1 = FD ? aop[FD ? 2 * u + 1 : 0] : As[(c4 + 1) * 16 + r];
-                    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a0.x, (float)wh[u][0], acc, 0, 0, 0);
-                    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a0.y, (float)wh[u][1], acc, 0, 0, 0);
-                    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a0.z, (float)wh[u][2], acc, 0, 0, 0);
-                    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a0.w, (float)wh[u][3], acc, 0, 0, 0);
-                    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a1.x, (float)wh[u][4], acc, 0, 0, 0);
-                    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a1.y, (float)wh[u][5], acc, 0, 0, 0);
-                    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a1.z, (float)wh[u][6], acc, 0, 0, 0);
-                    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a1.w, (float)wh[u][7], acc, 0, 0, 0);
+                    // (int8: codes widened straight to fp32, one instruction each like the fp16 fragment's)
+                    auto whu = [&](int e) { return WT == 2 ? (float)i8_at(wq[WT == 2 ? u : 0], e) : (float)wh[WT == 1 ? u : 0][e]; };
+                    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a0.x, whu(0), acc, 0, 0, 0);
+                    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a0.y, whu(1), acc, 0, 0, 0);
+                    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a0.z, whu(2), acc, 0, 0, 0);
+                    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a0.w, whu(3), acc, 0, 0, 0);
+                    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a1.x, whu(4), acc, 0, 0, 0);
+                    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a1.y, whu(5), acc, 0, 0, 0);
+                    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a1.z, whu(6), acc, 0, 0, 0);
+                    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a1.w, whu(7), acc, 0, 0, 0);
                 }
             }
         } else {
@@ -1196,6 +1236,7 @@ __global__ __launch_bounds__(SF_WAVES * 64) void skinny_fused_kernel(SkinnyFused
             float o = 0.f;
 #pragma unroll
             for (int w = 0; w < SF_WAVES; ++w) o += red[w][j][ln];
+            if (WT == 2) o *= e_sc;   // the column's scale: before the LayerNorm fix-up, the bias, GELU and a split-K partial's store
             const int col = n0 + (ln & 15), mo = mc * 16 + 4 * (ln >> 4) + j;
             if (col < g.N && mo < g.M) {
                 if (g.ksplit > 1) {
@@ -1269,7 +1310,7 @@ __device__ __forceinline__ f32x4 mlpf_merge(const f32x4& hi, const f32x4& lo) {
     return o;
 }
 
-template <int WT>   // weight storage of both packed images: 0 fp32, 1 fp16
+template <int WT>   // weight storage of both packed images: 0 fp32, 1 fp16, 2 int8 codes (the fp16 lane map, 512 B per wave load) + row scales
 __global__ __launch_bounds__(SF_WAVES * 64) void ar_mlp_fused_kernel(MlpFusedArgs g) {
     __shared__ float4 As[256 * 16];          // phase 1: the rows [k/4][16 rows] (K = D <= 1024); phase 2: the hidden slice (D / 2 columns)
     __shared__ float4 gm_s[256];             // ln2 gamma
@@ -1305,11 +1346,27 @@ __global__ __launch_bounds__(SF_WAVES * 64) void ar_mlp_fused_kernel(MlpFusedArg
     float e_cs = 0.f, e_ds = 0.f;
     if (tid < 256) { e_cs = g.ln_cs[n0 + (tid & 15)]; e_ds = g.ln_ds[n0 + (tid & 15)]; }
     float4 wv[WT ? 1 : 8];
-    half8_t wh[WT ? 4 : 1];
+    half8_t wh[WT == 1 ? 4 : 1];
+    u32x2 wq[WT == 2 ? 4 : 1];
     float4 dv[WT ? 1 : 8];   // down weights: 2 column tiles x this wave's kper2 = 64 of the slice
-    half8_t dh[WT ? 4 : 1];
+    half8_t dh[WT == 1 ? 4 : 1];
+    u32x2 dq[WT == 2 ? 4 : 1];
     const int t2 = 2 * jx;   // this workgroup's two output column tiles of the down-projection
-    if (WT) {
+    float e_s1 = 1.f, e_s2 = 1.f;   // int8: scales of this thread's hidden column (phase 1, tid < 256) and of its output column of the down-projection (phase 2)
+    if (WT == 2) {
+        if (tid < 256) e_s1 = g.Wup_sc[n0 + (tid & 15)];
+        e_s2 = g.Wdn_sc[(t2 + (tid >> 8)) * 16 + (tid & 15)];
+        const char* wp = reinterpret_cast<const char*>(g.Wup) + (((long)tile * (D >> 5) + ((wave * kper) >> 5)) * 64 + lane) * 8;
+#pragma unroll
+        for (int u = 0; u < 4; ++u) wq[u] = __builtin_nontemporal_load(reinterpret_cast<const u32x2*>(wp + (long)min(u, (kper >> 5) - 1) * 512));
+#pragma unroll
+        for (int t = 0; t < 2; ++t)
+#pragma unroll
+            for (int u = 0; u < 2; ++u) {
+                const char* dp = reinterpret_cast<const char*>(g.Wdn) + (((long)(t2 + t) * (K2 >> 5) + ((xcd * slice + wave * kper2) >> 5) + u) * 64 + lane) * 8;
+                dq[2 * t + u] = __builtin_nontemporal_load(reinterpret_cast<const u32x2*>(dp));
+            }
+    } else if (WT) {
         const _Float16* wp = reinterpret_cast<const _Float16*>(g.Wup) + (((long)tile * (D >> 5) + ((wave * kper) >> 5)) * 64 + lane) * 8;
 #pragma unroll
         for (int u = 0; u < 4; ++u) wh[u] = __builtin_nontemporal_load(reinterpret_cast<const half8_t*>(wp + (long)min(u, (kper >> 5) - 1) * 512));
@@ -1380,7 +1437,7 @@ __global__ __launch_bounds__(SF_WAVES * 64) void ar_mlp_fused_kernel(MlpFusedArg
         f32x4 acc_lo = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int u = 0; u < 4; ++u)
-            if (32 * u < kper) mlpf_mma_f16(aop[2 * u], aop[2 * u + 1], wh[u], acc, acc_lo, bad);
+            if (32 * u < kper) mlpf_mma_f16(aop[2 * u], aop[2 * u + 1], WT == 2 ? i8x8_to_half8(wq[WT == 2 ? u : 0]) : wh[WT == 1 ? u : 0], acc, acc_lo, bad);
         acc = mlpf_merge(acc, acc_lo);
     } else {
 #pragma unroll
@@ -1403,6 +1460,7 @@ __global__ __launch_bounds__(SF_WAVES * 64) void ar_mlp_fused_kernel(MlpFusedArg
         float o = 0.f;
 #pragma unroll
         for (int w = 0; w < SF_WAVES; ++w) o += red[0][w][j][ln];
+        if (WT == 2) o *= e_s1;   // the hidden column's scale, before the LayerNorm fix-up and GELU
         const int rw = 4 * (ln >> 4) + j;
         float t1 = 0.f, t2s = 0.f;
 #pragma unroll
@@ -1492,8 +1550,9 @@ __global__ __launch_bounds__(SF_WAVES * 64) void ar_mlp_fused_kernel(MlpFusedArg
             guard_half8(ah, bad);
 #pragma unroll
             for (int t = 0; t < 2; ++t) {
-                acc2[t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, dh[2 * t + u], acc2[t], 0, 0, 0);
-                acc2_lo[t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(al, dh[2 * t + u], acc2_lo[t], 0, 0, 0);
+                const half8_t dw = WT == 2 ? i8x8_to_half8(dq[WT == 2 ? 2 * t + u : 0]) : dh[WT == 1 ? 2 * t + u : 0];
+                acc2[t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, dw, acc2[t], 0, 0, 0);
+                acc2_lo[t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(al, dw, acc2_lo[t], 0, 0, 0);
             }
         }
 #pragma unroll
@@ -1523,6 +1582,7 @@ __global__ __launch_bounds__(SF_WAVES * 64) void ar_mlp_fused_kernel(MlpFusedArg
         float o = 0.f;
 #pragma unroll
         for (int w = 0; w < SF_WAVES; ++w) o += red[t][w][j][ln];
+        if (WT == 2) o *= e_s2;   // the output column's scale, before the partial plane's store
         const int mo = 16 * mc + 4 * (ln >> 4) + j, col = (t2 + t) * 16 + (ln & 15);
         if (mo < g.M) g.C[((long)xcd * g.M + mo) * D + col] = o;
     }
@@ -1576,12 +1636,16 @@ void launch_ar_mlp_fused(const MlpFusedArgs& g, hipStream_t s) {
     MlpFusedArgs ga = g;
     BG_REQUIRE(mlp_fused_supported(g.M, g.D, g.w_f16 != 0), "ar_mlp_fused: unsupported shape M=%d D=%d (or a device with fewer CUs than workgroups)", g.M, g.D);
     BG_REQUIRE(g.A && g.ln_w && g.ln_cs && g.ln_ds && g.Wup && g.Wdn && g.hidden && g.C && g.sync && g.err && g.lda % 4 == 0, "ar_mlp_fused: missing operand");
+    BG_REQUIRE(g.w_f16 >= 0 && g.w_f16 <= 2 && (g.w_f16 != 2 || (g.Wup_sc && g.Wdn_sc)), "ar_mlp_fused: weight storage %d (0 fp32, 1 fp16, 2 int8 with both scale vectors)", g.w_f16);
     static const int acq_env = getenv("BEVGEN_MLPF_ACQ") ? atoi(getenv("BEVGEN_MLPF_ACQ")) : 1;
     ga.acq = acq_env;
     const dim3 grid(4 * g.D / 16);
     // work = algorithmic bytes: both weight matrices once + rows in, hidden out and back, partial planes out
-    ProfScope prof(PROF_GEMM_SKINNY, 8.0 * g.D * g.D * (g.w_f16 ? 2 : 4) + ((double)g.M * g.D + 2.0 * g.M * 4 * g.D + (double)MLP_FUSED_PLANES * g.M * g.D) * sizeof(float), s, true);
-    if (g.w_f16) {
+    ProfScope prof(PROF_GEMM_SKINNY, 8.0 * g.D * g.D * (g.w_f16 == 2 ? 1 : g.w_f16 ? 2 : 4) + (g.w_f16 == 2 ? 5.0 * g.D * sizeof(float) : 0.0) + ((double)g.M * g.D + 2.0 * g.M * 4 * g.D + (double)MLP_FUSED_PLANES * g.M * g.D) * sizeof(float), s, true);
+    if (g.w_f16 == 2) {
+        if (prof.attached()) hipExtLaunchKernelGGL(ar_mlp_fused_kernel<2>, grid, dim3(SF_WAVES * 64), 0, s, prof.ev_a(), prof.ev_b(), 0, ga);
+        else hipLaunchKernelGGL(ar_mlp_fused_kernel<2>, grid, dim3(SF_WAVES * 64), 0, s, ga);
+    } else if (g.w_f16) {
         if (prof.attached()) hipExtLaunchKernelGGL(ar_mlp_fused_kernel<1>, grid, dim3(SF_WAVES * 64), 0, s, prof.ev_a(), prof.ev_b(), 0, ga);
         else hipLaunchKernelGGL(ar_mlp_fused_kernel<1>, grid, dim3(SF_WAVES * 64), 0, s, ga);
     } else {
@@ -1630,6 +1694,72 @@ void launch_pack_skinny_weight_f16(const float* W, void* Wp, int N, int K, hipSt
     hipLaunchKernelGGL(pack_skinny_weight_f16_kernel, dim3(cdiv(total, 256)), dim3(256), 0, s, W, reinterpret_cast<_Float16*>(Wp), N, K, status_current());
     LAUNCH_CHECK();
 }
+// int8 image and row scales: one wave per row of the image (rows beyond N: zero codes, no scale).  Lane l takes the 8-element groups l, l + 64, ... of the row: group k8
+// of row n = 16 tile + r is lane r + 16 (k8 % 4) of k-chunk k8 / 4 - the fp16 image's lane map, 8 bytes per lane
+__device__ __forceinline__ float row_amax_i8(const float* __restrict__ w, int K, int lane, bool& bad) {
+    float amax = 0.f;
+    bool nf = false;
+    for (int k = lane; k < K; k += 64) { const float v = w[k]; amax = fmaxf(amax, fabsf(v)); nf = nf || nonfinite(v); }
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) amax = fmaxf(amax, __shfl_xor(amax, o, 64));
+    bad = __builtin_amdgcn_ballot_w64(nf) != 0ull;
+    return amax;
+}
+__device__ __forceinline__ int code_i8(float v, float inv) { return (int)fminf(fmaxf(rintf(__fmul_rn(v, inv)), -127.f), 127.f); }
+__global__ __launch_bounds__(256) void pack_skinny_weight_i8_kernel(const float* __restrict__ W, unsigned* __restrict__ Wp, float* __restrict__ scales, int N, int K,
+                                                                    unsigned* __restrict__ status) {
+    const int lane = threadIdx.x & 63, n = blockIdx.x * 4 + (threadIdx.x >> 6);   // (n < 16 cdiv(N, 16): the grid is exact)
+    const bool real = n < N;
+    const float* w = W + (long)(real ? n : 0) * K;
+    bool bad;
+    const float amax = row_amax_i8(w, K, lane, bad);
+    const bool zero = !real || !(amax >= 1e-30f);
+    const float inv = zero ? 0.f : __fdiv_rn(127.f, amax);
+    if (real && lane == 0) scales[n] = zero ? 0.f : __fdiv_rn(amax, 127.f);
+    if (real && bad && lane == 0) status_raise(status, BG_ST_F16_RANGE);
+    for (int k8 = lane; k8 < (K >> 3); k8 += 64) {
+        unsigned lo = 0, hi = 0;
+        if (!zero) {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                lo |= ((unsigned)code_i8(w[8 * k8 + e], inv) & 0xFFu) << (8 * e);
+                hi |= ((unsigned)code_i8(w[8 * k8 + 4 + e], inv) & 0xFFu) << (8 * e);
+            }
+        }
+        const long at = (((long)(n >> 4) * (K >> 5) + (k8 >> 2)) * 64 + (n & 15) + 16 * (k8 & 3)) * 2;
+        Wp[at] = lo; Wp[at + 1] = hi;
+    }
+}
+size_t skinny_packed_bytes_i8(int N, int K) { return (size_t)cdiv(N, 16) * 16 * K; }
+void launch_pack_skinny_weight_i8(const float* W, void* Wp, float* scales, int N, int K, hipStream_t s) {
+    BG_REQUIRE(K % 32 == 0 && N >= 1, "pack_skinny_weight_i8: K=%d must be a multiple of 32", K);
+    hipLaunchKernelGGL(pack_skinny_weight_i8_kernel, dim3(cdiv(N, 16) * 4), dim3(256), 0, s, W, reinterpret_cast<unsigned*>(Wp), scales, N, K, status_current());
+    LAUNCH_CHECK();
+}
+// the quantiser alone: codes row-major, scales, dequantised values (`dequant` may be W itself: a lane reads its element before it writes it, and the row's maximum is
+// complete - a wave-wide exchange - before the first write)
+__global__ __launch_bounds__(256) void quantize_rows_i8_kernel(const float* W, signed char* __restrict__ codes, float* __restrict__ scales, float* dequant, int N, int K,
+                                                               unsigned* __restrict__ status) {
+    const int lane = threadIdx.x & 63, n = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (n >= N) return;   // (wave-uniform)
+    const float* w = W + (long)n * K;
+    bool bad;
+    const float amax = row_amax_i8(w, K, lane, bad);
+    const bool zero = !(amax >= 1e-30f);
+    const float sc = zero ? 0.f : __fdiv_rn(amax, 127.f), inv = zero ? 0.f : __fdiv_rn(127.f, amax);
+    if (scales && lane == 0) scales[n] = sc;
+    if (bad && lane == 0) status_raise(status, BG_ST_F16_RANGE);
+    for (int k = lane; k < K; k += 64) {
+        const int c = zero ? 0 : code_i8(w[k], inv);
+        if (codes) codes[(long)n * K + k] = (signed char)c;
+        if (dequant) dequant[(long)n * K + k] = __fmul_rn((float)c, sc);
+    }
+}
+void launch_quantize_rows_i8(const float* W, int N, int K, void* codes, float* scales, float* dequant, hipStream_t s) {
+    BG_REQUIRE(W && N >= 1 && K >= 1, "quantize_rows_i8: bad arguments");
+    hipLaunchKernelGGL(quantize_rows_i8_kernel, dim3(cdiv(N, 4)), dim3(256), 0, s, W, reinterpret_cast<signed char*>(codes), scales, dequant, N, K, status_current());
+    LAUNCH_CHECK();
+}
 size_t skinny_packed_floats(int N, int K) { return (size_t)cdiv(N, 16) * 16 * K; }
 void launch_pack_skinny_weight(const float* W, float* Wp, int N, int K, hipStream_t s) {
     BG_REQUIRE(K % 16 == 0, "pack_skinny_weight: K=%d must be a multiple of 16", K);
@@ -1657,8 +1787,9 @@ void launch_skinny_fused(const SkinnyFusedArgs& g0, hipStream_t s) {
     const bool fd = g.ln_cs != nullptr;
     BG_REQUIRE(!fd || (ln && !rs && g.ln_ds && g.K <= 1024), "skinny_fused: the folded LayerNorm needs the plain-A LayerNorm form and both row constants");
     dim3 grid(cdiv(g.N, 16), g.ksplit);
-    if (g.w_f16) BG_REQUIRE((g.K / g.ksplit) % (SF_WAVES * 32) == 0, "skinny_fused: fp16 weights need a K slice that is a multiple of %d (K=%d, ksplit=%d)", SF_WAVES * 32, g.K, g.ksplit);
-    ProfScope prof(PROF_GEMM_SKINNY, (double)g.N * g.K * (g.w_f16 ? 2 : 4) + ((double)g.M * g.K + (double)g.M * g.N) * sizeof(float), s, !rs || g.M <= 16);   // work = algorithmic bytes; one launch: events attached to it
+    if (g.w_f16) BG_REQUIRE((g.K / g.ksplit) % (SF_WAVES * 32) == 0, "skinny_fused: fp16 / int8 weights need a K slice that is a multiple of %d (K=%d, ksplit=%d)", SF_WAVES * 32, g.K, g.ksplit);
+    BG_REQUIRE(g.w_f16 >= 0 && g.w_f16 <= 2 && (g.w_f16 != 2 || g.w_scale), "skinny_fused: weight storage %d (0 fp32, 1 fp16, 2 int8 with its row scales)", g.w_f16);
+    ProfScope prof(PROF_GEMM_SKINNY, (double)g.N * g.K * (g.w_f16 == 2 ? 1 : g.w_f16 ? 2 : 4) + (g.w_f16 == 2 ? (double)g.N * sizeof(float) : 0.0) + ((double)g.M * g.K + (double)g.M * g.N) * sizeof(float), s, !rs || g.M <= 16);   // work = algorithmic bytes; one launch: events attached to it
 #define SF_LAUNCH(K, ARGS) do { if (prof.attached()) hipExtLaunchKernelGGL(K, grid, dim3(SF_WAVES * 64), 0, s, prof.ev_a(), prof.ev_b(), 0, ARGS); \
                                 else hipLaunchKernelGGL(K, grid, dim3(SF_WAVES * 64), 0, s, ARGS); } while (0)
     if (rs) {   // 16 rows per launch
@@ -1670,9 +1801,14 @@ void launch_skinny_fused(const SkinnyFusedArgs& g0, hipStream_t s) {
             h.src.partial += (long)m0 * g.src.pld;   // (aliases base when there are no partials: any valid address will do)
             h.C = g.C + (long)m0 * g.ldc;
             if (g.xn_out) h.xn_out = g.xn_out + (long)m0 * g.ldxn;
-            if (g.w_f16) SF_LAUNCH((skinny_fused_kernel<true, 1, true>), h);
+            if (g.w_f16 == 2) SF_LAUNCH((skinny_fused_kernel<true, 2, true>), h);
+            else if (g.w_f16) SF_LAUNCH((skinny_fused_kernel<true, 1, true>), h);
             else SF_LAUNCH((skinny_fused_kernel<true, 0, true>), h);
         }
+    } else if (g.w_f16 == 2) {
+        if (ln && fd) SF_LAUNCH((skinny_fused_kernel<true, 2, false, true>), g);
+        else if (ln) SF_LAUNCH((skinny_fused_kernel<true, 2>), g);
+        else SF_LAUNCH((skinny_fused_kernel<false, 2>), g);
     } else if (g.w_f16) {
         if (ln && fd) SF_LAUNCH((skinny_fused_kernel<true, 1, false, true>), g);
         else if (ln) SF_LAUNCH((skinny_fused_kernel<true, 1>), g);

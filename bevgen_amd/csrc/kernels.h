@@ -283,6 +283,7 @@ struct ArAttnFusedArgs {
     const float* xn = nullptr;         //   and x / ln_w / wqkv are not read
     const float* wqkv = nullptr;       // fused [3D, D] (q | k | v), bqkv [3D]
     const void* wqkv_h = nullptr;      // non-null: the same matrix stored as fp16 (decode_weights = f16), read instead of wqkv
+    const float* wqkv_sc = nullptr;    // non-null (decode_weights = i8): wqkv_h holds int8 codes [3D, D] row-major and this the [3D] row scales (launch_quantize_rows_i8)
     const float* bqkv = nullptr;
     const float *ln_cs = nullptr, *ln_ds = nullptr;   // [3D] each: W gamma and W beta + b of the fused matrix (launch_ar_ln_fold): the fused kernel folds ln1 into its projection
     void* kcache = nullptr;            // this layer's [B, H, Lmax, 64]
@@ -320,7 +321,8 @@ struct SkinnyFusedArgs {
     const float *ln_w = nullptr, *ln_b = nullptr; float eps = 1e-5f;   // ln_w != null: LayerNorm over K fused in front of the product
     const float *ln_cs = nullptr, *ln_ds = nullptr;   // [N] each, non-null (plain A + LayerNorm): W gamma and W beta + bias (launch_ar_ln_fold) - the LayerNorm is folded into the product, `bias` is not read
     const float* Wp = nullptr;               // [N, K] weights in the packed operand layout (launch_pack_skinny_weight / _f16)
-    int w_f16 = 0;                           // the packed image holds fp16 values
+    int w_f16 = 0;                           // storage of the packed image: 0 fp32, 1 fp16 values, 2 int8 codes (launch_pack_skinny_weight_i8) with one fp32 scale per row of W:
+    const float* w_scale = nullptr;          //   [N], multiplied into the fp32 accumulator before anything else touches it
     const float* bias = nullptr;       // [N] (ksplit == 1 only)
     float* C = nullptr; int ldc = 0;   // [M, N], or the partial sums [ksplit][M][N] when ksplit > 1
     int M = 0, N = 0, K = 0, ksplit = 0 /* 0 = skinny_fused_ksplit(N, K) */, act = 0;
@@ -341,7 +343,8 @@ struct MlpFusedArgs {
     float eps = 1e-5f;
     const float* Wup = nullptr;                        // packed operand image of the up matrix [4 D, D]
     const float* Wdn = nullptr;                        // packed operand image of the down matrix [D, 4 D]
-    int w_f16 = 0;
+    int w_f16 = 0;                                     // storage of both images: 0 fp32, 1 fp16, 2 int8 codes with the row scales below
+    const float *Wup_sc = nullptr, *Wdn_sc = nullptr;  // int8: [4 D] and [D] row scales of the two matrices
     float* hidden = nullptr;                           // [M][4 D] scratch (the GELU output, exchanged through L2)
     float* C = nullptr;                                // [8][M][D] partial sums of the down-projection
     unsigned* sync = nullptr;                          // mlp_fused_sync_words() words of device memory, zeroed once (barrier state per XCD + placement check)
@@ -357,6 +360,14 @@ void launch_ar_mlp_fused(const MlpFusedArgs& g, hipStream_t s);
 size_t skinny_packed_floats(int N, int K);
 void launch_pack_skinny_weight(const float* W, float* Wp, int N, int K, hipStream_t s);
 void launch_pack_skinny_weight_f16(const float* W, void* Wp /* N16 * K halves */, int N, int K, hipStream_t s);
+// int8 decode weights: one scale per row of W [N, K], the rule of kv_i8_quant (common.h) applied to the row - amax = max |w|; amax < 1e-30 -> codes 0, scale 0; else
+// scale = amax / 127, code = clamp(rint(w * (127 / amax)), -127, 127), value = code * scale; IEEE fp32 throughout (torch on the CPU gives the same bytes).  A row holding a
+// NaN / inf raises BG_ST_F16_RANGE like the fp16 packer.  The quantiser is idempotent - the dequantised row quantises to the same codes and scale (checked for every fp32
+// mantissa: tests/test_decode_w_i8_cpu.py) - so images packed from a matrix that was already replaced by its dequantised values are the images of the original.
+size_t skinny_packed_bytes_i8(int N, int K);   // the int8 image: N rounded up to 16, K codes per row
+void launch_pack_skinny_weight_i8(const float* W, void* Wp /* int8 image in the lane map of the fp16 image */, float* scales /* [N] */, int N, int K, hipStream_t s);
+void launch_quantize_rows_i8(const float* W, int N, int K, void* codes /* [N, K] int8 row-major, or null */, float* scales /* [N] or null */, float* dequant /* [N, K] or null; may be W */,
+                             hipStream_t s);
 size_t ar_attn_fused_max_lds();   // LDS bytes a workgroup may allocate on the current device
 size_t ar_attn_lds_bytes(int G, int Lpad);   // the attention-only kernel (decode_path = split)
 void launch_skinny_fused(const SkinnyFusedArgs& g, hipStream_t s);

@@ -46,7 +46,9 @@ struct ArLayer {
     float *wqkv, *bqkv;  // fused [3D, D], [3D], owned
     const float *mlp0_w, *mlp0_b, *mlp2_w, *mlp2_b;
     float *mlp0_wp = nullptr, *mlp2_wp = nullptr;   // decode-step operand images of the MLP weights (owned; fused decode path; fp32 or fp16 packed)
-    void* wqkv_h = nullptr;                          // decode_weights = f16: fp16 copy of the fused QKV weight [3D, D]
+    void* wqkv_h = nullptr;                          // decode_weights = f16: fp16 copy of the fused QKV weight [3D, D]; i8: its int8 codes, row-major
+    // decode_weights = i8: one fp32 scale per row of each projection matrix (owned); the images above then hold int8 codes
+    float *wqkv_sc = nullptr, *mlp0_sc = nullptr, *mlp2_sc = nullptr;
     float *mlp0_cs = nullptr, *mlp0_ds = nullptr;    // the same for ln2 in front of the MLP up-projection (skinny_fused_kernel<.., FD>)
     float *ln1_cs = nullptr, *ln1_ds = nullptr;      // fused decode kernel: ln1 folded into the projection - W gamma and W beta + b of the fused QKV matrix (launch_ar_ln_fold)
     float* wqkv_wp = nullptr;                        // decode_path = split: operand image of the fused QKV weight (packed like the MLP images)
@@ -85,6 +87,7 @@ struct Ctx {
     // ---- Route A
     std::vector<ArLayer> ar;
     float* head_wp = nullptr;      // packed head.weight (fused decode path)
+    float* head_sc = nullptr;      // decode_weights = i8: its [V] row scales
     // visibility = element mask x block layout (kernels.h SparseVis): one [L, L] byte plane + per layer (or shared) block layouts and key-chunk lists
     uint8_t* allowed = nullptr;    // [L, L]
     uint8_t* lay = nullptr;        // [keep_layers, Hk, nb, nb]

@@ -16,7 +16,9 @@ option is: a key next to the ``_target_`` (``+model.transformer.kv_cache=f16`` o
     weights         $BEVGEN_WEIGHTS          f32 | f16              f32     (f16: GEMM / conv matrices rounded once at load, two MFMAs per product)
     kv_cache        $BEVGEN_KV_CACHE         f32 | f16 | i8         f32     (Route A; f16 = fp16 storage / fp32 accumulate: BASELINE config 4; i8 = opt-in, lossy: int8
                                                                             codes + one fp32 scale per (token, head) row, fp32 accumulate)
-    decode_weights  $BEVGEN_DECODE_WEIGHTS   f32 | f16              f32     (Route A decode step streams 2-byte q/k/v, MLP and head weights)
+    decode_weights  $BEVGEN_DECODE_WEIGHTS   f32 | f16 | i8         f32     (Route A; f16 = the decode step streams 2-byte q/k/v, MLP and head weights, rounded once at load;
+                                                                            i8 = opt-in, lossy: int8 codes + one fp32 scale per output row, 1-byte weights in the decode step;
+                                                                            prefill, scoring and decode run the one quantised model; not together with weights=f16)
     decode_path     $BEVGEN_DECODE_PATH      auto | fused | split | per_op   auto
 
 Precedence: explicit constructor key > environment variable > default.  A key given to an outer module (``Net2NetTransformer``) is handed down to the
@@ -31,7 +33,7 @@ CHOICES = {
     "precision": ("fp32", "f16x3", "f16x3r", "f16x1"),
     "weights": ("f32", "f16"),
     "kv_cache": ("f32", "f16", "i8"),
-    "decode_weights": ("f32", "f16"),
+    "decode_weights": ("f32", "f16", "i8"),
     "decode_path": ("auto", "fused", "split", "per_op"),
 }
 ENV = {"precision": "BEVGEN_PRECISION", "weights": "BEVGEN_WEIGHTS", "kv_cache": "BEVGEN_KV_CACHE", "decode_weights": "BEVGEN_DECODE_WEIGHTS",

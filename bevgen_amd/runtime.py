@@ -17,6 +17,20 @@ from . import _lib, tables
 from ._lib import bevgen_cfg
 from .weights import ff_inner_dim
 
+# Route A projection-weight storage of the decode step: the `decode_weights` choice -> bevgen_cfg.decode_weight_dtype (BEVGEN_W_*)
+DECODE_WEIGHTS = {"f32": _lib.W_F32, "f16": _lib.W_F16, "i8": _lib.W_I8}
+
+
+def decode_weight_dtype(route: str, weights: str, decode_weights: str) -> int:
+    """bevgen_cfg.decode_weight_dtype of a Context, or ValueError: an unknown choice, or Route A with weights='f16' and decode_weights='i8' (the library refuses the
+    pair at bevgen_finalize as well)."""
+    if decode_weights not in DECODE_WEIGHTS:
+        raise ValueError(f"decode_weights must be one of {tuple(DECODE_WEIGHTS)}, got {decode_weights!r}")
+    if route == "ar" and weights == "f16" and decode_weights == "i8":
+        raise ValueError("weights='f16' cannot be combined with decode_weights='i8': the dequantised int8 matrices are not fp16-representable, "
+                         "so prefill and decode could not run one model")
+    return DECODE_WEIGHTS[decode_weights]
+
 
 def _ptr(t: Optional[torch.Tensor]):
     return None if t is None else C.c_void_p(t.data_ptr())
@@ -70,7 +84,7 @@ class Context:
         decode_path = decode_path or os.environ.get("BEVGEN_DECODE_PATH") or "auto"
         decode_weights = decode_weights or os.environ.get("BEVGEN_DECODE_WEIGHTS") or "f32"
         for key, val, ok in (("kv_cache", kv_cache, ("f32", "f16", "i8")), ("decode_path", decode_path, ("auto", "fused", "split", "per_op")),
-                             ("decode_weights", decode_weights, ("f32", "f16"))):
+                             ("decode_weights", decode_weights, tuple(DECODE_WEIGHTS))):
             if val not in ok:
                 raise ValueError(f"{key} must be one of {ok}, got {val!r}")
         if precision not in ("fp32", "f16x3", "f16x3r", "f16x1"):
@@ -92,8 +106,9 @@ class Context:
         c.decode_path = {"fused": _lib.DECODE_FUSED, "per_op": _lib.DECODE_PER_OP, "split": _lib.DECODE_SPLIT, "auto": _lib.DECODE_AUTO}[decode_path]
         self.decode_path = decode_path
         # Route A projection weights: 'f32', or 'f16' = the model with fp16-representable q/k/v, MLP and head weights (rounded at finalize), whose decode
-        # step streams 2-byte weights
-        c.decode_weight_dtype = {"f32": _lib.W_F32, "f16": _lib.W_F16}[decode_weights]
+        # step streams 2-byte weights, or 'i8' (opt-in, lossy) = the model whose projection weights are int8 codes x one fp32 scale per output row (quantised at
+        # finalize; prefill, scoring and decode run that one model), whose decode step streams 1-byte weights
+        # (bevgen_cfg.decode_weight_dtype is set below, once `weights` is known: decode_weight_dtype())
         self.decode_weights = decode_weights
         # Route A fused decode step: number of independent sequence groups enqueued on separate streams (0 = the library's choice; $BEVGEN_DECODE_CHAINS)
         c.decode_chains = int(os.environ.get("BEVGEN_DECODE_CHAINS", "0")) if decode_chains is None else int(decode_chains)
@@ -101,6 +116,7 @@ class Context:
         weights = weights or os.environ.get("BEVGEN_WEIGHTS") or "f32"
         if weights not in ("f32", "f16"):
             raise ValueError(f"weights must be 'f32' or 'f16', got {weights!r}")
+        c.decode_weight_dtype = decode_weight_dtype(route, weights, decode_weights)
         c.weight_dtype = {"f32": _lib.W_F32, "f16": _lib.W_F16}[weights]
         self.weights = weights
         if cfg is not None:
@@ -589,8 +605,18 @@ class Context:
                                                C.byref(ks), self._s()))
         return out[0] if ks.value == 1 else out[:ks.value].sum(0)
 
+    def op_quantize_rows_i8(self, w, dequant=True):
+        """The row quantiser of decode_weights='i8' alone: w [N, K] fp32 -> (codes [N, K] int8, scales [N] fp32, code * scale [N, K] fp32 or None)."""
+        N, K = w.shape
+        codes = torch.empty((N, K), dtype=torch.int8, device=self.device)
+        scales = torch.empty((N,), dtype=torch.float32, device=self.device)
+        deq = torch.empty((N, K), dtype=torch.float32, device=self.device) if dequant else None
+        self._check(self.lib.bevgen_op_quantize_rows_i8(self._h, _ptr(w), N, K, _ptr(codes), _ptr(scales), _ptr(deq), self._s()))
+        return codes, scales, deq
+
     def op_mlp_fused(self, x, ln_w, ln_b, w1, b1, w2, b2, w_f16=False, eps=1e-5):
-        """Both MLP projections of a Route A decode layer in one launch: Linear2(GELU(Linear1(LayerNorm(x)))) for M <= 64 rows, without the residual."""
+        """Both MLP projections of a Route A decode layer in one launch: Linear2(GELU(Linear1(LayerNorm(x)))) for M <= 64 rows, without the residual.
+        w_f16: False / 0 fp32 weights, True / 1 rounded to fp16, 2 int8 codes with row scales (decode_weights='i8')."""
         M, D = x.shape
         out = torch.empty((M, D), dtype=torch.float32, device=self.device)
         self._check(self.lib.bevgen_op_mlp_fused(self._h, _ptr(x), _ptr(ln_w), _ptr(ln_b), float(eps), _ptr(w1), _ptr(b1), _ptr(w2), _ptr(b2), int(w_f16), _ptr(out), M, D, self._s()))
@@ -725,7 +751,8 @@ class Context:
 
     def op_ar_attn_fused(self, x, ln_w, ln_b, wqkv, bqkv, kcache, vcache, n, *, partial=None, rbias=None, bias=None, attn_mask=None, layout=None, block=1, G=1, prefix=0,
                          kv_dtype=0, w_f16=False, split=False, Lmax=None):
-        """Attention half of a fused Route A decode layer (appends k/v to cache row n-1 in place) -> x2 [B, D].  kv_dtype 2: flat uint8 caches + an explicit Lmax."""
+        """Attention half of a fused Route A decode layer (appends k/v to cache row n-1 in place) -> x2 [B, D].  kv_dtype 2: flat uint8 caches + an explicit Lmax.
+        w_f16: False / 0 fp32 projection weights, True / 1 rounded to fp16, 2 int8 codes with row scales (decode_weights='i8')."""
         B, D = x.shape
         H = D // 64
         Lmax = self._cache_lmax(kcache, kv_dtype, Lmax)

@@ -52,7 +52,9 @@ enum { BEVGEN_PRECISION_FP32 = 0, BEVGEN_PRECISION_BF16 = 1 /* reserved */, BEVG
  * back is code_i * scale.  Every finite row is representable (no range refusal); a NaN / inf in a row raises BEVGEN_STATUS_KV_NONFINITE. */
 enum { BEVGEN_KV_F32 = 0, BEVGEN_KV_F16 = 1, BEVGEN_KV_I8 = 2 };
 enum { BEVGEN_DECODE_FUSED = 0, BEVGEN_DECODE_PER_OP = 1, BEVGEN_DECODE_SPLIT = 2, BEVGEN_DECODE_AUTO = 3 };
-enum { BEVGEN_W_F32 = 0, BEVGEN_W_F16 = 1 };
+/* BEVGEN_W_I8 (decode_weight_dtype only): int8 codes with one fp32 scale per output row of a projection matrix W [N, K] - the quantiser of the int8 KV cache above applied
+ * to the row W[n, :] (amax over the row; amax < 1e-30: codes 0, scale 0; scale = amax / 127, code = clamp(rint(w * (127 / amax)), -127, 127), value = code * scale). */
+enum { BEVGEN_W_F32 = 0, BEVGEN_W_F16 = 1, BEVGEN_W_I8 = 2 };
 enum { BEVGEN_DTYPE_F32 = 0, BEVGEN_DTYPE_I64 = 1, BEVGEN_DTYPE_U8 = 2, BEVGEN_DTYPE_F64 = 3 };
 
 enum {
@@ -123,7 +125,12 @@ typedef struct bevgen_cfg {
                                                           decode_weight_dtype = BEVGEN_W_F16 FUSED at every batch size: its single MLP launch makes it the faster form, 0.71 vs 0.83) */
     int32_t decode_weight_dtype;                       /* Route A projection weights (q/k/v, MLP, head): BEVGEN_W_F32 (default) or BEVGEN_W_F16: bevgen_finalize rounds them to
                                                           fp16-representable values (prefill and decode then use the same model: the reference's Route A runs fp16,
-                                                          sparse_self_attention.py:127) and the decode step streams the 2-byte copies: half the weight traffic */
+                                                          sparse_self_attention.py:127) and the decode step streams the 2-byte copies: half the weight traffic; or
+                                                          BEVGEN_W_I8: bevgen_finalize replaces them by code * scale (int8 codes, one fp32 scale per output row; the
+                                                          fused q | k | v matrix row by row, i.e. per row of each [D, D] matrix) - prefill, bevgen_ar_forward and decode
+                                                          run that one model - and the decode step streams the 1-byte codes, with the row scale applied to the fp32
+                                                          accumulator.  Both need a fused-like decode_path and dim % 256 == 0; BEVGEN_W_I8 excludes weight_dtype =
+                                                          BEVGEN_W_F16 (dequantised values are not fp16-representable) */
     int32_t weight_dtype;                              /* every matrix that feeds a split-precision GEMM / convolution (needs BEVGEN_PRECISION_F16X3): BEVGEN_W_F32
                                                           (default: hi + lo f16 planes, three MFMAs per product, fp32-class results on the fp32 weights) or BEVGEN_W_F16:
                                                           bevgen_finalize rounds those matrices to f16 once (the reference's own GPU runs cast them to bf16 / fp16 on
@@ -377,11 +384,15 @@ int bevgen_op_layernorm_planes(bevgen_ctx* ctx, const float* d_x, int ldx, const
                                int geglu, void* stream);
 /* Decode-step projection (decode_fused.hip): C = act(LayerNorm?(A) W^T + bias) for M <= 64 rows; d_ln_w NULL = no LayerNorm; ksplit > 1 (no LayerNorm, no bias / act):
  * d_c receives the split-K partial sums [ksplit, M, N] that the consumer adds; ksplit 0 = the library's choice for (N, K), returned through *ksplit_out if non-NULL;
- * ksplit -1 (LayerNorm with beta and bias): one K slice, the LayerNorm folded into the product the way the decode step launches ln2 + MLP-up. */
+ * ksplit -1 (LayerNorm with beta and bias): one K slice, the LayerNorm folded into the product the way the decode step launches ln2 + MLP-up.
+ * On a context created with decode_weight_dtype = BEVGEN_W_I8 the operator quantises d_w and runs the int8 image (the result is that of the dequantised matrix). */
 int bevgen_op_ln_gemm(bevgen_ctx* ctx, const float* d_a, const float* d_ln_w, const float* d_ln_b, float eps, const float* d_w, const float* d_bias, float* d_c,
                       int M, int N, int K, int act_gelu, int ksplit, int* ksplit_out, void* stream);
+/* The row quantiser of BEVGEN_W_I8 alone: d_w [N, K] fp32 -> d_codes [N, K] int8 row-major, d_scales [N], and (d_dequant non-NULL) the values code * scale [N, K]. */
+int bevgen_op_quantize_rows_i8(bevgen_ctx* ctx, const float* d_w, int N, int K, void* d_codes, float* d_scales, float* d_dequant /* or NULL */, void* stream);
 /* Both MLP projections of a Route-A decode layer in one launch (decode_fused.hip ar_mlp_fused_kernel; Block.forward's mlp(ln2(x)), transformer/mingpt_sparse.py:232-253):
- * d_out [M, D] = Linear2(GELU(Linear1(LayerNorm(d_x)))) WITHOUT the residual, M <= 64, D = 1024; w_f16: the matrices are rounded to fp16 first (decode_weights = f16).
+ * d_out [M, D] = Linear2(GELU(Linear1(LayerNorm(d_x)))) WITHOUT the residual, M <= 64, D = 1024; w_f16 = 1: the matrices are rounded to fp16 first (decode_weights = f16);
+ * w_f16 = 2: quantised to int8 codes with row scales (decode_weights = i8: the result is that of the dequantised matrices).
  * Returns BEVGEN_ERR_INVALID where the launch is not supported (shape, or a device with fewer CUs than its 4 D / 16 workgroups). */
 int bevgen_op_mlp_fused(bevgen_ctx* ctx, const float* d_x, const float* d_ln_w, const float* d_ln_b, float eps, const float* d_w1 /*[4D, D]*/, const float* d_b1,
                         const float* d_w2 /*[D, 4D]*/, const float* d_b2, int w_f16, float* d_out, int M, int D, void* stream);
@@ -430,7 +441,8 @@ int bevgen_op_decode_attention(bevgen_ctx* ctx, const float* d_q, const void* d_
  *   k, v written to cache row n-1 -> softmax(dh^-0.5 (q k^T + d_bias[n-1, :]) + mask) v over keys 0..n-1 -> d_out[b] = xn + attention.
  * Visibility as the reference defines it: d_attn_mask [L, L] fp32 (0 = hidden) AND d_layout int64 [H, L/block, L/block] (0 = block absent, never read);
  * either may be NULL.  G > 1: consecutive groups of G sequences share their first `prefix` keys, read from the group's first cache slot.
- * kv_dtype 0 fp32 / 1 fp16 cache [B, H, Lmax, 64]; w_f16 != 0: the projection weights are rounded to fp16 and streamed as 2-byte values.
+ * kv_dtype 0 fp32 / 1 fp16 cache [B, H, Lmax, 64]; w_f16 = 1: the projection weights are rounded to fp16 and streamed as 2-byte values;
+ * w_f16 = 2: quantised to int8 codes with one scale per row (BEVGEN_W_I8) and streamed as 1-byte values.
  * split = 0: the fused kernel as the sampling path launches it (G = 1: leading K/V steps of the key walk staged in LDS by LDS-DMA); split = -1: without staged pieces.
  * split > 0: the BEVGEN_DECODE_SPLIT form of the same computation (LayerNorm + QKV projection kernel, then the attention-only kernel); split = k > 1: with the
  * key walk of every (sequence, head) cut into k ranges on k workgroups and merged by the combine kernel (what one- and two-sequence calls run; G = 1). */

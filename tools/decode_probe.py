@@ -1,6 +1,6 @@
 #!/usr/bin/env python
 """Route A decode probe: BASELINE config 4 (L=2368, 24 layers), B sequences, `steps` greedy steps through the hipGraph path.
-usage: decode_probe.py [B] [steps] [paths=fused,per_op] [kv=f32,f16 (or i8)] [samples_per_layout=1] [weights=f32] [precision=fp32 (prefill arithmetic: fp32 | f16x3)]"""
+usage: decode_probe.py [B] [steps] [paths=fused,per_op] [kv=f32,f16 (or i8)] [samples_per_layout=1] [weights=f32 (f32 | f16 | i8, comma-separated)] [precision=fp32 (prefill arithmetic: fp32 | f16x3)]"""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
