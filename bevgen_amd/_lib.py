@@ -63,8 +63,10 @@ SIGNATURES = {
     "bevgen_set_tables": (_i, [_p, _p, _p, _p, _p, _p]),
     "bevgen_finalize": (_i, [_p]),
     "bevgen_muse_forward": (_i, [_p, _p, _p, _p, _p, _i, _p, _p, _p]),
+    "bevgen_muse_forward_ex": (_i, [_p, _p, _p, _p, _p, _i, _p, _p, _i, _p]),
     "bevgen_maskgit_generate": (_i, [_p, _p, _p, _p, _i, _i, C.POINTER(C.c_int32), _f, _i, _f, _p, _p, _p, _p, C.c_uint64, _p]),
     "bevgen_maskgit_generate_ex": (_i, [_p, _p, _p, _p, _i, _i, C.POINTER(C.c_int32), _f, _i, _f, _p, _p, _p, _p, C.c_uint64, _i, _i, _p]),
+    "bevgen_maskgit_generate_guided": (_i, [_p, _p, _p, _p, _i, _i, C.POINTER(C.c_int32), _f, _i, _f, _p, _p, _p, _p, C.c_uint64, _i, _i, _f, _p]),
     "bevgen_maskgit_loss": (_i, [_p, _p, _p, _p, _p, _i, C.POINTER(C.c_int32), _p, _p, _f, C.c_uint64, _i, _f, _p, _p, _p, _p, _p]),
     "bevgen_op_maskgit_train_mask": (_i, [_p, _p, _p, _p, _i, _i, C.c_int64, C.c_uint64, _p, _p, _p]),
     "bevgen_op_masked_ce": (_i, [_p, _p, _i, _p, _p, _l, _i, _l, _p, _p, _p]),
@@ -86,6 +88,8 @@ SIGNATURES = {
     "bevgen_op_muse_qkv": (_i, [_p, _i, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _f, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p]),
     "bevgen_op_muse_ff": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p]),
     "bevgen_op_layernorm_planes": (_i, [_p, _p, _i, _p, _p, _p, _i, _i, _i, _i, _p]),
+    "bevgen_op_add_row_layernorm": (_i, [_p, _p, _i, _p, _p, _p, _i, _i, _i, _i, _p]),
+    "bevgen_op_cfg_combine": (_i, [_p, _p, _i, _p, _i, _l, _i, _f, _p]),
     "bevgen_op_ln_gemm": (_i, [_p, _p, _p, _p, _f, _p, _p, _p, _i, _i, _i, _i, _i, C.POINTER(_i), _p]),
     "bevgen_op_quantize_rows_i8": (_i, [_p, _p, _i, _i, _p, _p, _p, _p]),
     "bevgen_op_mlp_fused": (_i, [_p, _p, _p, _p, _f, _p, _p, _p, _p, _i, _p, _i, _i, _p]),

@@ -135,11 +135,16 @@ int bevgen_finalize(bevgen_ctx* ctx) {
 }
 
 int bevgen_muse_forward(bevgen_ctx* ctx, const int64_t* ids, const int64_t* cond, const float* I_inv, const float* E_inv, int B, float* logits, float* embed, void* stream) {
+    return bevgen_muse_forward_ex(ctx, ids, cond, I_inv, E_inv, B, logits, embed, 0, stream);
+}
+
+int bevgen_muse_forward_ex(bevgen_ctx* ctx, const int64_t* ids, const int64_t* cond, const float* I_inv, const float* E_inv, int B, float* logits, float* embed,
+                           int null_condition, void* stream) {
     return guarded(ctx, [&] {
         need_final(ctx);
         BG_REQUIRE(ids && cond && I_inv && E_inv, "muse_forward: null input");
         BG_REQUIRE(B >= 1 && (ctx->cfg.max_batch <= 0 || B <= ctx->cfg.max_batch), "muse_forward: batch %d exceeds max_batch %d", B, ctx->cfg.max_batch);
-        muse_forward(*ctx, MuseBatch{cond, I_inv, E_inv, B}, ids, logits, embed, (hipStream_t)stream);
+        muse_forward(*ctx, MuseBatch{cond, I_inv, E_inv, B}, ids, logits, embed, (hipStream_t)stream, null_condition != 0);
     });
 }
 
@@ -152,7 +157,15 @@ int bevgen_maskgit_generate(bevgen_ctx* ctx, const int64_t* cond, const float* I
 int bevgen_maskgit_generate_ex(bevgen_ctx* ctx, const int64_t* cond, const float* I_inv, const float* E_inv, int B, int timesteps, const int32_t* sched, float temperature,
                                int topk_k, float critic_noise_scale, const float* gumbel_u, const float* critic_u, const int64_t* init_ids, int64_t* out,
                                unsigned long long noise_seed, int score_mode, int samples_per_layout, void* stream) {
+    return bevgen_maskgit_generate_guided(ctx, cond, I_inv, E_inv, B, timesteps, sched, temperature, topk_k, critic_noise_scale, gumbel_u, critic_u, init_ids, out, noise_seed,
+                                          score_mode, samples_per_layout, 1.f, stream);
+}
+
+int bevgen_maskgit_generate_guided(bevgen_ctx* ctx, const int64_t* cond, const float* I_inv, const float* E_inv, int B, int timesteps, const int32_t* sched, float temperature,
+                                   int topk_k, float critic_noise_scale, const float* gumbel_u, const float* critic_u, const int64_t* init_ids, int64_t* out,
+                                   unsigned long long noise_seed, int score_mode, int samples_per_layout, float cond_scale, void* stream) {
     return guarded(ctx, [&] {
+        BG_REQUIRE(cond_scale == cond_scale && cond_scale - cond_scale == 0.f, "maskgit_generate: cond_scale must be finite");
         need_final(ctx);
         BG_REQUIRE(cond && I_inv && E_inv && out && sched, "maskgit_generate: null argument");
         BG_REQUIRE(B >= 1 && (ctx->cfg.max_batch <= 0 || B <= ctx->cfg.max_batch), "maskgit_generate: batch %d exceeds max_batch %d", B, ctx->cfg.max_batch);
@@ -160,7 +173,7 @@ int bevgen_maskgit_generate_ex(bevgen_ctx* ctx, const int64_t* cond, const float
         for (int i = 0; i < timesteps; ++i)
             BG_REQUIRE(sched[i] >= 1 && sched[i] <= ctx->cfg.cam_latent_h * ctx->cfg.cam_latent_w, "maskgit_generate: mask_schedule[%d]=%d out of range", i, sched[i]);
         BG_REQUIRE(samples_per_layout >= 1 && B % samples_per_layout == 0, "maskgit_generate: batch %d is not a multiple of samples_per_layout %d", B, samples_per_layout);
-        const MaskgitSampling sp{timesteps, sched, temperature, topk_k, critic_noise_scale, gumbel_u, critic_u, init_ids, noise_seed, score_mode};
+        const MaskgitSampling sp{timesteps, sched, temperature, topk_k, critic_noise_scale, gumbel_u, critic_u, init_ids, noise_seed, score_mode, cond_scale};
         maskgit_generate(*ctx, MuseBatch{cond, I_inv, E_inv, B, samples_per_layout}, sp, out, (hipStream_t)stream);
     });
 }
@@ -668,6 +681,20 @@ int bevgen_op_mean_fixed_order(bevgen_ctx* ctx, const float* x, long n, float* o
 
 int bevgen_op_layernorm(bevgen_ctx* ctx, const float* x, const float* gamma, const float* beta, float* y, int rows, int D, float eps, void* stream) {
     return guarded(ctx, [&] { launch_layernorm(x, D, gamma, beta, y, D, rows, D, eps, (hipStream_t)stream); });
+}
+
+int bevgen_op_add_row_layernorm(bevgen_ctx* ctx, float* x, int ldx, const float* r, const float* gamma, void* y, int ldy, int rows, int D, int planes, void* stream) {
+    return guarded(ctx, [&] {
+        BG_REQUIRE(x && r && gamma && y && rows >= 1 && D >= 1, "op_add_row_layernorm: bad arguments");
+        launch_add_row_layernorm(x, ldx, r, gamma, y, ldy, rows, D, 1e-5f, planes != 0, (hipStream_t)stream);
+    });
+}
+
+int bevgen_op_cfg_combine(bevgen_ctx* ctx, float* cond, int ldc, const float* null_logits, int ldn, long rows, int V, float cond_scale, void* stream) {
+    return guarded(ctx, [&] {
+        BG_REQUIRE(cond && null_logits && rows >= 1 && V >= 1, "op_cfg_combine: bad arguments");
+        launch_cfg_combine(cond, ldc, null_logits, ldn, rows, V, cond_scale, (hipStream_t)stream);
+    });
 }
 
 int bevgen_op_geglu_layernorm(bevgen_ctx* ctx, const float* h, const float* gamma, float* y, int rows, int F, int ldy, void* stream) {

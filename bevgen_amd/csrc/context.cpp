@@ -254,6 +254,10 @@ static void finalize_muse(Ctx& c) {
         }
     }
     c.split_weight(c.pf(p + "to_logits.weight"), (long)g.vocab_size * D, true);
+    // the null-condition pass: what every layer's cross-attention block adds when no layout token is visible (after split_weight: a mode that rounds to_out computes the
+    // row from the rounded matrix, the one its model multiplies by); null_kv [2, H, 1, 64]: the value half
+    c.null_rows = reinterpret_cast<float*>(c.own((size_t)g.num_layers * D * sizeof(float)));
+    for (int i = 0; i < g.num_layers; ++i) launch_muse_null_row(c.muse[i].to_out[1], c.muse[i].null_kv[1] + inner, c.null_rows + (size_t)i * D, D, inner, 0);
     // attention bias matrices with the null-key column
     c.NkS_pad = (int)round_up(c.N + 1, 32);
     c.NkC_pad = (int)round_up(c.K + 1, 32);

@@ -138,6 +138,9 @@ void launch_geglu_layernorm(const float* h, int ldh, const float* gamma, float* 
 // Same two, writing the interleaved (hi, lo) f16 plane image [row][ldy/32][2][32] that the LDS-DMA split-precision GEMM reads (ldy % 32 == 0)
 void launch_layernorm_planes(const float* x, int ldx, const float* gamma, const float* beta, void* planes, int ldy, int rows, int D, float eps, hipStream_t s);
 void launch_geglu_layernorm_planes(const float* h, int ldh, const float* gamma, void* planes, int ldy, int rows, int F, float eps, hipStream_t s);
+// x[row, :] += r[:] (written back to x), then y[row, :] = LayerNorm(x[row, :]) * gamma, as fp32 rows or (planes) as the plane image above: the bits of an fp32 add
+// followed by launch_layernorm / launch_layernorm_planes.  D % 4 == 0; Route M's null-condition pass (muse.cpp)
+void launch_add_row_layernorm(float* x, int ldx, const float* r, const float* gamma, void* y, int ldy, int rows, int D, float eps, bool planes, hipStream_t s);
 // GroupNorm(32 groups, eps) statistics over NHWC [n, hw, C] -> stats[n*32*2] = (mean, rstd)
 size_t groupnorm_ws_bytes(int n, int hw);
 // decoder tail: GroupNorm(32)-apply + swish + 3x3 convolution C -> 3 + denormalise + NCHW (fp32 y or uint8 y8) in one kernel (x NHWC fp32, wgt [3][3][3][C])
@@ -406,6 +409,9 @@ void launch_maskgit_pick(int64_t* ids, const float* logits, int ldl, const float
 // Self-critic scores (muse_net:392-396, 602-611): scores = embed . w + b + ((u - 0.5) * noise_scale) * frac
 void launch_critic_scores(const float* embed, int lde, const float* w, const float* b, const float* u /*or null*/, float noise_scale, float frac,
                           float* scores, int rows, int D, hipStream_t s, unsigned long long seed = 0, unsigned iter = 0);
+// Classifier-free guidance (muse_net:272-276): cond[row, 0:V] = null + (cond - null) * scale in place, three separately rounded fp32 operations (sub, mul, add; no FMA);
+// columns [V, ldc) of cond are not touched
+void launch_cfg_combine(float* cond, int ldc, const float* null_logits, int ldn, long rows, int V, float scale, hipStream_t s);
 void launch_philox_fill(float* out, long n, unsigned long long seed, unsigned iter, unsigned stream, int V /* stream 0: vocabulary size (row layout) */, hipStream_t s);
 // Route A token pick (ar_lm:204-219): logits/temperature, top-k (ties kept), softmax, argmax or inverse-CDF draw with explicit u
 //   forced [steps, rows] (or null): entries >= 0 are emitted instead of a drawn token (partial decoding, ar_lm:161-165,181-182)

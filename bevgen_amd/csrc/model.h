@@ -83,6 +83,7 @@ struct Ctx {
     float *bias_self = nullptr, *bias_cross = nullptr;  // [N, ldS] / [N, ldC] with the null-key column and masks baked in
     float *bias_self_pk = nullptr, *bias_cross_pk = nullptr;  // the same two matrices as packed images for attention_split (launch_pack_attn_bias)
     int ldS = 0, ldC = 0, NkS_pad = 0, NkC_pad = 0;
+    float* null_rows = nullptr;   // [layers, D]: r_i = to_out_i vec(null_v_i) of every layer's cross-attention - what that block adds to every row in the null-condition pass (launch_muse_null_row)
 
     // ---- Route A
     std::vector<ArLayer> ar;
@@ -207,8 +208,9 @@ struct MaskgitSampling {   // bevgen_maskgit_generate_ex's sampling arguments (b
     int timesteps; const int32_t* sched; float temperature; int topk_k; float critic_noise_scale;
     const float *gumbel_u, *critic_u; const int64_t* init_ids;
     unsigned long long noise_seed = 0; int score_mode = 0;   // 0 token critic, 1 / 2 softmax confidence (muse_net:611-622)
+    float cond_scale = 1.f;   // != 1: classifier-free guidance, logits = null + (cond - null) * cond_scale with the null-condition pass (bevgen_maskgit_generate_guided)
 };
-void muse_forward(Ctx& c, const MuseBatch& in, const int64_t* ids, float* logits, float* embed, hipStream_t s);
+void muse_forward(Ctx& c, const MuseBatch& in, const int64_t* ids, float* logits, float* embed, hipStream_t s, bool null_condition = false);
 void maskgit_generate(Ctx& c, const MuseBatch& in, const MaskgitSampling& sp, int64_t* out, hipStream_t s);
 struct MaskgitLoss {   // bevgen_maskgit_loss's arguments behind the batch (bevgen_hip.h)
     const int32_t* h_num_masked; const float *perm_u, *gumbel_u; float temperature; unsigned long long noise_seed; int with_critic; float critic_loss_weight;
@@ -279,5 +281,6 @@ void launch_relayout_conv_weight(const float* w_oihw, float* w_ohwi, int cout, i
 void launch_fuse_qkv(const float* wq, const float* wk, const float* wv, const float* bq, const float* bk, const float* bv, float* w, float* b, int D, hipStream_t s);
 void launch_pad_rows(const float* src, int ld_src, float* dst, int ld_dst, int rows, int cols, hipStream_t s);
 void launch_fill_i64(int64_t* p, long n, int64_t v, hipStream_t s);
+void launch_muse_null_row(const float* to_out /* [D, inner] */, const float* null_v /* [inner] */, float* r /* [D] */, int D, int inner, hipStream_t s);
 
 }  // namespace bevgen

@@ -8,7 +8,8 @@
 //   * cross-attention K/V of every layer (to_kv(context) + l2norm)    (context is never updated)
 //   * the attention-bias matrices                                     (built once in bevgen_finalize)
 // and what is dropped: the classifier-free-guidance "null" forwards (bit-identical to the conditional ones in eval mode,
-// muse_net:352) and the critic forward after the last iteration (its scores are never read).
+// muse_net:352) and the critic forward after the last iteration (its scores are never read).  Opt-in guidance (MaskgitSampling::cond_scale != 1) adds a REAL null pass
+// per iteration - context_mask all false - in which a layer's cross-attention block is the constant row c.null_rows[i] (muse_blocks, null_condition).
 //
 // A forward (muse_blocks) is the token embedding, the layers in ONE of two precisions - muse_blocks_f32, the exact-fp32 path, or muse_blocks_split, the f16x3 path on
 // (hi, lo) f16 planes - and the final LayerNorm.  Every LDS-DMA projection of the split path ends in project(), which executes the decision of muse_plan.h.
@@ -24,12 +25,14 @@ struct MuseWs {
     int S = 1;   // samples per BEV layout: consecutive groups of S scenes share their condition, whose cross-attention K / V exist once per layout
     bool generate = false;   // the call also needs logits and scores
     bool loss = false;       // MaskGit.forward's losses: logits, the masked ids / mask / counts and one value per token row
+    bool guided = false;     // generate with classifier-free guidance: a second logits buffer for the null-condition pass
 
     long rows = 0;
     float *img = nullptr, *c_embed = nullptr, *context = nullptr;
     int64_t* cond_g = nullptr; float* c_embed_g = nullptr;   // S > 1: the first scene of every group as contiguous [G, ...] inputs of the condition side
     std::vector<float*> crossK, crossV;
     float *logits = nullptr, *scores = nullptr;   // generate only (logits: loss too)
+    float* logits_null = nullptr;                 // guided generate only
     int64_t* loss_x = nullptr; uint8_t* loss_mask = nullptr; int* loss_n = nullptr; float* loss_rows = nullptr;   // loss only: x [rows], mask [rows], n [B * cams], nll / bce [rows]
     float *x = nullptr, *xn = nullptr, *qraw = nullptr, *kvraw = nullptr, *Q = nullptr, *Ks = nullptr, *Vs = nullptr, *att = nullptr, *h = nullptr, *g = nullptr;
     size_t kvS = 0, kvC = 0;   // elements of one self- / cross-attention K (or V) buffer: B (or B / S) x H x Nk_pad x 64
@@ -224,12 +227,14 @@ void cross_attention_split(Fwd& f, const MuseLayer& l, int i) {
     project(f, PROJ_OUT, on_planes(w.att, D, gemm_args(c, {l.to_out[1], D}, {w.x, D}, rows, D, D, {w.x, D})), f.fold == 2 ? &f.prod_x : nullptr);
 }
 
-// x += W4 LayerNorm(GEGLU(W1 LayerNorm(x))) (muse_net:78-88); `last`: no layer follows
-void feed_forward_split(Fwd& f, const MuseLayer& l, bool last) {
+// x += W4 LayerNorm(GEGLU(W1 LayerNorm(x))) (muse_net:78-88); `last`: no layer follows.  `null_row` (null-condition pass, fold <= 1): x += null_row first, in the
+// launch of the first LayerNorm - the whole cross-attention block of that pass
+void feed_forward_split(Fwd& f, const MuseLayer& l, bool last, const float* null_row = nullptr) {
     const Ctx& c = f.c;
     MuseWs& w = f.w;
     const int D = c.D, rows = f.rows, fold = f.fold;
-    if (fold != 2) launch_layernorm_planes(w.x, D, l.ff_g0, nullptr, w.xn, D, rows, D, 1e-5f, f.s);
+    if (null_row) launch_add_row_layernorm(w.x, D, null_row, l.ff_g0, w.xn, D, rows, D, 1e-5f, true, f.s);
+    else if (fold != 2) launch_layernorm_planes(w.x, D, l.ff_g0, nullptr, w.xn, D, rows, D, 1e-5f, f.s);
     if (l.ff_w1_geglu) {
         // GEGLU in the up-projection's epilogue: h = gate * gelu(x) as [rows, Fpad] (pad columns exactly 0), then the LayerNorm half on its own - or (fold >= 1)
         // folded away: the epilogue writes the raw planes of h and its row statistics, the down-projection multiplies by W4 o gamma
@@ -254,22 +259,25 @@ void feed_forward_split(Fwd& f, const MuseLayer& l, bool last) {
 }
 
 // the layers in split precision (f16x3; f16x1 and weights = f16 are this path with other weight planes)
-void muse_blocks_split(const Ctx& c, MuseWs& w, hipStream_t s) {
+void muse_blocks_split(const Ctx& c, MuseWs& w, hipStream_t s, bool null_condition) {
     Fwd f{c, w, s, (int)w.rows, w.B, c.N, muse_switches()};
     f.fold = muse_fold_level(f.sw, !c.muse.empty() && c.muse[0].fold_w4);
+    // (the null-condition pass adds a row to x between the self-attention's output projection and the feed-forward's first LayerNorm: planes and statistics that
+    // projection would produce at fold level 2 describe the row before the add, so that pass runs at level <= 1)
+    if (null_condition) f.fold = std::min(f.fold, 1);
     f.tile_merge = muse_tile_merge(f.sw, f.rows);
     f.prod_x.out_planes = w.xn; f.prod_x.out_stats = w.stats_d; f.prod_x.out_ld = c.D;
     const int layers = c.cfg.num_layers;
     for (int i = 0; i < layers; ++i) {
         const MuseLayer& l = c.muse[i];
         self_attention_split(f, l);
-        cross_attention_split(f, l, i);
-        feed_forward_split(f, l, i + 1 == layers);
+        if (!null_condition) cross_attention_split(f, l, i);
+        feed_forward_split(f, l, i + 1 == layers, null_condition ? c.null_rows + (size_t)i * c.D : nullptr);
     }
 }
 
-// the layers in exact fp32: sixteen launches per layer
-void muse_blocks_f32(const Ctx& c, MuseWs& w, hipStream_t s) {
+// the layers in exact fp32: sixteen launches per layer (null-condition pass: eleven - the cross-attention block and the LayerNorm behind it are one launch)
+void muse_blocks_f32(const Ctx& c, MuseWs& w, hipStream_t s, bool null_condition) {
     const int D = c.D, H = c.H, B = w.B, N = c.N, F = c.F, Fpad = c.Fpad, rows = (int)w.rows;
     AttnArgs self{};
     self.Q = w.Q; self.K = w.Ks; self.V = w.Vs; self.bias = c.bias_self; self.R = nullptr; self.O = w.att;
@@ -292,15 +300,20 @@ void muse_blocks_f32(const Ctx& c, MuseWs& w, hipStream_t s) {
         launch_muse_kv_prep(w.kvraw, l.null_kv[0], l.k_scale[0], w.Ks, w.Vs, B, H, N, c.NkS_pad, s);
         launch_attention(self, s);
         gemm({w.att, D}, gemm_args(c, {l.to_out[0], D}, {w.x, D}, rows, D, D, {w.x, D}), s);   // x = to_out(att) + x
-        // ---- cross attention
-        launch_layernorm(w.x, D, l.norm_g[1], nullptr, w.xn, D, rows, D, 1e-5f, s);
-        gemm({w.xn, D}, gemm_args(c, {l.to_q[1], D}, {w.qraw, D}, rows, D, D), s);
-        launch_muse_q_prep(w.qraw, l.q_scale[1], w.Q, B, H, N, s);
-        cross.K = w.crossK[i]; cross.V = w.crossV[i];
-        launch_attention(cross, s);
-        gemm({w.att, D}, gemm_args(c, {l.to_out[1], D}, {w.x, D}, rows, D, D, {w.x, D}), s);
-        // ---- feed forward
-        launch_layernorm(w.x, D, l.ff_g0, nullptr, w.xn, D, rows, D, 1e-5f, s);
+        if (null_condition) {
+            // ---- cross attention over no visible key (x += r_i) and the feed-forward's first LayerNorm
+            launch_add_row_layernorm(w.x, D, c.null_rows + (size_t)i * D, l.ff_g0, w.xn, D, rows, D, 1e-5f, false, s);
+        } else {
+            // ---- cross attention
+            launch_layernorm(w.x, D, l.norm_g[1], nullptr, w.xn, D, rows, D, 1e-5f, s);
+            gemm({w.xn, D}, gemm_args(c, {l.to_q[1], D}, {w.qraw, D}, rows, D, D), s);
+            launch_muse_q_prep(w.qraw, l.q_scale[1], w.Q, B, H, N, s);
+            cross.K = w.crossK[i]; cross.V = w.crossV[i];
+            launch_attention(cross, s);
+            gemm({w.att, D}, gemm_args(c, {l.to_out[1], D}, {w.x, D}, rows, D, D, {w.x, D}), s);
+            // ---- feed forward
+            launch_layernorm(w.x, D, l.ff_g0, nullptr, w.xn, D, rows, D, 1e-5f, s);
+        }
         gemm({w.xn, D}, gemm_args(c, {l.ff_w1, D}, {w.h, 2 * F}, rows, 2 * F, D), s);
         launch_geglu_layernorm(w.h, 2 * F, l.ff_g3, w.g, Fpad, rows, F, 1e-5f, s);
         gemm({w.g, Fpad}, gemm_args(c, {l.ff_w4_padded, Fpad}, {w.x, D}, rows, D, Fpad, {w.x, D}), s);
@@ -343,6 +356,7 @@ void muse_layout(const Ctx& c, MuseWs& w, Arena& a) {
         w.crossV[i] = a.get<float>(w.kvC);
     }
     w.logits = w.generate || w.loss ? a.get<float>((size_t)w.rows * c.V) : nullptr;
+    w.logits_null = w.guided ? a.get<float>((size_t)w.rows * c.V) : nullptr;
     w.scores = w.generate ? a.get<float>((size_t)w.rows) : nullptr;
     w.loss_x = w.loss ? a.get<int64_t>((size_t)w.rows) : nullptr;
     w.loss_mask = w.loss ? a.get<uint8_t>((size_t)w.rows) : nullptr;
@@ -351,7 +365,7 @@ void muse_layout(const Ctx& c, MuseWs& w, Arena& a) {
 }
 
 // per-batch constants: the workspace, the tensors used by name, embeddings + cross-attention K/V
-void muse_prepare(Ctx& c, MuseWs& w, const MuseBatch& in, bool generate, hipStream_t s, bool loss = false) {
+void muse_prepare(Ctx& c, MuseWs& w, const MuseBatch& in, bool generate, hipStream_t s, bool loss = false, bool guided = false) {
     const auto& g = c.cfg;
     const std::string p = "transformer.";
     const int B = in.B, S = in.samples_per_layout < 1 ? 1 : in.samples_per_layout;
@@ -361,6 +375,7 @@ void muse_prepare(Ctx& c, MuseWs& w, const MuseBatch& in, bool generate, hipStre
     w.B = B;
     w.generate = generate;
     w.loss = loss;
+    w.guided = guided;
     w.rows = (long)B * c.N;
     c.arena.carve([&](Arena& a) { muse_layout(c, w, a); });
     w.token_emb = c.pf(p + "token_emb.weight"); w.pos_emb = c.pf(p + "pos_emb.weight");
@@ -405,23 +420,25 @@ void muse_prepare(Ctx& c, MuseWs& w, const MuseBatch& in, bool generate, hipStre
     }
 }
 
-// one transformer pass over the current ids: leaves LayerNorm(x) (= `embed`, muse_net:202) in w.xn.  The two precisions share the token embedding and the final LayerNorm
-void muse_blocks(const Ctx& c, MuseWs& w, const int64_t* ids, hipStream_t s) {
+// one transformer pass over the current ids: leaves LayerNorm(x) (= `embed`, muse_net:202) in w.xn.  The two precisions share the token embedding and the final LayerNorm.
+// null_condition: the pass with context_mask = False for every scene (muse_net:158-166, 352-356: what a dropped condition is) - each layer's cross-attention block is
+// x += c.null_rows[i], fused into the feed-forward's first LayerNorm (launch_add_row_layernorm); everything else is the same launches
+void muse_blocks(const Ctx& c, MuseWs& w, const int64_t* ids, hipStream_t s, bool null_condition = false) {
     const int D = c.D, rows = (int)w.rows;
     launch_token_embed(ids, w.token_emb, w.img, w.pos_emb, w.x, w.B, c.N, D, c.cfg.vocab_size + 1, s);
-    if (c.cfg.precision == BEVGEN_PRECISION_F16X3) muse_blocks_split(c, w, s);
-    else muse_blocks_f32(c, w, s);
+    if (c.cfg.precision == BEVGEN_PRECISION_F16X3) muse_blocks_split(c, w, s, null_condition);
+    else muse_blocks_f32(c, w, s, null_condition);
     launch_layernorm(w.x, D, w.norm_g, nullptr, w.xn, D, rows, D, 1e-5f, s);
 }
 
 }  // namespace
 
-void muse_forward(Ctx& c, const MuseBatch& in, const int64_t* ids, float* logits, float* embed, hipStream_t s) {
+void muse_forward(Ctx& c, const MuseBatch& in, const int64_t* ids, float* logits, float* embed, hipStream_t s, bool null_condition) {
     BG_REQUIRE(c.cfg.route == BEVGEN_ROUTE_MASKGIT, "context was not created for the MaskGit route");
     BG_REQUIRE(in.B >= 1, "batch must be positive");
     MuseWs w;
     muse_prepare(c, w, in, false, s);
-    muse_blocks(c, w, ids, s);
+    muse_blocks(c, w, ids, s, null_condition);
     const int rows = (int)w.rows;
     if (embed) HIP_CHECK(hipMemcpyAsync(embed, w.xn, (size_t)rows * c.D * sizeof(float), hipMemcpyDeviceToDevice, s));
     if (logits) gemm({w.xn, c.D}, gemm_args(c, {w.to_logits, c.D}, {logits, c.V}, rows, c.V, c.D), s);
@@ -433,8 +450,9 @@ void maskgit_generate(Ctx& c, const MuseBatch& in, const MaskgitSampling& sp, in
     BG_REQUIRE(in.B >= 1 && timesteps >= 1 && sp.sched, "bad generate arguments");
     BG_REQUIRE(score_mode != 0 || c.find("token_critic.to_pred.weight"), "maskgit_generate: the context holds no token critic (token_critic.to_pred.*): use score_mode 1 / 2");
     BG_REQUIRE(score_mode >= 0 && score_mode <= 2, "score_mode %d: 0 token critic, 1 softmax confidence, 2 softmax confidence with re-masking of earlier tokens", score_mode);
+    const bool guided = sp.cond_scale != 1.f;   // (scale 1 is the conditional logits: the launches of an unguided call)
     MuseWs w;
-    muse_prepare(c, w, in, true, s);
+    muse_prepare(c, w, in, true, s, false, guided);
     const int rows = (int)w.rows;            // B*C*T token rows
     const int seqs = in.B * c.cfg.num_cams;  // rows of the [B*C, T] id matrix
     const int T = c.T, V = c.V, D = c.D;
@@ -449,11 +467,16 @@ void maskgit_generate(Ctx& c, const MuseBatch& in, const MaskgitSampling& sp, in
         launch_remask(ids, scores, sp.init_ids, seqs, T, sp.sched[step], mask_id, s);
         muse_blocks(c, w, ids, s);
         gemm({w.xn, D}, gemm_args(c, {w.to_logits, D}, {logits, V}, rows, V, D), s);
+        if (guided) {   // the null-condition pass over the same ids; from here on `logits` holds null + (cond - null) * cond_scale (top-k filter, pick and confidence scores)
+            muse_blocks(c, w, ids, s, true);
+            gemm({w.xn, D}, gemm_args(c, {w.to_logits, D}, {w.logits_null, V}, rows, V, D), s);
+            launch_cfg_combine(logits, V, w.logits_null, V, rows, V, sp.cond_scale, s);
+        }
         // score_mode 1 / 2 (force_not_use_token_critic, muse_net:611-622): the scores come out of the pick itself (1 - softmax(logits)[pred]) and the critic forward
         // is not run at all - 18 transformer forwards per call instead of 35
         launch_maskgit_pick(ids, logits, V, sp.gumbel_u ? sp.gumbel_u + (size_t)step * rows * V : nullptr, rows, V, sp.topk_k, (float)((double)sp.temperature * frac), mask_id, s,
                             sp.noise_seed, (unsigned)step, score_mode ? scores : nullptr, score_mode);
-        if (score_mode == 0 && step + 1 < timesteps) {  // the critic scores only select what the NEXT iteration re-masks
+        if (score_mode == 0 && step + 1 < timesteps) {  // the critic scores only select what the NEXT iteration re-masks (guided too: the critic reads the conditional embed, muse_net:394-396)
             muse_blocks(c, w, ids, s);
             launch_critic_scores(w.xn, D, w.critic_w, w.critic_b, sp.critic_u ? sp.critic_u + (size_t)step * rows : nullptr, sp.critic_noise_scale, (float)frac, scores, rows, D, s,
                                  sp.noise_seed, (unsigned)step);

@@ -36,14 +36,15 @@ constexpr int LN_MAXV = 12;  // float4 per lane -> D <= 3072
 
 // PLANES: y is the interleaved (hi, lo) f16 plane image [row][ldy/32][2][32] read by the split-precision GEMM (gemm_split.hip) instead of fp32
 // MAXV: float4 per lane the instantiation holds (4: rows up to 1024 wide - 16 row registers instead of 48, eight waves per SIMD instead of five)
-template <bool PLANES, int MAXV = LN_MAXV>
-__global__ __launch_bounds__(256) void layernorm_vec_kernel(const float* __restrict__ x, int ldx, const float* __restrict__ gamma, const float* __restrict__ beta,
-                                                            float* __restrict__ y, int ldy, int rows, int D, float eps, unsigned* __restrict__ status) {
+// The row body of layernorm_vec_kernel and add_row_layernorm_kernel (one wave per row).  ADD: the row is first updated as x[row, :] += radd[:] (plain fp32 adds, written
+// back to x; D % 4 == 0) and the LayerNorm is taken of the updated row - the same instructions behind the add as the plain kernel runs on a row that already holds the sum,
+// hence the same bits.  radd: the added row as float4 (LDS)
+template <bool PLANES, int MAXV, bool ADD>
+__device__ __forceinline__ void layernorm_vec_row(const float* x /* (ADD: written too) */, int ldx, const float* __restrict__ gamma, const float* __restrict__ beta, float* __restrict__ y,
+                                                  int ldy, int row, int D, float eps, unsigned* __restrict__ status, const float4* radd) {
     // D need not be a multiple of 4 (Route M: LayerNorm over F = 2730 columns of a row padded to 2752): the last vector of a row is then partly
     // padding - read (the row storage is ldx >= round_up(D, 4) wide), excluded from the statistics, written as zero.
     const int lane = threadIdx.x & 63;
-    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (row >= rows) return;
     const float4* xr = reinterpret_cast<const float4*>(x + (long)row * ldx);
     const int nv = (D + 3) >> 2;
     float4 v[MAXV];
@@ -52,6 +53,11 @@ __global__ __launch_bounds__(256) void layernorm_vec_kernel(const float* __restr
     for (int j = 0; j < MAXV; ++j) {
         const int i = lane + 64 * j;
         v[j] = i < nv ? xr[i] : make_float4(0.f, 0.f, 0.f, 0.f);
+        if (ADD && i < nv) {
+            const float4 a = radd[i];
+            v[j] = make_float4(__fadd_rn(v[j].x, a.x), __fadd_rn(v[j].y, a.y), __fadd_rn(v[j].z, a.z), __fadd_rn(v[j].w, a.w));
+            reinterpret_cast<float4*>(const_cast<float*>(x) + (long)row * ldx)[i] = v[j];
+        }
         if (4 * i + 3 >= D) {   // boundary / padding vector: elements at columns >= D do not exist
             if (4 * i + 0 >= D) v[j].x = 0.f;
             if (4 * i + 1 >= D) v[j].y = 0.f;
@@ -132,6 +138,47 @@ __global__ __launch_bounds__(256) void layernorm_vec_kernel(const float* __restr
         }
     }
     if (PLANES && bad) status_raise(status, BG_ST_F16_RANGE);
+}
+
+template <bool PLANES, int MAXV = LN_MAXV>
+__global__ __launch_bounds__(256) void layernorm_vec_kernel(const float* __restrict__ x, int ldx, const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                            float* __restrict__ y, int ldy, int rows, int D, float eps, unsigned* __restrict__ status) {
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= rows) return;
+    layernorm_vec_row<PLANES, MAXV, false>(x, ldx, gamma, beta, y, ldy, row, D, eps, status, nullptr);
+}
+
+// x[row, :] += r[:] (written back), y = LayerNorm(x[row, :]) gamma: the null-condition pass of Route M (muse.cpp), where a layer's cross-attention block adds the same
+// row r to every token and the feed-forward's first LayerNorm follows.  r is read once per workgroup (into LDS), every access is 16 bytes wide.
+// `beta` is a launch argument (null in every launch) and not a constant of the instantiation on purpose: with a known-null beta the compiler contracts the output
+// product into the hi / lo split of the plane writer (fma(a, gamma, -hi): the lo plane of an UNROUNDED product), which layernorm_vec_kernel, whose beta is a run-time
+// value, cannot do - the two kernels would differ in the last bit of the lo plane
+template <bool PLANES, int MAXV>
+__global__ __launch_bounds__(256) void add_row_layernorm_kernel(float* x, int ldx, const float* __restrict__ r, const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                                float* __restrict__ y, int ldy, int rows, int D, float eps, unsigned* __restrict__ status) {
+    __shared__ float4 rs[64 * MAXV];
+    for (int i = threadIdx.x; i < (D >> 2); i += 256) rs[i] = reinterpret_cast<const float4*>(r)[i];
+    __syncthreads();
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= rows) return;
+    layernorm_vec_row<PLANES, MAXV, true>(x, ldx, gamma, beta, y, ldy, row, D, eps, status, rs);
+}
+
+void launch_add_row_layernorm(float* x, int ldx, const float* r, const float* gamma, void* y, int ldy, int rows, int D, float eps, bool planes, hipStream_t s) {
+    if (rows <= 0) return;
+    BG_REQUIRE(D % 4 == 0 && D <= 256 * LN_MAXV && ldx % 4 == 0 && ldx >= D && ldy >= D && ldy <= 256 * LN_MAXV && ldy % (planes ? 32 : 4) == 0 &&
+                   (reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(gamma) | reinterpret_cast<uintptr_t>(r)) % 16 == 0,
+               "add_row_layernorm: unsupported shape D=%d ldx=%d ldy=%d", D, ldx, ldy);
+    const dim3 grid(cdiv(rows, 4)), block(256);
+    float* yf = reinterpret_cast<float*>(y);
+    unsigned* st = planes ? status_current() : nullptr;
+    const float* beta = nullptr;
+    const bool small = D <= 1024 && ldy <= 1024;   // (the instantiation launch_layernorm / launch_layernorm_planes pick for the same shape)
+    if (planes && small) hipLaunchKernelGGL((add_row_layernorm_kernel<true, 4>), grid, block, 0, s, x, ldx, r, gamma, beta, yf, ldy, rows, D, eps, st);
+    else if (planes) hipLaunchKernelGGL((add_row_layernorm_kernel<true, LN_MAXV>), grid, block, 0, s, x, ldx, r, gamma, beta, yf, ldy, rows, D, eps, st);
+    else if (small) hipLaunchKernelGGL((add_row_layernorm_kernel<false, 4>), grid, block, 0, s, x, ldx, r, gamma, beta, yf, ldy, rows, D, eps, st);
+    else hipLaunchKernelGGL((add_row_layernorm_kernel<false, LN_MAXV>), grid, block, 0, s, x, ldx, r, gamma, beta, yf, ldy, rows, D, eps, st);
+    LAUNCH_CHECK();
 }
 
 void launch_layernorm(const float* x, int ldx, const float* gamma, const float* beta, float* y, int ldy, int rows, int D, float eps, hipStream_t s) {

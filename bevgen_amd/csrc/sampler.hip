@@ -516,6 +516,44 @@ void launch_maskgit_loss_combine(float* out, float weight, int with_critic, hipS
     LAUNCH_CHECK();
 }
 
+// ---------------------------------------------------------------------------------------------- classifier-free guidance
+// logits = null + (cond - null) * scale (muse_net:272-276) in place on the conditional logits: sub, mul and add each rounded once (no FMA), so that the fp32 torch expression
+// gives the same bits.  VEC: rows of whole, 16-byte aligned float4 (the vocabulary sizes of the model); else one element per step
+// (HIP's __fmul_rn / __fadd_rn are the plain operators and may be contracted like them: the contraction is switched off for this function instead)
+__device__ __forceinline__ float cfg_mix(float c, float n, float scale) {
+#pragma clang fp contract(off)
+    const float d = c - n;
+    const float m = d * scale;
+    return n + m;
+}
+
+template <bool VEC>
+__global__ __launch_bounds__(256) void cfg_combine_kernel(float* __restrict__ cond, int ldc, const float* __restrict__ nul, int ldn, long rows, int V, float scale) {
+    const int per_row = VEC ? V >> 2 : V;
+    const long n = rows * per_row;
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
+        const long row = i / per_row;
+        const int col = (int)(i - row * per_row);
+        if (VEC) {
+            float4* cp = reinterpret_cast<float4*>(cond + row * ldc) + col;
+            const float4 c = *cp, u = reinterpret_cast<const float4*>(nul + row * ldn)[col];
+            *cp = make_float4(cfg_mix(c.x, u.x, scale), cfg_mix(c.y, u.y, scale), cfg_mix(c.z, u.z, scale), cfg_mix(c.w, u.w, scale));
+        } else {
+            cond[row * ldc + col] = cfg_mix(cond[row * ldc + col], nul[row * ldn + col], scale);
+        }
+    }
+}
+void launch_cfg_combine(float* cond, int ldc, const float* null_logits, int ldn, long rows, int V, float scale, hipStream_t s) {
+    if (rows <= 0 || V <= 0) return;
+    BG_REQUIRE(ldc >= V && ldn >= V, "cfg_combine: leading dimensions %d / %d below V=%d", ldc, ldn, V);
+    const bool vec = V % 4 == 0 && ldc % 4 == 0 && ldn % 4 == 0 && (reinterpret_cast<uintptr_t>(cond) | reinterpret_cast<uintptr_t>(null_logits)) % 16 == 0;
+    const long n = rows * (vec ? V >> 2 : V);
+    const dim3 grid((unsigned)std::min<long>((n + 255) / 256, 8192));
+    if (vec) hipLaunchKernelGGL(cfg_combine_kernel<true>, grid, dim3(256), 0, s, cond, ldc, null_logits, ldn, rows, V, scale);
+    else hipLaunchKernelGGL(cfg_combine_kernel<false>, grid, dim3(256), 0, s, cond, ldc, null_logits, ldn, rows, V, scale);
+    LAUNCH_CHECK();
+}
+
 // the uniforms the samplers draw in registers, written out (tests: explicit-noise run == seeded run)
 __global__ void philox_fill_kernel(float* __restrict__ out, long n, unsigned long long seed, unsigned iter, unsigned stream, int V) {
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {

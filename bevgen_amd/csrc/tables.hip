@@ -314,6 +314,24 @@ void launch_pad_rows(const float* src, int ld_src, float* dst, int ld_dst, int r
     LAUNCH_CHECK();
 }
 
+// Route M null-condition pass (muse.cpp): with every layout token masked the cross-attention puts weight exactly 1 on the learned null key, so its block adds
+// r = to_out vec(null_v) to every row.  One wave per element of r: the `inner` products in fp64, lane-strided, then a fixed-order butterfly - run once per context
+__global__ __launch_bounds__(256) void muse_null_row_kernel(const float* __restrict__ to_out /* [D, inner] */, const float* __restrict__ null_v /* [inner] */, float* __restrict__ r,
+                                                            int D, int inner) {
+    const int lane = threadIdx.x & 63;
+    const int d = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (d >= D) return;
+    double acc = 0.0;
+    for (int k = lane; k < inner; k += 64) acc += (double)to_out[(long)d * inner + k] * (double)null_v[k];
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
+    if (lane == 0) r[d] = (float)acc;
+}
+void launch_muse_null_row(const float* to_out, const float* null_v, float* r, int D, int inner, hipStream_t s) {
+    hipLaunchKernelGGL(muse_null_row_kernel, dim3(cdiv(D, 4)), dim3(256), 0, s, to_out, null_v, r, D, inner);
+    LAUNCH_CHECK();
+}
+
 __global__ void fill_i64_kernel(int64_t* p, long n, int64_t v) {
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) p[i] = v;
 }

@@ -41,6 +41,8 @@ class Net2NetTransformer(_Base):
                  lr_decay: bool = False, sample_iterations: int = 18, **kwargs):
         super().__init__()
         runtime = pop_runtime_options(kwargs)     # precision / weights: handed down to the modules that own a Context (bevgen_amd/modules/options.py)
+        # classifier-free guidance of the sampler (`+model.guidance=null +model.cond_scale=3`): handed to MaskGit.generate by sample(); None = the MaskGit's own setting
+        self.guidance, self.cond_scale = kwargs.pop("guidance", None), kwargs.pop("cond_scale", None)
         for k, v in kwargs.items():
             if k != "self":
                 setattr(self, k, v)
@@ -98,8 +100,9 @@ class Net2NetTransformer(_Base):
             init_ids = torch.full_like(z, self.maskgit.mask_id)
             init_ids[:, partial_decoding_idx, :] = z[:, partial_decoding_idx]
             init_ids = init_ids.reshape(-1, z.shape[-1])
+        guided = {} if self.cond_scale is None else {"cond_scale": self.cond_scale}   # (absent: generate's default, the reference's 3)
         ids = self.maskgit.generate(init_ids=init_ids, cond_images=cond, fmap_size=(self.cfg.cam_latent_h, self.cfg.cam_latent_w), batch=batch,
-                                    timesteps=self.sample_iterations, noise=noise)
+                                    timesteps=self.sample_iterations, noise=noise, guidance=self.guidance, **guided)
         return ids
 
     @torch.no_grad()

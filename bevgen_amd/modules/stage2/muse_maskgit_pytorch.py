@@ -88,10 +88,12 @@ class SelfCritic(nn.Module):
 class MaskGit(RuntimeOptionsMixin, nn.Module):
     def __init__(self, image_size, transformer: MaskGitTransformerMultiView, noise_schedule: Callable = cosine_schedule, token_critic=None,
                  self_token_critic=False, cond_image_size=None, cond_drop_prob=0.5, self_cond_prob=0.9, no_mask_token_prob=0.0, critic_loss_weight=1.0,
-                 precision=None, weights=None):
+                 precision=None, weights=None, guidance=None):
         """muse_net:467-509 + the library's modes (``precision`` / ``weights``; bevgen_amd/modules/options.py): explicit here > given to the transformer >
-        $BEVGEN_PRECISION / $BEVGEN_WEIGHTS > f16x3 / f32."""
+        $BEVGEN_PRECISION / $BEVGEN_WEIGHTS > f16x3 / f32.  ``guidance``: None / 'off' = ``generate`` ignores ``cond_scale`` like the reference's eval mode does in
+        effect; 'null' = classifier-free guidance with a real null-condition forward (``generate``'s own keyword overrides this)."""
         super().__init__()
+        self.guidance = self._check_guidance(guidance)
         self._ctx: Optional[Context] = None
         opts = dict(getattr(transformer, "runtime_kwargs", {}))
         opts.update({k: v for k, v in (("precision", precision), ("weights", weights)) if v is not None})
@@ -110,6 +112,12 @@ class MaskGit(RuntimeOptionsMixin, nn.Module):
         self.critic_loss_weight = critic_loss_weight
         self.self_cond_prob = self_cond_prob
         self.no_mask_token_prob = no_mask_token_prob
+
+    @staticmethod
+    def _check_guidance(guidance):
+        if guidance not in (None, "off", "null"):
+            raise ValueError(f"guidance must be None, 'off' or 'null', got {guidance!r}")
+        return guidance
 
     # ---------------------------------------------------------------------------------- device context
     def load_state_dict(self, *a, **k):
@@ -141,14 +149,17 @@ class MaskGit(RuntimeOptionsMixin, nn.Module):
     @torch.no_grad()
     def generate(self, init_ids: Optional[torch.Tensor] = None, cond_images: Optional[torch.Tensor] = None, fmap_size=None, temperature=1.0,
                  topk_filter_thres=0.9, can_remask_prev_masked=False, force_not_use_token_critic=False, timesteps=12, cond_scale=3,
-                 critic_noise_scale=1, batch=None, noise=None, samples_per_layout=1):
-        """muse_net:511-627.  ``noise``: None -> stochastic like the reference (uniforms drawn in the sampler kernels, seeded from torch's generator);
+                 critic_noise_scale=1, batch=None, noise=None, samples_per_layout=1, guidance=None):
+        """muse_net:511-627.  ``guidance`` (None = the constructor's): 'null' honours ``cond_scale`` - every iteration also runs the forward with all layout tokens masked
+        out of the cross-attention and samples from null + (cond - null) * cond_scale; None / 'off' ignores ``cond_scale`` (the reference passes 3 everywhere, where its
+        eval-mode null forward equals the conditional one: muse_net:352).  ``noise``: None -> stochastic like the reference (uniforms drawn in the sampler kernels, seeded from torch's generator);
         an int -> that seed; 'greedy' -> gumbel noise 0 / critic uniform 0.5; or {'gumbel_u','critic_u'} explicit uniforms."""
         use_token_critic = self.token_critic is not None and not force_not_use_token_critic   # muse_net:553
         if not use_token_critic and can_remask_prev_masked:
             assert self.no_mask_token_prob > 0., 'without training with some of the non-masked tokens forced to predict, not sure if the logits will be meaningful for these token'   # muse_net:621
         cfg = self.transformer.cfg
         ctx = self.context()
+        guidance = self.guidance if guidance is None else self._check_guidance(guidance)
         if fmap_size is not None and tuple(fmap_size) != (cfg.cam_latent_h, cfg.cam_latent_w):
             raise ValueError(f"fmap_size {tuple(fmap_size)} != cam_latent_res {(cfg.cam_latent_h, cfg.cam_latent_w)}")
         B = len(cond_images)
@@ -167,12 +178,14 @@ class MaskGit(RuntimeOptionsMixin, nn.Module):
             gu, cu = noise["gumbel_u"], noise["critic_u"]
         return ctx.maskgit_generate(cond_images, batch["intrinsics_inv"], batch["extrinsics_inv"], timesteps=timesteps, temperature=temperature,
                                     topk_filter_thres=topk_filter_thres, critic_noise_scale=critic_noise_scale, gumbel_u=gu, critic_u=cu, init_ids=init_ids,
-                                    noise_seed=seed, use_token_critic=use_token_critic, can_remask_prev_masked=can_remask_prev_masked, samples_per_layout=samples_per_layout)
+                                    noise_seed=seed, use_token_critic=use_token_critic, can_remask_prev_masked=can_remask_prev_masked, samples_per_layout=samples_per_layout,
+                                    cond_scale=float(cond_scale) if guidance == "null" else None)
 
     @torch.no_grad()
-    def transformer_forward(self, x, conditioning_token_ids, batch, return_embed=False):
-        """TransformerMultiView.forward in eval mode (muse_net:283-371): x [(B*C),T] -> logits [(B*C),T,V] (and embed)."""
-        logits, embed = self.context().muse_forward(x, conditioning_token_ids, batch["intrinsics_inv"], batch["extrinsics_inv"])
+    def transformer_forward(self, x, conditioning_token_ids, batch, return_embed=False, null_condition=False):
+        """TransformerMultiView.forward in eval mode (muse_net:283-371): x [(B*C),T] -> logits [(B*C),T,V] (and embed).  null_condition: with every layout token masked
+        out of the cross-attention (what cond_drop_prob = 1 gives in training mode)."""
+        logits, embed = self.context().muse_forward(x, conditioning_token_ids, batch["intrinsics_inv"], batch["extrinsics_inv"], null_condition=null_condition)
         return (logits, embed) if return_embed else logits
 
     PHILOX_HOST_STREAM = 3   # noise=int: the mask times (elements 0 .. rows-1) and the temperature (element rows) come from this Philox stream at iteration 0

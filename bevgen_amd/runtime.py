@@ -238,7 +238,8 @@ class Context:
         self._finalized = True
 
     # ------------------------------------------------------------------------------------------ Route M
-    def muse_forward(self, ids, cond_ids, I_inv, E_inv, want_logits=True, want_embed=True, check=True):
+    def muse_forward(self, ids, cond_ids, I_inv, E_inv, want_logits=True, want_embed=True, check=True, null_condition=False):
+        """null_condition=True: the forward with every layout token masked out of the cross-attention (``bevgen_muse_forward_ex``), the null pass of classifier-free guidance."""
         cfg = self.cfg
         d = self.device
         ids = _req(ids, torch.int64, d, "ids")
@@ -249,13 +250,19 @@ class Context:
         rows = B * cfg.num_cams
         logits = torch.empty((rows, cfg.num_cam_tokens, cfg.vocab_size), dtype=torch.float32, device=d) if want_logits else None
         embed = torch.empty((rows, cfg.num_cam_tokens, cfg.num_embed), dtype=torch.float32, device=d) if want_embed else None
-        self._check(self.lib.bevgen_muse_forward(self._h, _ptr(ids), _ptr(cond_ids), _ptr(I_inv), _ptr(E_inv), B, _ptr(logits), _ptr(embed), self._s()))
+        if null_condition:
+            self._check(self.lib.bevgen_muse_forward_ex(self._h, _ptr(ids), _ptr(cond_ids), _ptr(I_inv), _ptr(E_inv), B, _ptr(logits), _ptr(embed), 1, self._s()))
+        else:
+            self._check(self.lib.bevgen_muse_forward(self._h, _ptr(ids), _ptr(cond_ids), _ptr(I_inv), _ptr(E_inv), B, _ptr(logits), _ptr(embed), self._s()))
         self._done(check)
         return logits, embed
 
     def maskgit_generate(self, cond_ids, I_inv, E_inv, *, timesteps=18, temperature=1.0, topk_filter_thres=0.9, critic_noise_scale=1.0,
-                         gumbel_u=None, critic_u=None, init_ids=None, noise_seed=0, use_token_critic=True, can_remask_prev_masked=False, samples_per_layout=1, check=True):
-        """gumbel_u / critic_u: explicit uniforms (parity tests); else noise_seed != 0: the samplers draw them in registers (Philox); else deterministic.
+                         gumbel_u=None, critic_u=None, init_ids=None, noise_seed=0, use_token_critic=True, can_remask_prev_masked=False, samples_per_layout=1, check=True,
+                         cond_scale=None):
+        """cond_scale: None or 1 = no guidance (``bevgen_maskgit_generate_ex``); else classifier-free guidance with the null-condition pass
+        (``bevgen_maskgit_generate_guided``): the logits of every iteration are null + (cond - null) * cond_scale.
+        gumbel_u / critic_u: explicit uniforms (parity tests); else noise_seed != 0: the samplers draw them in registers (Philox); else deterministic.
         use_token_critic=False: scores = 1 - softmax(logits)[pred] (muse_net:611-622; no critic forwards), can_remask_prev_masked as the reference's flag.
         samples_per_layout S: consecutive groups of S scenes share their condition (cross-attention K / V built once per layout)."""
         cfg = self.cfg
@@ -278,9 +285,13 @@ class Context:
             init_ids = _req(init_ids, torch.int64, d, "init_ids").reshape(rows, T)
         out = torch.empty((rows, T), dtype=torch.int64, device=d)
         score_mode = 0 if use_token_critic else (2 if can_remask_prev_masked else 1)
-        self._check(self.lib.bevgen_maskgit_generate_ex(self._h, _ptr(cond_ids), _ptr(I_inv), _ptr(E_inv), B, timesteps, sched_c, float(temperature),
-                                                         topk_count(topk_filter_thres, cfg.vocab_size), float(critic_noise_scale), _ptr(gumbel_u), _ptr(critic_u),
-                                                         _ptr(init_ids), _ptr(out), C.c_uint64(int(noise_seed) & 0xFFFFFFFFFFFFFFFF), score_mode, int(samples_per_layout), self._s()))
+        args = (self._h, _ptr(cond_ids), _ptr(I_inv), _ptr(E_inv), B, timesteps, sched_c, float(temperature), topk_count(topk_filter_thres, cfg.vocab_size),
+                float(critic_noise_scale), _ptr(gumbel_u), _ptr(critic_u), _ptr(init_ids), _ptr(out), C.c_uint64(int(noise_seed) & 0xFFFFFFFFFFFFFFFF), score_mode,
+                int(samples_per_layout))
+        if cond_scale is None or float(cond_scale) == 1.0:
+            self._check(self.lib.bevgen_maskgit_generate_ex(*args, self._s()))
+        else:
+            self._check(self.lib.bevgen_maskgit_generate_guided(*args, float(cond_scale), self._s()))
         self._done(check)
         return out.reshape(rows, cfg.cam_latent_h, cfg.cam_latent_w)
 
@@ -705,6 +716,24 @@ class Context:
         out = torch.empty((), dtype=torch.float32, device=self.device)
         self._check(self.lib.bevgen_op_mean_fixed_order(self._h, _ptr(x), x.numel(), _ptr(out), self._s()))
         return out
+
+    def op_add_row_layernorm(self, x, r, gamma, *, planes=False, ldy=None, rows=None, out=None):
+        """x [rows, D] += r [D] in place, then LayerNorm (gamma, eps 1e-5) of the updated rows -> fp32 [rows, ldy] or (planes) the raw plane image as int16
+        [rows, ldy / 32, 2, 32] (``bevgen_op_add_row_layernorm``).  ``rows`` < x.shape[0]: only the leading rows are touched; ``out``: a caller-owned result (never cleared)."""
+        D = x.shape[-1]
+        n = x.shape[0] if rows is None else int(rows)
+        ldy = D if ldy is None else int(ldy)
+        y = out
+        if y is None:
+            y = torch.empty((n, ldy // 32, 2, 32), dtype=torch.int16, device=self.device) if planes else torch.empty((n, ldy), dtype=torch.float32, device=self.device)
+        self._check(self.lib.bevgen_op_add_row_layernorm(self._h, _ptr(x), x.stride(0), _ptr(r), _ptr(gamma), _ptr(y), ldy, n, D, int(bool(planes)), self._s()))
+        return y
+
+    def op_cfg_combine(self, cond, null, scale, *, V=None):
+        """cond[:, :V] = null + (cond - null) * scale in place on 2-D fp32 tensors with row strides (``bevgen_op_cfg_combine``)."""
+        V = cond.shape[1] if V is None else int(V)
+        self._check(self.lib.bevgen_op_cfg_combine(self._h, _ptr(cond), cond.stride(0), _ptr(null), null.stride(0), cond.shape[0], V, float(scale), self._s()))
+        return cond
 
     def op_layernorm(self, x, gamma, beta=None, eps=1e-5):
         y = torch.empty_like(x)

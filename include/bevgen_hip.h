@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define BEVGEN_ABI_VERSION 10   /* 10 (additive, same version and struct): bevgen_vq_encode_ex, bevgen_op_vq_geo_embed, bevgen_op_vq_quant_error; a library without them is told apart by the missing symbols.  10: bevgen_cfg.vq_range covers bevgen_vq_encode (bevgen_vq_range_exponents reports the most recent decode OR encode call), bevgen_op_conv_ranged.  9: operator entries of the VQGAN building blocks (bevgen_op_conv3x3_down, _vq_attn_block, _vq_out_tail, _vq_quantize, _conv3x3_gn_stats), BEVGEN_STATUS_NONFINITE_LATENTS.  8: bevgen_cfg.vq_range (taken out of reserved[]: the struct size is unchanged), bevgen_vq_range_exponents, bevgen_op_range_split.  7: operator entries of the token samplers (bevgen_op_remask, _maskgit_pick, _critic_scores, _ar_pick, _ar_score_rows, _mean_fixed_order).  6: device status word (bevgen_synchronize, bevgen_status, BEVGEN_ERR_NUMERIC, BEVGEN_STATUS_*).  5: bevgen_op_mlp_fused; a context without max_batch <= 4 packs the split decode layer lazily (see Conventions).  4: 4: BEVGEN_PROFILE_KINDS 5 -> 6 (bevgen_profile_end writes 18 doubles), bevgen_cfg.decode_chains, decode_path values 2 / 3 */
+#define BEVGEN_ABI_VERSION 10   /* 10 (additive, same version and struct): classifier-free guidance of Route M - bevgen_maskgit_generate_guided, bevgen_muse_forward_ex, bevgen_op_add_row_layernorm, bevgen_op_cfg_combine; a library without them is told apart by the missing symbols.  10 (additive, same version and struct): bevgen_vq_encode_ex, bevgen_op_vq_geo_embed, bevgen_op_vq_quant_error; a library without them is told apart by the missing symbols.  10: bevgen_cfg.vq_range covers bevgen_vq_encode (bevgen_vq_range_exponents reports the most recent decode OR encode call), bevgen_op_conv_ranged.  9: operator entries of the VQGAN building blocks (bevgen_op_conv3x3_down, _vq_attn_block, _vq_out_tail, _vq_quantize, _conv3x3_gn_stats), BEVGEN_STATUS_NONFINITE_LATENTS.  8: bevgen_cfg.vq_range (taken out of reserved[]: the struct size is unchanged), bevgen_vq_range_exponents, bevgen_op_range_split.  7: operator entries of the token samplers (bevgen_op_remask, _maskgit_pick, _critic_scores, _ar_pick, _ar_score_rows, _mean_fixed_order).  6: device status word (bevgen_synchronize, bevgen_status, BEVGEN_ERR_NUMERIC, BEVGEN_STATUS_*).  5: bevgen_op_mlp_fused; a context without max_batch <= 4 packs the split decode layer lazily (see Conventions).  4: 4: BEVGEN_PROFILE_KINDS 5 -> 6 (bevgen_profile_end writes 18 doubles), bevgen_cfg.decode_chains, decode_path values 2 / 3 */
 
 enum { BEVGEN_ROUTE_MASKGIT = 0, BEVGEN_ROUTE_AR = 1 };
 /* FP32  : every product and accumulation in exact fp32 on the matrix cores (v_mfma_f32_32x32x2_f32) - bit-exact greedy tokens vs the CPU reference.
@@ -194,6 +194,13 @@ int bevgen_finalize(bevgen_ctx* ctx);
  *   -> d_logits [B*C, T, V] and/or d_embed [B*C, T, D] (either may be NULL). */
 int bevgen_muse_forward(bevgen_ctx* ctx, const int64_t* d_ids, const int64_t* d_cond_ids, const float* d_I_inv, const float* d_E_inv,
                         int B, float* d_logits, float* d_embed, void* stream);
+/* The same with null_condition != 0: the forward with context_mask = False for every scene (:158-166) - what the reference computes in .train() mode with
+ * cond_drop_prob = 1 (:352-354), the "null" forward of classifier-free guidance.  No layout token is visible to the cross-attention, whose softmax then puts weight exactly 1
+ * on the learned null key (exp(-finfo.max - finite) is 0 in fp32): layer i's cross-attention block adds r_i = to_out_i vec(null_v_i) to every row, a [D] vector that
+ * bevgen_finalize computes once (fp64 accumulation, from the to_out matrix the context's mode multiplies by).  Self-attention, feed-forward, the final LayerNorm and
+ * to_logits are bevgen_muse_forward's.  null_condition == 0 is bevgen_muse_forward. */
+int bevgen_muse_forward_ex(bevgen_ctx* ctx, const int64_t* d_ids, const int64_t* d_cond_ids, const float* d_I_inv, const float* d_E_inv,
+                           int B, float* d_logits, float* d_embed, int null_condition, void* stream);
 
 /* MaskGit.generate with the self token critic (stage2/muse_maskgit_pytorch.py:511-627).
  *   h_mask_schedule[timesteps]  tokens re-masked at each iteration, max(int(cos(pi/2 t) T), 1) (:566-567) - host-computed
@@ -206,7 +213,8 @@ int bevgen_muse_forward(bevgen_ctx* ctx, const int64_t* d_ids, const int64_t* d_
  *   d_init_ids [B*C, T] or NULL (partial decoding, :543-544, 573-574)
  *   -> d_out_ids [B*C, T]
  * The classifier-free-guidance "null" forwards of the reference (:272-276, 394-396) are bit-identical to the conditional
- * ones in eval mode and are not executed; the critic forward after the last iteration (result unused) is skipped. */
+ * ones in eval mode and are not executed; the critic forward after the last iteration (result unused) is skipped.  Guidance with a real null-condition forward is
+ * bevgen_maskgit_generate_guided (below). */
 int bevgen_maskgit_generate(bevgen_ctx* ctx, const int64_t* d_cond_ids, const float* d_I_inv, const float* d_E_inv, int B,
                             int timesteps, const int32_t* h_mask_schedule, float temperature, int topk_k, float critic_noise_scale,
                             const float* d_gumbel_u, const float* d_critic_u, const int64_t* d_init_ids, int64_t* d_out_ids,
@@ -224,6 +232,16 @@ int bevgen_maskgit_generate_ex(bevgen_ctx* ctx, const int64_t* d_cond_ids, const
                                int timesteps, const int32_t* h_mask_schedule, float temperature, int topk_k, float critic_noise_scale,
                                const float* d_gumbel_u, const float* d_critic_u, const int64_t* d_init_ids, int64_t* d_out_ids,
                                unsigned long long noise_seed, int score_mode, int samples_per_layout, void* stream);
+
+/* bevgen_maskgit_generate_ex with classifier-free guidance (opt-in; departs from the reference's eval-mode behaviour, whose null forward equals the conditional one):
+ * every iteration also runs the null-condition pass of bevgen_muse_forward_ex over the same ids and the logits the iteration uses - top-k filter, gumbel pick and the
+ * 1 - softmax(logits)[pred] scores of score_mode 1 / 2 - are null + (cond - null) * cond_scale, evaluated in fp32 as three separately rounded operations (sub, mul, add).
+ * The token critic reads the CONDITIONAL embed (SelfCritic.forward_with_cond_scale, :272, 394-396): its forward is the one of the unguided call.  Per iteration:
+ * conditional forward + null pass (+ critic forward).  cond_scale == 1 runs exactly the launches of bevgen_maskgit_generate_ex. */
+int bevgen_maskgit_generate_guided(bevgen_ctx* ctx, const int64_t* d_cond_ids, const float* d_I_inv, const float* d_E_inv, int B,
+                                   int timesteps, const int32_t* h_mask_schedule, float temperature, int topk_k, float critic_noise_scale,
+                                   const float* d_gumbel_u, const float* d_critic_u, const int64_t* d_init_ids, int64_t* d_out_ids,
+                                   unsigned long long noise_seed, int score_mode, int samples_per_layout, float cond_scale, void* stream);
 
 /* MaskGit.forward in eval mode (stage2/muse_maskgit_pytorch.py:629-729; no condition drop, no self conditioning): the validation losses.
  *   d_ids [B*C, T]              the ground-truth token ids
@@ -382,6 +400,13 @@ int bevgen_op_muse_ff(bevgen_ctx* ctx, const float* d_x, const float* d_w1, cons
  * [D, ldy) zero); geglu != 0: d_x is [rows, 2 D] = (a | gate), row stride ldx, and the rows normalised are gate * gelu(a) (no beta). */
 int bevgen_op_layernorm_planes(bevgen_ctx* ctx, const float* d_x, int ldx, const float* d_gamma, const float* d_beta /* or NULL */, void* d_planes, int ldy, int rows, int D,
                                int geglu, void* stream);
+/* The null-condition pass's stand-in for a cross-attention block and the LayerNorm behind it: d_x[row, 0:D] += d_r[0:D] (written back), then LayerNorm (gamma, eps 1e-5) of
+ * the updated row into d_y - fp32 rows [rows, ldy] (planes == 0) or the plane image of bevgen_op_layernorm_planes (planes != 0, ldy % 32 == 0); columns [D, ldy) zero.
+ * The bits of an fp32 add followed by bevgen_op_layernorm / bevgen_op_layernorm_planes.  D % 4 == 0, 16-byte aligned pointers. */
+int bevgen_op_add_row_layernorm(bevgen_ctx* ctx, float* d_x, int ldx, const float* d_r, const float* d_gamma, void* d_y, int ldy, int rows, int D, int planes, void* stream);
+/* Classifier-free guidance on logits: d_cond[row, 0:V] = d_null + (d_cond - d_null) * cond_scale in place (fp32 sub, mul, add, each rounded once); row strides ldc / ldn,
+ * columns [V, ldc) untouched. */
+int bevgen_op_cfg_combine(bevgen_ctx* ctx, float* d_cond, int ldc, const float* d_null, int ldn, long rows, int V, float cond_scale, void* stream);
 /* Decode-step projection (decode_fused.hip): C = act(LayerNorm?(A) W^T + bias) for M <= 64 rows; d_ln_w NULL = no LayerNorm; ksplit > 1 (no LayerNorm, no bias / act):
  * d_c receives the split-K partial sums [ksplit, M, N] that the consumer adds; ksplit 0 = the library's choice for (N, K), returned through *ksplit_out if non-NULL;
  * ksplit -1 (LayerNorm with beta and bias): one K slice, the LayerNorm folded into the product the way the decode step launches ln2 + MLP-up.
