@@ -754,6 +754,40 @@ int bevgen_op_attention_ex(bevgen_ctx* ctx, const float* q, const float* k, cons
     });
 }
 
+int bevgen_op_muse_attention(bevgen_ctx* ctx, const void* qh, const void* ql, const void* kh, const void* kl, const void* vth, const void* vtl, const float* bias, int ldbias,
+                             int B, int H, int Nq, int Nk_pad, int kv_group, int key_splits, float* out, void* out_planes, void* stream) {
+    return guarded(ctx, [&] {
+        hipStream_t s = (hipStream_t)stream;
+        auto al16 = [](const void* p) { return reinterpret_cast<uintptr_t>(p) % 16 == 0; };
+        BG_REQUIRE(ctx->cfg.precision == BEVGEN_PRECISION_F16X3, "op_muse_attention: needs a split-precision (f16x3) context");
+        BG_REQUIRE(qh && ql && kh && kl && vth && vtl && B >= 1 && H >= 1 && Nq >= 1 && Nk_pad >= 32 && Nk_pad % 32 == 0 && (long)B * H * std::max(Nq, Nk_pad) * 64 < (1L << 30),
+                   "op_muse_attention: bad arguments (planes Qh / Ql [B,H,Nq,64], Kh / Kl [B/kv_group,H,Nk_pad,64], VTh / VTl [B/kv_group,H,64,Nk_pad], Nk_pad %% 32)");
+        BG_REQUIRE(al16(qh) && al16(ql) && al16(kh) && al16(kl) && al16(vth) && al16(vtl) && al16(bias) && al16(out) && al16(out_planes), "op_muse_attention: every pointer must be 16-byte aligned");
+        BG_REQUIRE(bias == nullptr || (ldbias % 4 == 0 && ldbias >= Nk_pad), "op_muse_attention: bias row stride %d must be a multiple of 4 and >= Nk_pad = %d", ldbias, Nk_pad);
+        BG_REQUIRE(kv_group >= 1 && B % kv_group == 0, "op_muse_attention: batch %d is not a multiple of kv_group %d", B, kv_group);
+        BG_REQUIRE(key_splits >= 1 && key_splits <= 8 && key_splits <= Nk_pad / 32, "op_muse_attention: key_splits=%d out of range (1..8, at most Nk_pad / 32 = %d)", key_splits, Nk_pad / 32);
+        BG_REQUIRE((out != nullptr) != (out_planes != nullptr), "op_muse_attention: exactly one of d_out and d_out_planes must be given");
+        float* pk;
+        AttnSplitArgs sa{};
+        ctx->arena.carve([&](Arena& ar) {
+            pk = bias ? ar.get<float>((size_t)attn_bias_packed_floats(Nq, Nk_pad)) : nullptr;
+            sa.kws = key_splits > 1 ? ar.get<float>((size_t)attn_split_ws_floats(B, H, Nq, key_splits)) : nullptr;
+        });
+        if (bias) launch_pack_attn_bias(bias, ldbias, Nq, Nk_pad, pk, s);
+        // (muse.cpp attn_args, self_attention_split / cross_attention_split)
+        sa.Qh = reinterpret_cast<const _Float16*>(qh); sa.Ql = reinterpret_cast<const _Float16*>(ql);
+        sa.Kh = reinterpret_cast<const _Float16*>(kh); sa.Kl = reinterpret_cast<const _Float16*>(kl);
+        sa.VTh = reinterpret_cast<const _Float16*>(vth); sa.VTl = reinterpret_cast<const _Float16*>(vtl);
+        sa.bias = bias; sa.bias_pk = pk; sa.ldbias = ldbias; sa.bias_head_stride = 0;
+        sa.O = out; sa.Op = reinterpret_cast<_Float16*>(out_planes);
+        sa.B = B; sa.H = H; sa.Nq = Nq; sa.Nk_pad = Nk_pad; sa.scale = 8.0f * kLog2e;
+        sa.o_bstride = (long)Nq * H * 64; sa.o_qstride = (long)H * 64; sa.o_hstride = 64;
+        sa.kv_group = kv_group;
+        sa.ksplit = key_splits;
+        launch_attention_split(sa, s);
+    });
+}
+
 int bevgen_op_decode_attention(bevgen_ctx* ctx, const float* q, const void* kc, const void* vc, int kv_dtype, const float* bias, int ldbias, const uint8_t* keep,
                                int ldkeep, long keep_head_stride, int B, int H, int n, int Lmax, float scale, float* out, void* stream) {
     return guarded(ctx, [&] {

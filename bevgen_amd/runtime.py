@@ -757,6 +757,15 @@ class Context:
                                                     self._s()))
         return out
 
+    def op_muse_attention(self, planes, bias, *, B, H, Nq, Nk_pad, kv_group=1, key_splits=1, out=None, out_planes=None):
+        """Route M's split-precision attention as the model launches it, on the f16 planes of op_muse_qkv: planes = dict Qh, Ql [B, H, Nq, 64]; Kh, Kl [B / kv_group, H,
+        Nk_pad, 64]; VTh, VTl [B / kv_group, H, 64, Nk_pad].  bias [Nq, ld] fp32 or None: base-2 domain, -1e30 = hidden (include/bevgen_hip.h).  Exactly one of `out`
+        (fp32 [B, Nq, 64 H]) and `out_planes` (f16 image [B Nq, 64 H / 32, 2, 32]), both caller-owned and never cleared."""
+        ld = 0 if bias is None else bias.shape[-1]
+        self._check(self.lib.bevgen_op_muse_attention(self._h, _ptr(planes["Qh"]), _ptr(planes["Ql"]), _ptr(planes["Kh"]), _ptr(planes["Kl"]), _ptr(planes["VTh"]),
+                                                      _ptr(planes["VTl"]), _ptr(bias), int(ld), int(B), int(H), int(Nq), int(Nk_pad), int(kv_group), int(key_splits), _ptr(out),
+                                                      _ptr(out_planes), self._s()))
+
     @staticmethod
     def _cache_lmax(kcache, kv_dtype, Lmax):
         # kv_dtype 2 (int8): the cache is a flat uint8 buffer in the BEVGEN_KV_I8 layout (codes, then row scales) and says nothing about Lmax

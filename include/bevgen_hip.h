@@ -457,6 +457,18 @@ int bevgen_op_attention(bevgen_ctx* ctx, const float* d_q, const float* d_k, con
  * the Route M model path picks for its self-attention at one scene per call (muse.cpp pick_attn_ksplit); fp32-precision contexts ignore key_splits. */
 int bevgen_op_attention_ex(bevgen_ctx* ctx, const float* d_q, const float* d_k, const float* d_v, const float* d_bias, int ldbias,
                            int B, int H, int Nq, int Nk_pad, float scale, int key_splits, float* d_out, void* stream);
+/* Route M's split-precision attention kernel (attention_split.hip) launched the way muse.cpp launches it (attn_args, self_attention_split / cross_attention_split) on
+ * caller-owned f16 planes - what bevgen_op_muse_qkv writes: Qh / Ql [B, H, Nq, 64] with the score scale (x log2 e) folded in, Kh / Kl [B / kv_group, H, Nk_pad, 64],
+ * VTh / VTl [B / kv_group, H, 64, Nk_pad]; batch element b reads K / V slot b / kv_group (kv_group >= 1 divides B).  d_bias [Nq, ldbias] (or NULL; ldbias % 4 == 0,
+ * ldbias >= Nk_pad) is the matrix the context hands to the kernel's bias packer: in the base-2 domain (already multiplied by log2 e), -1e30 = hidden, every column the
+ * kernel must not see (from the last key on) hidden; it is not rescaled here, only packed into scratch.  Rows / columns of K / V^T behind the last visible key may hold
+ * any finite values.  key_splits 1..8 and <= Nk_pad / 32: the key tiles in that many ranges and the combine kernel.  Exactly one output: d_out fp32 [B, Nq, 64 H], or
+ * d_out_planes, the f16 image [B Nq][64 H / 32][hi 32 | lo 32] the to_out projection reads - (hi, lo) of the same fp32 values, bit for bit; an output value outside the
+ * f16 range raises BEVGEN_STATUS_F16_RANGE in the plane form.  Nothing is cleared or pre-filled; every pointer 16-byte aligned.  f16x3 contexts only; unsupported
+ * arguments return BEVGEN_ERR_INVALID without a launch. */
+int bevgen_op_muse_attention(bevgen_ctx* ctx, const void* d_qh, const void* d_ql, const void* d_kh, const void* d_kl, const void* d_vth, const void* d_vtl,
+                             const float* d_bias /* or NULL */, int ldbias, int B, int H, int Nq, int Nk_pad, int kv_group, int key_splits, float* d_out /* or NULL */,
+                             void* d_out_planes /* or NULL */, void* stream);
 int bevgen_op_decode_attention(bevgen_ctx* ctx, const float* d_q, const void* d_kcache, const void* d_vcache, int kv_dtype,
                                const float* d_bias, int ldbias, const uint8_t* d_keep, int ldkeep, long keep_head_stride,
                                int B, int H, int n, int Lmax, float scale, float* d_out, void* stream);
